@@ -11,10 +11,13 @@ the row bands when N > 1].  Model fitting (Step 1) is out of scope.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (algorithmic work per
-launch from SURVEY.md section 8d divided by its HIP-event duration on the launch stream);
-`cpu_baseline` is the oracle's C restatement timed on this box's host cores on a bounded
-sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints
+the headline (`value`, `ms_per_step`, the configuration, lambda and R^2 of the last step).
+With --full the line also carries the records that take runs of their own: `roofline`
+describes the dominant kernel (algorithmic work per launch from SURVEY.md section 8d divided
+by its HIP-event duration on the launch stream); `cpu_baseline` is the oracle's C restatement
+timed on this box's host cores on a bounded sample of the same workload.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import contextlib
@@ -128,7 +131,62 @@ def parse():
                          "(mhs_init_devices + mhs_mltps_grid_multi_dev / mhs_tiles_units_multi: the path the single-threaded R host "
                          "takes) instead of one process per GPU under torch.distributed; with fewer physical devices than --gpus "
                          "the slots share devices (plumbing only, flagged in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every record of the line as well: per-kernel table and roofline, stand-alone fit, "
+                         "reference-tiled Step 3, float64 boundary, raster sensitivity, direct-sum check, projections, the CPU "
+                         "baseline (unless --no-cpu-baseline), and at N > 1 the phase table and model check.  Off: set-up, warm-up, "
+                         "the timed steps and the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them handed its caller as DIR/<name>.npy (float64; "
+                         "planes sampled at a fixed, seeded set of cells)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 22      # cells of the output planes --dump-outputs writes, shared by all planes (float64: 32 MB in all)
+
+
+def dump_outputs(path, planes, values):
+    """--dump-outputs: `planes` (device tensors or host arrays) are written at DUMP_SAMPLE // len(planes) cells each, drawn
+    without replacement by a fixed seed from the flattened plane and sorted (the whole plane when it is smaller), so that
+    the same arguments give the same cells in every run; `values` (scalars, small arrays) are written whole.  float64."""
+    os.makedirs(path, exist_ok=True)
+    per = max(1, DUMP_SAMPLE // max(1, len(planes)))
+    for name, a in planes.items():
+        n = int(np.prod(a.shape))
+        idx = None if n <= per else np.sort(np.random.default_rng(0).choice(n, per, replace=False))
+        if hasattr(a, "cpu"):
+            import torch
+            flat = a.reshape(-1)
+            v = (flat if idx is None else flat[torch.from_numpy(idx).to(flat.device)]).cpu().numpy()
+        else:
+            flat = np.asarray(a).reshape(-1)
+            v = flat if idx is None else flat[idx]
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+    for name, v in values.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
+def step_outputs(last):
+    """(planes, values) of a Workload / TileWorkload step's result, for dump_outputs."""
+    if "layers" in last:       # TileWorkload: the merged plane of every response layer this rank owns
+        return ({"layer_%02d" % l: p for l, p in sorted(last["layers"].items())},
+                {"rsq_model": last["rsq_model"], "rsq_final": last["rsq_final"]})
+    return {"final": last["final"]}, {k: v for k, v in last.items() if k != "final" and v is not None}
+
+
+def ensemble_params(synth, X, y, seed, n_gbm_trees, n_rf_trees):
+    """synth.ensemble_params(X, y, seed, ...), the same dicts in the same order.  Every member draws from a generator of its
+    own, so at full size the two tree members -- tens of seconds of single-threaded host work each -- are made in child
+    processes (spawned: they never touch the GPU) while this one makes the other four."""
+    if n_rf_trees * X.shape[0] < 10 ** 6:
+        return synth.ensemble_params(X, y, seed, n_gbm_trees=n_gbm_trees, n_rf_trees=n_rf_trees)
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(2, mp_context=multiprocessing.get_context("spawn")) as pool:
+        gbm = pool.submit(synth.gbm_params, X, y, seed, n_trees=n_gbm_trees)
+        rf = pool.submit(synth.rf_params, X, y, seed, n_trees=n_rf_trees)
+        rest = synth.ensemble_params(X, y, seed, which="gnmv")
+        return [gbm.result()] + rest[:3] + [rf.result(), rest[3]]
 
 
 class Workload:
@@ -146,7 +204,7 @@ class Workload:
         X = np.column_stack([cov, self.xy])
         if cfg["ensemble"]:
             self.resp = synth.response(X, uv, seed)
-            self.params = synth.ensemble_params(X, self.resp, seed, n_gbm_trees=cfg["gbm_trees"], n_rf_trees=cfg["rf_trees"])
+            self.params = ensemble_params(synth, X, self.resp, seed, cfg["gbm_trees"], cfg["rf_trees"])
             _, self.weights, self.wt_total = mhs.models.select_weights(synth.OPTX_WEIGHTS)
         else:  # TPS only: a zero "ensemble" (lm with zero coefficients, weight 1) so resp IS the residual
             self.resp = synth.tps_residual(uv, seed)
@@ -1124,11 +1182,19 @@ def main_in_library(args, require_distinct=False):
     if dist is not None:
         dist.barrier()
     line.update({"value": cells * args.steps / dt / 1e6, "ms_per_step": dt / args.steps * 1e3, "config": config})
+    if args.dump_outputs:
+        if cfg.get("tiled"):
+            dump_outputs(args.dump_outputs, {"layer_%02d" % l: p for l, p in enumerate(last[0])},
+                         {"rsq_model": last[1][:, :, 0], "rsq_final": last[1][:, :, 1]})
+        else:
+            dump_outputs(args.dump_outputs, {"final": ms.download()},
+                         {k: last[k] for k in ("lambda", "rsq_model", "rsq_final") if last.get(k) is not None})
     if cfg.get("tiled"):
         outs, rsq, uinfo = last
         driver.update(uinfo)
-        line.update({"rsq_model_mean": float(np.nanmean(rsq[:, :, 0])), "rsq_final_mean": float(np.nanmean(rsq[:, :, 1])),
-                     "roofline": None, "cpu_baseline": None})
+        line.update({"rsq_model_mean": float(np.nanmean(rsq[:, :, 0])), "rsq_final_mean": float(np.nanmean(rsq[:, :, 1]))})
+        if args.full:
+            line.update({"roofline": None, "cpu_baseline": None})
     else:
         driver.update({k: last[k] for k in ("bands", "band_ms", "tiles_ms", "tiles_owned", "tiles_pulled_bytes", "fit_ms", "step_ms", "collective",
                                              "suggested_slot0_share")})
@@ -1143,6 +1209,13 @@ def main_in_library(args, require_distinct=False):
             sys.stderr.write("bench.py: %d distinct devices but the step's collective was '%s', not the RCCL all-gather\n" % (N, last["collective"]))
             sys.exit(4)
         line.update({"lambda": last["lambda"], "rsq_model": last["rsq_model"], "rsq_final": last["rsq_final"]})
+        if not args.full:      # the headline only: the records below take runs of their own
+            ms.free()
+            line["in_library"] = driver
+            emit_line(line)
+            if dist is not None:
+                dist.destroy_process_group()
+            return
         # the dominant kernel's roofline: the slots launch the kernels of the one-device step on their bands; the member-by-member
         # HIP-event table is taken from that step on slot 0's device over the whole grid (outside the timed region)
         for _ in range(2):
@@ -1237,6 +1310,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *step_outputs(wl.last))
 
     if cfg.get("tiled"):
         if rank == 0:
@@ -1257,17 +1332,56 @@ def main():
                 "units_on_rank0": len(unit), "unit_ms_mean_rank0": float(np.mean(list(unit.values()))) if unit else None,
                 "unit_ms_max_rank0": float(np.max(list(unit.values()))) if unit else None,
                 "rsq_model_mean": float(np.nanmean(out["rsq_model"])), "rsq_final_mean": float(np.nanmean(out["rsq_final"])),
-                "roofline": None, "cpu_baseline": None,
             }
-            prof = wl.unit_profile()
-            dom = max(prof["kernels"], key=lambda r: r["launch_ms"]) if prof["kernels"] else None
-            res["unit_profile"] = prof
-            res["roofline"] = ({k: dom[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "work", "issue_view")
-                                if k in dom} if dom else None)
-            if res["roofline"] is not None:
-                res["roofline"].setdefault("traffic", None)
-            if not args.no_cpu_baseline and world == 1:
-                res["cpu_baseline"] = wl.cpu_baseline(res["ms_per_step"])
+            if args.full:
+                res.update({"roofline": None, "cpu_baseline": None})
+                prof = wl.unit_profile()
+                dom = max(prof["kernels"], key=lambda r: r["launch_ms"]) if prof["kernels"] else None
+                res["unit_profile"] = prof
+                res["roofline"] = ({k: dom[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "work", "issue_view")
+                                    if k in dom} if dom else None)
+                if res["roofline"] is not None:
+                    res["roofline"].setdefault("traffic", None)
+                if not args.no_cpu_baseline and world == 1:
+                    res["cpu_baseline"] = wl.cpu_baseline(res["ms_per_step"])
+            emit_line(res)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    def headline():
+        return {
+            "metric": "grid Mcells/s (ensemble+TPS predict) + TPS-solve GFLOP/s",
+            "value": wl.cells * args.steps / dt / 1e6,
+            "unit": "Mcells/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": cfg["name"], "stations": cfg["stations"], "grid": [cfg["side"], cfg["side"]],
+                       "covariates": "%d x float32 planes resident in HBM" % cfg["layers"],
+                       "members": [p["kind"] for p in wl.params], "gbm_trees": cfg["gbm_trees"], "rf_trees": cfg["rf_trees"],
+                       "tps_mode": ("global (one fit on all stations, GCV lambda, V73:748-753)" if args.tps_mode == "global" else
+                                    "reference-tiled (ceil(n/1500)^2 overlapping tiles with their own GCV fits, mosaic, feathering, V73:636-897), tiles dealt over the ranks"),
+                       "parallelism": ("rowband%d + bcast(coef) + 1 all-gather" if args.tps_mode == "global" else
+                                       "rowband%d + Step-3 tiles dealt over the ranks + 1 all-gather") % world,
+                       "rank0_row_share": wl.rank0_share, "fit_reservation": wl.reservation},
+        }
+
+    def check_rsq():
+        if cfg["ensemble"] and wl.cfg["stations"] >= 2000:
+            # the synthetic members are fitted, not random: the ensemble explains the response and the spline improves on it
+            assert 0.5 < wl.last["rsq_model"] < wl.last["rsq_final"], (wl.last["rsq_model"], wl.last["rsq_final"])
+
+    if not args.full:      # the headline only: every record below takes runs of its own
+        if rank == 0:
+            check_rsq()
+            res = headline()
+            res.update({"lambda": wl.last.get("lambda"), "rsq_model": wl.last["rsq_model"], "rsq_final": wl.last["rsq_final"]})
             emit_line(res)
         if world > 1:
             dist.barrier()
@@ -1436,28 +1550,9 @@ def main():
                 projected["n%d" % N] = {"rank0_band_ms": x, "other_band_ms": others, "spline_band_ms": spl / N, "gather_ms": gather, "step_ms": step,
                                         "mcells_per_s": wl.cells / step / 1e3, "speedup_over_n1": step1 / step}
         m = wl.ops.X.shape[0] - 3
-        if cfg["ensemble"] and wl.cfg["stations"] >= 2000:
-            # the synthetic members are fitted, not random: the ensemble explains the response and the spline improves on it
-            assert 0.5 < wl.last["rsq_model"] < wl.last["rsq_final"], (wl.last["rsq_model"], wl.last["rsq_final"])
-        res = {
-            "metric": "grid Mcells/s (ensemble+TPS predict) + TPS-solve GFLOP/s",
-            "value": wl.cells * args.steps / dt / 1e6,
-            "unit": "Mcells/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": cfg["name"], "stations": cfg["stations"], "grid": [cfg["side"], cfg["side"]],
-                       "covariates": "%d x float32 planes resident in HBM" % cfg["layers"],
-                       "members": [p["kind"] for p in wl.params], "gbm_trees": cfg["gbm_trees"], "rf_trees": cfg["rf_trees"],
-                       "tps_mode": ("global (one fit on all stations, GCV lambda, V73:748-753)" if args.tps_mode == "global" else
-                                    "reference-tiled (ceil(n/1500)^2 overlapping tiles with their own GCV fits, mosaic, feathering, V73:636-897), tiles dealt over the ranks"),
-                       "parallelism": ("rowband%d + bcast(coef) + 1 all-gather" if args.tps_mode == "global" else
-                                       "rowband%d + Step-3 tiles dealt over the ranks + 1 all-gather") % world,
-                       "rank0_row_share": wl.rank0_share, "fit_reservation": wl.reservation},
+        check_rsq()
+        res = headline()
+        res.update({
             "roofline": ({k: dom[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "work", "pmc",
                                                "ops_view", "issue_view") if k in dom} if dom else None),  # None only if rank 0 was given no rows at all
             "kernels": table,
@@ -1474,7 +1569,7 @@ def main():
             "f64_boundary": f64_boundary, "raster_sensitivity": raster_sensitivity, "model_check": model_check, "projected": projected,
             "tiled_mode_same_run": tiled_mode,
             "lambda": wl.last.get("lambda"), "rsq_model": wl.last["rsq_model"], "rsq_final": wl.last["rsq_final"],
-        }
+        })
         if not args.no_cpu_baseline and world == 1:   # timed on rank 0 at N = 1 only
             ff = next((r["launch_ms"] for r in table if r["kernel"].startswith("tps_ff")), None)
             res["cpu_baseline"] = wl.cpu_baseline(res["ms_per_step"], eval_check["direct_sum_ms"] if eval_check else None, ff)

@@ -1,6 +1,7 @@
 """CPU: the GeoTIFF reader/writer (host functions of the C ABI, no GPU) against libtiff via Pillow:
-the reference's own bundled rasters (tiled, deflate, INT2S, NoData -32768, four overview levels) when
-/root/reference is present, and Pillow-written fixtures for strips / LZW / deflate / float32."""
+the reference's own bundled rasters (tiled, deflate, INT2S, NoData -32768, four overview levels; their
+north-west corners, cut out tile by tile by tests/golden/make_geotiff_overviews.py), and Pillow-written
+fixtures for strips / LZW / deflate / float32."""
 import os
 
 import numpy as np
@@ -10,16 +11,16 @@ from PIL import Image
 import machisplin_amd as mhs
 from machisplin_amd import io as mio
 
-REF = "/root/reference/inst/extdata"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF = os.path.join(GOLD, "extdata_ovr")
 Image.MAX_IMAGE_PIXELS = None
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "TWI.tif.ovr")), reason="reference data not mounted")
 @pytest.mark.parametrize("name", ["TWI.tif.ovr", "slope.tif.ovr"])
 def test_bundled_overviews_decode_like_libtiff(name):
     path = os.path.join(REF, name)
     info = mio.tiff_info(path)
-    assert (info["width"], info["height"], info["bits"], info["sample_format"]) == (1632, 1238, 16, 2)
+    assert (info["width"], info["height"], info["bits"], info["sample_format"]) == (300, 200, 16, 2)
     im = Image.open(path)
     assert info["compression"] == 8 and info["n_ifd"] == 4 and info["dtype"] == mhs._lib.I16
     assert info["nodata"] == float(im.tag_v2[42113])  # GDAL_NODATA: -32768 for TWI (slope.tif.ovr carries 65536)
@@ -29,11 +30,14 @@ def test_bundled_overviews_decode_like_libtiff(name):
         got = mio.read_host(path, ifd)
         assert got.dtype == np.int16 and got.shape == want.shape
         assert np.array_equal(got.astype(np.int64), want.astype(np.int64))
+        if ifd == 0:    # the cut is the whole raster's corner: level 0 as cfg1_extdata.npz holds it (decoded from the full file)
+            whole = np.load(os.path.join(GOLD, "cfg1_extdata.npz"))[name.split(".")[0]]
+            assert np.array_equal(got, whole[:200, :300])
     # georeference from the .tfw sidecar of the base raster (inst/extdata/TWI.tfw, alt.tfw)
     g = mio.geometry_of(path)
     w = mio.world_file(os.path.join(REF, name.split(".")[0] + ".tfw"))
     assert w["xres"] == pytest.approx(0.0008333333) and g.xres == pytest.approx(2 * w["xres"])
-    assert g.xmin == pytest.approx(-77.7435765934 - 0.5 * 0.0008333333) and (g.nrow, g.ncol) == (1238, 1632)
+    assert g.xmin == pytest.approx(-77.7435765934 - 0.5 * 0.0008333333) and (g.nrow, g.ncol) == (200, 300)
 
 
 @pytest.mark.parametrize("comp", ["raw", "tiff_lzw", "tiff_adobe_deflate"])

@@ -193,7 +193,7 @@ def _run_bench(world, workload, port, extra=()):
     env = dict(os.environ, MHS_BENCH_BACKEND="gloo", MHS_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--workload", workload,
-           "--steps", "2", "--warmup", "1", *extra]
+           "--steps", "2", "--warmup", "1", "--full", *extra]
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=root)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]

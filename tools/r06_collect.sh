@@ -2,6 +2,7 @@
 # round 6: the evidence set for profiles/ (run on the GPU box through gpurun; results land in gpurun_out/r06_final/, copied to profiles/r06_*)
 #   bash tools/r06_collect.sh [all|gputest|bench|benchmore|inlib|fit|pmc|fitpmc|forest|forestpmc|memberspmc|cfg5]
 cd "$GRAFT_REPO_ROOT"
+ROOT=$(pwd)
 O=gpurun_out/r06_final
 mkdir -p $O
 export TMPDIR=/tmp
@@ -20,35 +21,35 @@ if [ "$PART" = all ] || [ "$PART" = gputest ]; then
   timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -v "^/opt" | tail -25 > $O/gputest_full.log; tail -3 $O/gputest_full.log
 fi
 if [ "$PART" = all ] || [ "$PART" = bench ]; then
-  timeout 900 python bench.py > $O/bench_cfg3_n1.json 2> $O/bench_cfg3_n1.err; tail -c 300 $O/bench_cfg3_n1.json; echo
+  timeout 900 python bench.py --full > $O/bench_cfg3_n1.json 2> $O/bench_cfg3_n1.err; tail -c 300 $O/bench_cfg3_n1.json; echo
   # the timed steps alone under rocprofv3 (the line's extra records -- float64 boundary, raster sensitivity -- launch the same
   # kernels on other windows and would blur the per-kernel statistics): the line's HIP-event launch times and the profiler's
   # durations of the full-grid dispatches from ONE run on ONE box
   # (MHS_RESERVE_KEEP=1: under the profiler, creating and destroying the CU-masked streams in every step -- what lifting the
   # reservation does since this round -- made every kernel of the run 3 x slower; the streams are kept for this run only)
-  ( cd /tmp && rm -rf /tmp/kst && MHS_RESERVE_KEEP=1 MHS_BENCH_SKIP_F64=1 MHS_BENCH_SKIP_SENSITIVITY=1 MHS_BENCH_SKIP_FITTED=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kst -o cfg3 -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2>/tmp/kst.log )
+  ( cd /tmp && rm -rf /tmp/kst && MHS_RESERVE_KEEP=1 MHS_BENCH_SKIP_F64=1 MHS_BENCH_SKIP_SENSITIVITY=1 MHS_BENCH_SKIP_FITTED=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kst -o cfg3 -- python $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $ROOT/$O/bench_under_rocprof.json 2>/tmp/kst.log )
   find /tmp/kst -name "*kernel_stats.csv" -exec cp {} $O/cfg3_steps_only_rocprofv3_kernel_stats.csv \;
   find /tmp/kst -name "*kernel_trace.csv" -exec cp {} /tmp/cfg3_kernel_trace.csv \;
   python tools/r06_launch_vs_rocprof.py $O/bench_under_rocprof.json $O/cfg3_steps_only_rocprofv3_kernel_stats.csv /tmp/cfg3_kernel_trace.csv > $O/cfg3_launch_vs_rocprof.json; cat $O/cfg3_launch_vs_rocprof.json
   summ $O/bench_cfg3_n1.json $O/bench_under_rocprof.json
 fi
 if [ "$PART" = all ] || [ "$PART" = benchmore ]; then
-  timeout 900 python bench.py --tps-mode tiled > $O/bench_cfg3_n1_tiled_tps.json 2>/dev/null
-  timeout 600 python bench.py --workload cfg2 > $O/bench_cfg2_n1.json 2>/dev/null
-  timeout 600 python bench.py --workload cfg2 --tps-mode tiled --no-cpu-baseline > $O/bench_cfg2_n1_tiled_tps.json 2>/dev/null
-  timeout 1200 python bench.py --workload cfg4 --steps 3 --warmup 1 > $O/bench_cfg4_n1.json 2>/dev/null
-  MHS_BENCH_SKIP_F64=1 timeout 1800 python bench.py --workload cfg5 --steps 1 --warmup 1 > $O/bench_cfg5_n1.json 2>/dev/null
+  timeout 900 python bench.py --full --tps-mode tiled > $O/bench_cfg3_n1_tiled_tps.json 2>/dev/null
+  timeout 600 python bench.py --full --workload cfg2 > $O/bench_cfg2_n1.json 2>/dev/null
+  timeout 600 python bench.py --full --workload cfg2 --tps-mode tiled --no-cpu-baseline > $O/bench_cfg2_n1_tiled_tps.json 2>/dev/null
+  timeout 1200 python bench.py --full --workload cfg4 --steps 3 --warmup 1 > $O/bench_cfg4_n1.json 2>/dev/null
+  MHS_BENCH_SKIP_F64=1 timeout 1800 python bench.py --full --workload cfg5 --steps 1 --warmup 1 > $O/bench_cfg5_n1.json 2>/dev/null
   summ $O/bench_cfg3_n1_tiled_tps.json $O/bench_cfg2_n1.json $O/bench_cfg2_n1_tiled_tps.json $O/bench_cfg4_n1.json $O/bench_cfg5_n1.json
 fi
 if [ "$PART" = all ] || [ "$PART" = inlib ]; then      # the library's own multi-device drivers: 1 slot, and 2 / 4 / 8 slots sharing this GPU (plumbing + overhead)
   for n in 1 2 4 8; do
-    timeout 900 python bench.py --gpus $n --in-library --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg3_inlibrary_n$n.json 2> $O/bench_cfg3_inlibrary_n$n.err
+    timeout 900 python bench.py --full --gpus $n --in-library --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg3_inlibrary_n$n.json 2> $O/bench_cfg3_inlibrary_n$n.err
   done
   for n in 1 4; do
-    timeout 900 python bench.py --gpus $n --in-library --tps-mode tiled --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg3_inlibrary_tiled_n$n.json 2>/dev/null
+    timeout 900 python bench.py --full --gpus $n --in-library --tps-mode tiled --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_cfg3_inlibrary_tiled_n$n.json 2>/dev/null
   done
-  timeout 1200 python bench.py --workload cfg4 --gpus 1 --in-library --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg4_inlibrary_n1.json 2>/dev/null
-  timeout 1200 python bench.py --workload cfg4 --gpus 4 --in-library --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg4_inlibrary_n4.json 2>/dev/null
+  timeout 1200 python bench.py --full --workload cfg4 --gpus 1 --in-library --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg4_inlibrary_n1.json 2>/dev/null
+  timeout 1200 python bench.py --full --workload cfg4 --gpus 4 --in-library --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg4_inlibrary_n4.json 2>/dev/null
   python bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_gpus2_no_launcher.out 2> $O/bench_gpus2_no_launcher.err; echo "exit code $?" >> $O/bench_gpus2_no_launcher.err
   summ $O/bench_cfg3_inlibrary_n*.json $O/bench_cfg3_inlibrary_tiled_n*.json $O/bench_cfg4_inlibrary_n*.json
 fi
@@ -84,12 +85,12 @@ if [ "$PART" = all ] || [ "$PART" = forest ]; then      # cfg5's forest: the blo
   if [ -f machisplin_amd/libmhs_cbs_stats.so ]; then      # built by hand: forest.hip with -DRF_CBS_STATS (tools/README.md)
     MHS_LIB=machisplin_amd/libmhs_cbs_stats.so timeout 1100 python tools/r06_forest_stats.py 60 20000 2>&1 | grep -v "^/opt" > $O/forest_cbs_stats.txt; tail -5 $O/forest_cbs_stats.txt
   fi
-  ( cd /tmp && rm -rf /tmp/kfo && MHS_BENCH_SKIP_F64=1 MHS_BENCH_SKIP_TILED=1 timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kfo -o cfg5 -- python $GRAFT_REPO_ROOT/bench.py --workload cfg5 --steps 1 --warmup 1 --no-cpu-baseline > /tmp/kfo.json 2>/tmp/kfo.log )
+  ( cd /tmp && rm -rf /tmp/kfo && MHS_BENCH_SKIP_F64=1 MHS_BENCH_SKIP_TILED=1 timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kfo -o cfg5 -- python $ROOT/bench.py --full --workload cfg5 --steps 1 --warmup 1 --no-cpu-baseline > /tmp/kfo.json 2>/tmp/kfo.log )
   find /tmp/kfo -name "*kernel_stats.csv" -exec cp {} $O/cfg5_rocprofv3_kernel_stats.csv \;
   head -6 $O/cfg5_rocprofv3_kernel_stats.csv | cut -c1-160
 fi
 if [ "$PART" = cfg5 ]; then
-  MHS_BENCH_SKIP_F64=1 timeout 1800 python bench.py --workload cfg5 --steps 1 --warmup 1 > $O/bench_cfg5_n1.json 2>/dev/null
+  MHS_BENCH_SKIP_F64=1 timeout 1800 python bench.py --full --workload cfg5 --steps 1 --warmup 1 > $O/bench_cfg5_n1.json 2>/dev/null
   summ $O/bench_cfg5_n1.json
 fi
 if [ "$PART" = forestpmc ]; then      # memory-side bytes of the two big-tree forest kernels (a --pmc pass of its own)
