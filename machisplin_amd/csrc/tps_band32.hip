@@ -755,13 +755,16 @@ __global__ __launch_bounds__(256) void b32_symm_kernel(double *__restrict__ A, i
             // 2 q + 1 of the trip stand for columns j + 8 q + 2 l4 and + 1 -- the sum over a trip's 16 columns does not care
             // in which order they come, as long as A22's and V's operands agree.
             const int tcl = (t - 2) & ~1;
+            const int jlim = min(jend, t);      // jend is rounded up past t: columns t .. jend - 1 are not A22's
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int jc = j + 8 * q + 2 * l4;
-                const int col = jc < t ? jc : tcl;      // (jc = t - 1: its partner, column t, is finite memory of the same row and meets a zero row of V)
+                const int col = jc < t ? jc : tcl;
                 const double2 m00 = *(const double2 *)(Ab + (int64_t)r00 * ld + col), m01 = *(const double2 *)(Ab + (int64_t)r01 * ld + col);
                 const double2 m10 = *(const double2 *)(Ab + (int64_t)r10 * ld + col), m11 = *(const double2 *)(Ab + (int64_t)r11 * ld + col);
-                const bool lv0 = jc < jend, lv1 = jc + 1 < jend;
+                // jc = t - 1 (t odd): the pair's second half is row n of A, outside the matrix (padding whose bytes nothing
+                // initialises when ld > n): masked here, not multiplied by the zero row t of V
+                const bool lv0 = jc < jlim, lv1 = jc + 1 < jlim;
                 a0[2 * q].x = lv0 ? m00.x : 0.0; a0[2 * q].y = lv0 ? m01.x : 0.0; a1[2 * q].x = lv0 ? m10.x : 0.0; a1[2 * q].y = lv0 ? m11.x : 0.0;
                 a0[2 * q + 1].x = lv1 ? m00.y : 0.0; a0[2 * q + 1].y = lv1 ? m01.y : 0.0; a1[2 * q + 1].x = lv1 ? m10.y : 0.0; a1[2 * q + 1].y = lv1 ? m11.y : 0.0;
                 const double *vrow = Vr + (int64_t)min(jc, t + 58) * NB + l15;
@@ -2450,7 +2453,11 @@ extern "C" int mhs_band32_reduce(const double *B, const double *g, int64_t m64, 
     MHS_HIP(dws.alloc(band32_workspace_bytes(m, n)));
     // same placement as the fit: B starts at row / column 3, row 3 of every column on a 16-byte boundary
     double *A = dA.p + 1;
-    MHS_HIP(hipMemsetAsync(dA.p, 0, sizeof(double) * ((size_t)ld * n + 4), s));
+    // what the fit's lane arena would hold: a quiet NaN (all bits set) in every double the fit never writes -- rows n .. ld - 1
+    // of every column and the spare doubles around A -- and zeros in rows / columns 0 .. 2, so that a kernel which reads
+    // beyond the matrix shows it in its results
+    MHS_HIP(hipMemsetAsync(dA.p, 0xFF, sizeof(double) * ((size_t)ld * n + 4), s));
+    MHS_HIP(hipMemset2DAsync(A, sizeof(double) * ld, 0, sizeof(double) * n, (size_t)n, s));
     MHS_HIP(hipMemcpy2DAsync(A + 3 * ld + 3, sizeof(double) * ld, B, sizeof(double) * m, sizeof(double) * m, (size_t)m, hipMemcpyHostToDevice, s));
     MHS_HIP(hipMemcpyAsync(dg.p, g, sizeof(double) * m, hipMemcpyHostToDevice, s));
     Band32Ws w;

@@ -287,13 +287,16 @@ __device__ __forceinline__ void sb_reduce(const SmallJob *__restrict__ Jp, const
         }
     }
     if (tid == 0) S.stamp[1] = wall_clock64();
-    // the three given reflectors: into LDS (S.at is free until the loop is over) and into the reflector store
+    // the three given reflectors: into LDS (S.at is free until the loop is over) and into the reflector store.  A row of
+    // the store is ldv >= n wide, which can be less than NR (ldv = 32, 64, 96 when the launch's largest fit has at most
+    // 96 stations): entries ldv .. NR - 1 are zeros nobody reads, and storing them would land in the next row's slots,
+    // written by another wave with nothing ordering the two stores.
     if (tid < NR) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double hv = tid < n ? in[(size_t)(3 + k) * n + tid] : 0.0;
             S.at[k][tid] = hv;
-            Vg[(size_t)k * ldv + tid] = hv;
+            if (tid < ldv) Vg[(size_t)k * ldv + tid] = hv;
         }
     }
     }
@@ -359,7 +362,7 @@ __device__ __forceinline__ void sb_reduce(const SmallJob *__restrict__ Jp, const
                     const int r = a + 32 * i;
                     const double vi = r == r1 ? 1.0 : (r > r1 ? x[i] * scal : 0.0);
                     S.vs[buf][r] = vi;
-                    Vg[(size_t)kk * ldv + r] = vi;
+                    if (r < ldv) Vg[(size_t)kk * ldv + r] = vi;      // rows of the store do not overlap (see above)
                 }
                 if (a == 0) { S.ta[kk] = dkk; S.tb[kk] = beta; S.ttau[kk] = tk; S.sc[buf] = tk; }
             }

@@ -8,10 +8,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conftest import synth_stations
 from oracle import bandred as br
 from oracle import tps as ot
 
 pytestmark = pytest.mark.gpu
+
+
+def _rel(a, b):
+    return np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(b).max()
 
 
 def _tps_matrix(n, seed, cells=400):
@@ -100,26 +105,57 @@ def test_banded_solve(hip, m):
     assert np.max(np.abs(q - want)) < 1e-12 * np.max(np.abs(want))
 
 
-@pytest.mark.parametrize("n", [403, 900, 1003 + 32, 2600])
+# n = m + 3 with ld = round16(n): ld - n = 13, 12, 7, 6, 1, 0, 15, 14 (323 .. 338), n odd and even; an even n makes every
+# panel's trailing order t odd, where the symmetric product's paired loads reach row n of A
+@pytest.mark.parametrize("n", [323, 324, 329, 330, 335, 336, 337, 338, 403, 900, 1003 + 32, 2600])
 def test_band_reduction_keeps_the_spectrum_and_solves_the_system(hip, n):
     """B = Q2'KQ2 of n TPS stations on distinct cells: the reduced band has B's eigenvalues, Q'g its norm, Q Q'g = g, and
     c2 = Q (Bb + lambda I)^-1 Q'g solves (B + lambda I) c2 = g.  n - 3 mod 32 covers a short last panel (t < 64, the
-    classical Householder kernel) in 1035 -> m = 1032 (t = 8) and 403 -> m = 400 (t = 16)."""
+    classical Householder kernel) in 1035 -> m = 1032 (t = 8) and 403 -> m = 400 (t = 16).  The hook puts NaN in every
+    double of A's allocation the fit does not write (rows n .. ld - 1, the spare doubles around A): a kernel that reads
+    them, even against zeros, makes the results non-finite."""
     B, g = _tps_matrix(n, n)
     m = B.shape[0]
     ab, gq, _, bd = _reduce(hip, B, g)
     assert bd == 0
+    assert np.isfinite(ab).all() and np.isfinite(gq).all()
     e = np.linalg.eigvalsh(B)
     e2 = np.linalg.eigvalsh(br.band_dense(ab))
     assert np.max(np.abs(e2 - e)) < 2e-13 * e[-1]
     assert abs(np.linalg.norm(gq) - np.linalg.norm(g)) < 1e-12 * np.linalg.norm(g)
     _, _, back, _ = _reduce(hip, B, g, r=gq)
+    assert np.isfinite(back).all()
     assert np.max(np.abs(back - g)) < 5e-12 * np.max(np.abs(g))
     lam = 1e-4
     q = br.band_solve(ab, gq, lam)
     _, _, c2, _ = _reduce(hip, B, g, r=q)
+    assert np.isfinite(c2).all()
     want = np.linalg.solve(B + lam * np.eye(m), g)
     assert np.max(np.abs(c2 - want)) < 1e-9 * np.max(np.abs(want))
+
+
+# m = n - 3 just above B32_MIN_M = 320 and about 1 000, n even and odd.  test_tps_fit_gpu.py's GCV test reaches the
+# 32-column route only at n = 813 (odd), so none of these sizes is covered there.
+@pytest.mark.parametrize("n", [324, 329, 338, 1002, 1003])
+def test_gcv_fit_on_the_32_column_route_matches_oracle_and_8_column_route(hip, n, monkeypatch):
+    """The whole GCV fit on the 32-column band route at sizes just above its threshold: lambda against the oracle's
+    search, c and d against the oracle's solve at the fit's lambda, and everything against the same fit on the 8-column
+    route (MHS_FIT_LEGACY_BAND=1), whose kernels share none of the 32-column route's loads."""
+    xy, y = synth_stations(n, 600 + n)
+    got = hip.Tps(xy, y)
+    monkeypatch.setenv("MHS_FIT_LEGACY_BAND", "1")
+    legacy = hip.Tps(xy, y)
+    monkeypatch.delenv("MHS_FIT_LEGACY_BAND")
+    assert got.n == n
+    assert np.isfinite(got.c).all() and np.isfinite(got.d).all() and np.isfinite(got.lambda_)
+    want = ot.fit(xy, y)
+    assert abs(got.lambda_ - want["lambda"]) / want["lambda"] < 1e-8
+    assert abs(got.gcv - want["gcv"]) < 1e-9 * want["gcv"]
+    ref = ot.fit(xy, y, lam=got.lambda_)
+    assert _rel(got.c, ref["c"]) < 1e-8 and _rel(got.d, ref["d"]) < 1e-8
+    assert abs(legacy.lambda_ - got.lambda_) < 1e-8 * got.lambda_
+    assert abs(legacy.gcv - got.gcv) < 1e-9 * got.gcv
+    assert _rel(legacy.c, got.c) < 1e-8 and _rel(legacy.d, got.d) < 1e-8
 
 
 def test_rank_deficient_panel_is_reported(hip):

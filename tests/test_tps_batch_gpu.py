@@ -84,6 +84,14 @@ def test_batch_many_more_fits_than_compute_units(hip):
         assert fits[k].lambda_ == alone.lambda_ and np.array_equal(fits[k].c, alone.c) and np.array_equal(fits[k].d, alone.d)
     want = otps.fit(*sets[300])
     assert abs(fits[300].lambda_ - want["lambda"]) / want["lambda"] < 1e-8
+    # the largest fit has 46 stations (a reflector store 64 doubles wide): every fit's coefficients against the oracle at
+    # the fit's own lambda, which the comparison with the fit done alone (the same launch geometry) cannot show
+    bad = []
+    for k, ((xy, y), got) in enumerate(zip(sets, fits)):
+        ref = otps.fit(xy, y, lam=got.lambda_)
+        if not (_rel(got.c, ref["c"]) < 1e-8 and _rel(got.d, ref["d"]) < 1e-8):
+            bad.append((k, _rel(got.c, ref["c"]), _rel(got.d, ref["d"])))
+    assert not bad, bad[:10]
 
 
 def test_tiled_surface_batched_route_equals_lane_route(hip, monkeypatch):
@@ -180,3 +188,119 @@ def test_tiled_surface_zero_tiles_and_replicated_stations(hip):
     got = hip.tps_residual_surface(g, xy, resid, tile_edge=250).cpu().numpy()
     assert np.array_equal(got, want)
     assert np.all(got[:, 700:][np.isfinite(got[:, 700:])] == 0.0) or np.abs(got[:, 750:]).max() < 1e-12      # the zero tiles
+
+
+# One launch per width of the reflector store (ldv = the launch's largest fit rounded up to 32) and per register layout
+# (NS = ceil(n / 32), at least 4): (lo, hi) = the range of the launch's distinct-location counts, hi itself among them.
+# 8..32, 33..64 and 65..96 give stores narrower than the 128 entries a row of sb_reduce<4> holds; the others put the
+# largest fit on either side of each NS boundary.
+STRIDE_CLASSES = [(8, 32), (33, 64), (65, 96), (97, 128), (97, 129), (129, 160), (129, 161), (161, 192), (161, 193),
+                  (193, 224), (193, 225)]
+CLASS_FITS = 280      # more than the 256 compute units: workgroups loop over fits
+
+
+def _class_sets(lo, hi, seed):
+    """CLASS_FITS station sets of lo..hi distinct locations (hi once at least, 8 once when lo is 8); every seventh set
+    has a quarter of its stations observed again with other values (replicates collapse to the same distinct count)."""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(lo, hi + 1, CLASS_FITS)
+    sizes[0] = hi
+    if lo == 8:
+        sizes[1] = 8
+    sets = []
+    for k, n in enumerate(sizes):
+        xy, y = synth_stations(int(n), seed * 1000 + k)
+        if k % 7 == 3:
+            dup = rng.integers(0, n, max(2, n // 4))
+            xy = np.vstack([xy, xy[dup]])
+            y = np.concatenate([y, y[dup] + 0.05 * rng.standard_normal(dup.size)])
+        sets.append((xy, y))
+    return sets, [int(n) for n in sizes]
+
+
+def _off_station_points(k):
+    rng = np.random.default_rng(k)
+    return np.column_stack([rng.uniform(-78, -76, 64), rng.uniform(-7, -5, 64)])
+
+
+@pytest.mark.parametrize("lo,hi", STRIDE_CLASSES, ids=[f"nmax{hi}" for _, hi in STRIDE_CLASSES])
+def test_batch_every_stride_class_matches_oracle(hip, lo, hi):
+    """Every fit of a launch whose largest fit has `hi` distinct locations, against the oracle: lambda, effective degrees
+    of freedom and GCV as the GCV test above; c and d at the fit's own lambda; the handle's predictions off the stations.
+    Below 97 stations the reflector store's rows (ldv wide) are narrower than the rows sb_reduce computes (NR = 128): the
+    store must not spill a row's zeros into the next one, or the back-transform returns wrong c and d (lambda stays right)."""
+    sets, sizes = _class_sets(lo, hi, hi)
+    fits = hip.tps.fit_many([s[0] for s in sets], [s[1] for s in sets])
+    assert len(fits) == CLASS_FITS
+    bad = []
+    for k, ((xy, y), got, n) in enumerate(zip(sets, fits, sizes)):
+        assert got is not None and got.n == n, k
+        want = otps.fit(xy, y)
+        ref = otps.fit(xy, y, lam=got.lambda_)
+        pts = _off_station_points(k)
+        errs = {"lambda": abs(got.lambda_ - want["lambda"]) / want["lambda"] / 1e-8,
+                "eff_df": abs(got.eff_df - want["eff_df"]) / want["eff_df"] / 1e-5,
+                "gcv": abs(got.gcv - want["gcv"]) / want["gcv"] / 1e-9,
+                "c": _rel(got.c, ref["c"]) / 1e-8, "d": _rel(got.d, ref["d"]) / 1e-8,
+                "predict": _rel(got.predict(pts), otps.predict_points(ref, pts)) / 1e-9}
+        if not all(np.isfinite(v) and v < 1.0 for v in errs.values()):      # error / tolerance
+            bad.append((k, n, {q: float(v) for q, v in errs.items() if not v < 1.0}))
+    assert not bad, (len(bad), bad[:10])
+
+
+@pytest.mark.parametrize("lo,hi", STRIDE_CLASSES, ids=[f"nmax{hi}" for _, hi in STRIDE_CLASSES])
+def test_batch_every_stride_class_fixed_lambda(hip, lo, hi):
+    """The same launches with a fixed lambda (no search): c, d, effective degrees of freedom, GCV and predictions of every
+    fit against the oracle's solve at that lambda."""
+    lam = 3e-3
+    sets, sizes = _class_sets(lo, hi, hi)
+    fits = hip.tps.fit_many([s[0] for s in sets], [s[1] for s in sets], lambda_=lam)
+    bad = []
+    for k, ((xy, y), got, n) in enumerate(zip(sets, fits, sizes)):
+        assert got is not None and got.n == n and got.lambda_ == lam, k
+        want = otps.fit(xy, y, lam=lam)
+        pts = _off_station_points(k)
+        errs = {"eff_df": abs(got.eff_df - want["eff_df"]) / want["eff_df"] / 1e-8,
+                "gcv": abs(got.gcv - want["gcv"]) / want["gcv"] / 1e-9,
+                "c": _rel(got.c, want["c"]) / 1e-8, "d": _rel(got.d, want["d"]) / 1e-8,
+                "predict": _rel(got.predict(pts), otps.predict_points(want, pts)) / 1e-9}
+        if not all(np.isfinite(v) and v < 1.0 for v in errs.values()):
+            bad.append((k, n, {q: float(v) for q, v in errs.items() if not v < 1.0}))
+    assert not bad, (len(bad), bad[:10])
+
+
+@pytest.mark.parametrize("lo,hi", STRIDE_CLASSES[:3], ids=[f"nmax{hi}" for _, hi in STRIDE_CLASSES[:3]])
+def test_batch_result_does_not_depend_on_the_reflector_store_stride(hip, lo, hi):
+    """A launch whose fits have at most 96 stations (reflector store ldv = 32, 64, 96 doubles per row) and the same
+    launch with one 256-station fit appended (ldv = 256): every fit equal bit for bit.  ldv enters tps_batch.hip only as
+    the stride of the global reflector store and the offset of the GCV scratch behind it -- the values stored and read
+    back, and the order of every operation on them, are the same -- and with more fits than compute units both launches
+    have the same workgroups and deal them the same fits (the appended one last)."""
+    sets, _ = _class_sets(lo, hi, hi)
+    big = synth_stations(256, 4242)
+    narrow = hip.tps.fit_many([s[0] for s in sets], [s[1] for s in sets])
+    wide = hip.tps.fit_many([s[0] for s in sets] + [big[0]], [s[1] for s in sets] + [big[1]])
+    assert wide[-1] is not None and wide[-1].n == 256
+    for k, (a, b) in enumerate(zip(narrow, wide)):
+        assert a.lambda_ == b.lambda_ and a.gcv == b.gcv and a.eff_df == b.eff_df, k
+        assert np.array_equal(a.c, b.c) and np.array_equal(a.d, b.d), k
+
+
+def test_tiled_surface_of_small_tiles_batched_route_equals_lane_route(hip, monkeypatch):
+    """A reference-tiled surface whose tiles ALL hold 10..96 stations: the batch launch's largest fit is at most 96, so
+    its reflector store is narrower than a row of the reduction.  The batched route (one launch for every tile) against
+    the lane route (MHS_TILES_BATCH=0: each tile on its own, through the one-block tridiagonalisation) to 1e-10."""
+    from machisplin_amd import synth
+    g = synth.grid(700, 900)
+    xy, rows, cols, uv = synth.stations(g, 1800, 5)
+    resid = synth.tps_residual(uv, 5)
+    info = {}
+    hip.tps_residual_surface(g, xy, resid, tile_edge=120, info=info)
+    assert len(info["tile_n"]) > 40 and max(info["tile_n"]) <= 96 and min(info["tile_n"]) >= 10, info["tile_n"]
+    for lam in (None, 2e-3):
+        got = hip.tps_residual_surface(g, xy, resid, tile_edge=120, lambda_=lam).cpu().numpy()
+        monkeypatch.setenv("MHS_TILES_BATCH", "0")
+        want = hip.tps_residual_surface(g, xy, resid, tile_edge=120, lambda_=lam).cpu().numpy()
+        monkeypatch.delenv("MHS_TILES_BATCH")
+        assert np.isfinite(got).all() and np.isfinite(want).all(), lam
+        assert np.abs(got - want).max() <= 1e-10 * np.abs(want).max(), lam
