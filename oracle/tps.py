@@ -224,6 +224,110 @@ def fit_direct(xy, y, lam):
             "scale": scale, "knots": u}
 
 
+PI_LD = 4 * np.arctan(np.longdouble(1))   # pi to long-double precision (np.pi cast up is off by 1e-16)
+
+
+def _phi_ld(d2):
+    """radial_phi in long double, with fields' 1e-20 floor and exactly 0 at d2 = 0 (a knot)."""
+    f = np.maximum(d2, np.longdouble(1e-20))
+    return np.where(d2 == 0, np.longdouble(0), (np.longdouble(0.5) / (8 * PI_LD)) * np.log(f) * f)
+
+
+def _saddle_rows_ld(u, lam_w, x, rows):
+    """Rows `rows` (< n) of A x and of |A| |x| for A = [[K + diag(lam_w), T], [T', 0]], in long double."""
+    n = u.shape[0]
+    ul = u.astype(np.longdouble)
+    xl = np.asarray(x, dtype=np.longdouble)
+    dx = ul[rows, None, 0] - ul[None, :, 0]
+    dy = ul[rows, None, 1] - ul[None, :, 1]
+    K = _phi_ld(dx * dx + dy * dy)
+    c, d = xl[:n], xl[n:]
+    poly = d[0] + d[1] * ul[rows, 0] + d[2] * ul[rows, 1]
+    ax = K @ c + lam_w[rows] * c[rows] + poly
+    aK = np.abs(K)
+    aax = aK @ np.abs(c) + np.abs(lam_w[rows] * c[rows]) + abs(d[0]) + np.abs(d[1] * ul[rows, 0]) + np.abs(d[2] * ul[rows, 1])
+    arow = aK.sum(axis=1) + np.abs(lam_w[rows]) + 1 + np.abs(ul[rows, 0]) + np.abs(ul[rows, 1])
+    return ax, aax, arow
+
+
+def _saddle_apply_ld(u, lam_w, x, block=512):
+    """A x, |A| |x| and the absolute row sums of A for the whole saddle-point system, K built
+    in long double block of rows by block."""
+    n = u.shape[0]
+    ax = np.empty(n + NT, dtype=np.longdouble)
+    aax = np.empty(n + NT, dtype=np.longdouble)
+    arow = np.empty(n + NT, dtype=np.longdouble)
+    for s in range(0, n, block):
+        rows = np.arange(s, min(n, s + block))
+        ax[rows], aax[rows], arow[rows] = _saddle_rows_ld(u, lam_w, x, rows)
+    c = np.asarray(x, dtype=np.longdouble)[:n]
+    aT = np.abs(np.column_stack([np.ones(n), u]).astype(np.longdouble))
+    ax[n:] = np.column_stack([np.ones(n), u]).astype(np.longdouble).T @ c
+    aax[n:] = aT.T @ np.abs(c)
+    arow[n:] = aT.sum(axis=0)
+    return ax, aax, arow
+
+
+def _saddle_problem(xy, y, lam):
+    xm, ym, w, _ = collapse_replicates(xy, y)
+    center, scale = range_scale(xm)
+    u = (xm - center) / scale          # the same float64 knots as fit / fit_direct
+    lam_w = np.longdouble(lam) / w.astype(np.longdouble)
+    b = np.concatenate([ym, np.zeros(NT)]).astype(np.longdouble)
+    return u, w, center, scale, lam_w, b
+
+
+def refined_solution(xy, y, lam, max_iter=10):
+    """Extended-precision reference for `fit_direct`'s saddle-point system
+    [[K + lam W^-1, T], [T', 0]] [c; d] = [yM; 0] on the float64 knots:
+    iterative refinement with the residual and the iterate in long double (K
+    rebuilt in long double, block of rows by block) and the corrections from one
+    float64 LU.  Iterates until the residual stops falling (at most max_iter).
+    Returns c, d (long double), the knots, weightsM, center, scale, and the
+    number of refinement steps taken."""
+    import scipy.linalg
+    u, w, center, scale, lam_w, b = _saddle_problem(xy, y, lam)
+    n = u.shape[0]
+    A = np.zeros((n + NT, n + NT))
+    A[:n, :n] = gram(u) + np.diag((lam_w).astype(np.float64))
+    A[:n, n:] = np.column_stack([np.ones(n), u])
+    A[n:, :n] = A[:n, n:].T
+    lu = scipy.linalg.lu_factor(A, check_finite=False)
+    del A
+    x = scipy.linalg.lu_solve(lu, b.astype(np.float64)).astype(np.longdouble)
+    best = None
+    steps = 0
+    for steps in range(1, max_iter + 1):
+        r = b - _saddle_apply_ld(u, lam_w, x)[0]
+        rn = float(np.abs(r).max())
+        if best is not None and rn >= 0.5 * best[0]:
+            if rn < best[0]:
+                best = (rn, x)
+            break
+        best = (rn, x)
+        if rn == 0.0:
+            break
+        x = x + scipy.linalg.lu_solve(lu, r.astype(np.float64)).astype(np.longdouble)
+    x = best[1]
+    return {"c": x[:n], "d": x[n:], "knots": u, "w": w, "center": center, "scale": scale,
+            "lambda": float(lam), "steps": steps}
+
+
+def backward_error(xy, y, lam, c, d):
+    """Backward error of (c, d) for fit_direct's saddle-point system, residual in long
+    double: (componentwise, normwise) =
+    (max_i |r_i| / (sum_j |A_ij| |x_j| + |b_i|),  ||r||_inf / (||A||_inf ||x||_inf + ||b||_inf))."""
+    u, w, _, _, lam_w, b = _saddle_problem(xy, y, lam)
+    n = u.shape[0]
+    x = np.concatenate([np.asarray(c, dtype=np.longdouble), np.asarray(d, dtype=np.longdouble)])
+    ax, aax, arow = _saddle_apply_ld(u, lam_w, x)
+    r = np.abs(b - ax)
+    den = aax + np.abs(b)
+    comp = float(np.max(np.where(den > 0, r / np.where(den > 0, den, 1), np.where(r > 0, np.inf, 0))))
+    norm = float(r.max() / (float(arow.max()) * float(np.abs(x).max()) + float(np.abs(b).max())))
+    return comp, norm
+
+
 def predict_points(model, xy, block=4096):
     """predict.Krig: fields.mkpoly(x,2) %*% d + Rad.cov(x, knots, C=c)."""
     xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)

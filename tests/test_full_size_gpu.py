@@ -114,6 +114,13 @@ def test_fitted_spline_satisfies_its_normal_equations(hip, n):
         fg = hip.Tps(xy, y)
         assert np.abs(fg.predict(xy) - (y - fg.lambda_ * fg.c)).max() < 1e-7 * np.abs(y).max()
         assert 3.0 < fg.eff_df < n
+        # criterion B of tests/fitcheck.py on the host: the backward error of both fits, residual in long double
+        from oracle import tps as otps
+        import fitcheck
+        for route, f, lm in (("chol", fit, lam), ("gcv-band32", fg, fg.lambda_)):
+            be = otps.backward_error(xy, y, lm, f.c, f.d)[0]
+            print(f"CRITERIA route={route} n={n} lambda={lm:.6g} B={be:.3e} full size")
+            assert be <= fitcheck.TAU_B[route], (route, be)
 
 
 def test_cfg3_ensemble_linearity_on_the_full_grid(hip):

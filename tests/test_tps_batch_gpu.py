@@ -4,6 +4,7 @@ library's one-fit-at-a-time route (mhs_tps_fit) on the same stations."""
 import numpy as np
 import pytest
 
+import fitcheck
 from conftest import synth_stations
 from oracle import tps as otps
 
@@ -304,3 +305,16 @@ def test_tiled_surface_of_small_tiles_batched_route_equals_lane_route(hip, monke
         monkeypatch.delenv("MHS_TILES_BATCH")
         assert np.isfinite(got).all() and np.isfinite(want).all(), lam
         assert np.abs(got - want).max() <= 1e-10 * np.abs(want).max(), lam
+
+
+@pytest.mark.parametrize("lo,hi", STRIDE_CLASSES, ids=[f"nmax{hi}" for _, hi in STRIDE_CLASSES])
+def test_batch_stride_classes_meet_the_accuracy_criteria(hip, lo, hi):
+    """A handful of each stride class's fits (the largest, a replicated set among them), GCV and fixed lambda: the batch
+    kernel's c and d meet criteria B and F (tests/fitcheck.py) against the extended-precision solve at the fit's lambda."""
+    sets, sizes = _class_sets(lo, hi, hi)
+    sets, sizes = sets[:5], sizes[:5]
+    for lam in (None, 3e-3):
+        fits = hip.tps.fit_many([s[0] for s in sets], [s[1] for s in sets], lambda_=lam)
+        for k, ((xy, y), got, n) in enumerate(zip(sets, fits, sizes)):
+            assert got is not None and got.n == n, k
+            fitcheck.check("batch", xy, y, got.lambda_, got, f"class {hi} fit {k} {'gcv' if lam is None else 'fixed'}")

@@ -3,6 +3,7 @@ through the C ABI) vs the oracle's QR + eigen + GCV restatement on the same stat
 import numpy as np
 import pytest
 
+import fitcheck
 from conftest import synth_stations
 from oracle import tps as otps
 
@@ -45,6 +46,18 @@ def test_gcv_path(hip, n, mode):
     ref = otps.fit(xy, y, lam=got.lambda_)
     assert _rel(got.c, ref["c"]) < 1e-8
     assert _rel(got.d, ref["d"]) < 1e-8
+    fitcheck.check(fitcheck.gcv_route(n), xy, y, got.lambda_, got, mode)
+
+
+@pytest.mark.parametrize("n", [322, 323])     # m = 319: the last 8-column band order; m = 320 = B32_MIN_M: the first band-32
+def test_gcv_path_at_the_band32_threshold(hip, n):
+    xy, y = synth_stations(n, 200 + n)
+    got = hip.Tps(xy, y)
+    want = otps.fit(xy, y)
+    assert abs(got.lambda_ - want["lambda"]) / want["lambda"] < 1e-8
+    ref = otps.fit(xy, y, lam=got.lambda_)
+    assert _rel(got.c, ref["c"]) < 1e-8 and _rel(got.d, ref["d"]) < 1e-8
+    fitcheck.check(fitcheck.gcv_route(n), xy, y, got.lambda_, got)
 
 
 def test_replicates_are_collapsed(hip):
@@ -108,6 +121,8 @@ def test_large_fit_uses_streaming_panel_path(hip):
     assert _rel(got.c, ref["c"]) < 1e-7 and _rel(got.d, ref["d"]) < 1e-7
     fixed = hip.Tps(xy, y, lambda_=got.lambda_)  # Cholesky route agrees with the band route
     assert _rel(fixed.c, got.c) < 1e-8
+    fitcheck.check("gcv-band32", xy, y, got.lambda_, got)
+    fitcheck.check("chol", xy, y, got.lambda_, fixed)
 
 
 @pytest.mark.timeout(600)
@@ -130,6 +145,8 @@ def test_legacy_eight_column_route_equals_the_default_route(hip, n, monkeypatch)
     assert _rel(legacy.c, fast.c) < 1e-8 and _rel(legacy.d, fast.d) < 1e-8
     ref = otps.fit(xy, y, lam=fast.lambda_)
     assert _rel(fast.c, ref["c"]) < 1e-7 and _rel(fast.d, ref["d"]) < 1e-7
+    fitcheck.check("gcv-band32", xy, y, fast.lambda_, fast)
+    fitcheck.check("gcv-band8", xy, y, legacy.lambda_, legacy, "legacy")
 
 
 @pytest.mark.parametrize("n", [12, 131, 250])
