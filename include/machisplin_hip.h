@@ -189,6 +189,29 @@ MHS_API int mhs_tps_predict_rows_dev(const mhs_tps *t, const mhs_grid *g, int64_
 /* predict(tps, xy): arbitrary points, xy n x 2 column-major (Step-5 station check) */
 MHS_API int mhs_tps_predict_points(const mhs_tps *t, const double *xy, int64_t n, double *out_host);
 
+/* ------------------------------------------------------- TPS standard errors --
+ * replaces fields::predictSE.Krig(fit, x) and terra::interpolate(r, fit, fun = predictSE).  predictSE.Krig computes
+ *     var(x) = rho phi(0) - 2 rho k(x)'a(x) + a(x)' (rho K + sigma^2 W^-1) a(x),   f^(x) = a(x)' yM ,
+ * which for rho = sigma^2 / lambda (fields' own MLE pair satisfies shat.MLE^2 = lambda rho.MLE) is exactly
+ *     var(x) = -(sigma^2 / lambda) z(x)' M^-1 z(x),  M = [[K + lambda W^-1, T], [T', 0]],  z(x) = [phi(|u - u_j|^2)_j; 1; u; v];
+ * the SE is sqrt(max(var, 0)).  M^-1 is built once per spline on the host (O(n^3)) and kept in the handle, so SE needs a
+ * spline of at most MHS_TPS_SE_MAX_N distinct stations (MHS_ERR_INVALID above it).  sigma2 = NaN takes the fit's own
+ *     sigma^2 hat = (RSS_w(lambda) + pure_ss) / (N - eff_df),  RSS_w = sum_i w_i (yM_i - f^(xM_i))^2
+ * (fields' shat.GCV^2); to reproduce predictSE of a real fields object pass sigma2 = fit$best.model[2].  A handle of
+ * mhs_tps_from_coef has no observations: its weights are taken as 1 and sigma2 must be given (NaN => MHS_ERR_INVALID). */
+#define MHS_TPS_SE_MAX_N 2048
+/* sigma^2 hat of the fit (above); MHS_ERR_INVALID for a mhs_tps_from_coef handle */
+MHS_API int mhs_tps_sigma2(const mhs_tps *t, double *sigma2);
+/* predictSE.Krig(fit, xy): xy n x 2 column-major, SE of each point into out_host[n] */
+MHS_API int mhs_tps_predict_se_points(const mhs_tps *t, const double *xy, int64_t n, double sigma2, double *out_host);
+/* predictSE.Krig on every cell centre of the window [r0,r1) x [c0,c1) (the cells of mhs_tps_predict_grid_dev); out is
+ * (r1-r0) x ld row-major on the device.  Returns once the plane is written. */
+/* the same into a host buffer, (r1-r0) x (c1-c0) row-major (what a .Call() shim hands over) */
+MHS_API int mhs_tps_predict_se_grid(const mhs_tps *t, const mhs_grid *g, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                                    double sigma2, double *out_host);
+MHS_API int mhs_tps_predict_se_grid_dev(const mhs_tps *t, const mhs_grid *g, int64_t r0, int64_t r1, int64_t c0, int64_t c1,
+                                        double sigma2, double *out_dev, int64_t ld, void *stream);
+
 /* ------------------------------------------------------- ensemble members --
  * Loaders take the FLAT parameter arrays of the fitted R objects (the shim extracts
  * them with REAL()/INTEGER()); the library copies them to the device.  p = number of
@@ -391,6 +414,21 @@ MHS_API int mhs_tps_surface_dev(const mhs_grid *g, const double *xy, const doubl
                                 const double *cov1_at_stations, int64_t tile_edge, double lambda,
                                 int gcv_mode, double *out_dev, int64_t ld, int64_t *tiles_out,
                                 void *stream);
+/* The SE plane of mhs_tps_surface_dev (same arguments; fields::predictSE.Krig per tile, see "TPS standard errors"):
+ * each tile's spline (fitted as mhs_tps_fit_many fits it) gives the SE on its keep window with its own sigma^2 hat, and
+ * the tile planes go through the same mean mosaic and seam feathering as the estimate (the NA-aware path of
+ * mhs_mosaic_feather_dev).  A linear blend of SEs with non-negative weights is the SE of the blended estimate if the
+ * tiles' errors were perfectly correlated, and an upper bound on it otherwise.  A zero tile (fewer than 10 stations,
+ * V73:710-721) has no spline, so its SE is NaN, and a cell that only zero tiles cover is NaN.  One tile or
+ * tile_edge <= 0: the global fit's SE (at most MHS_TPS_SE_MAX_N distinct stations).  Blocks until done.
+ * mhs_tps_surface_se: the same plane into a host buffer (as mhs_tps_surface). */
+MHS_API int mhs_tps_surface_se(const mhs_grid *g, const double *xy, const double *resid, int64_t n,
+                               const double *cov1_at_stations, int64_t tile_edge, double lambda, int gcv_mode,
+                               double *out_host, int64_t *tiles_out);
+MHS_API int mhs_tps_surface_se_dev(const mhs_grid *g, const double *xy, const double *resid, int64_t n,
+                                   const double *cov1_at_stations, int64_t tile_edge, double lambda,
+                                   int gcv_mode, double *out_dev, int64_t ld, int64_t *tiles_out,
+                                   void *stream);
 
 /* ------------------------------------------------------------ several devices --
  * ONE host process drives 1..16 devices ("mhs_init(int n_devices) ... library may use internal host

@@ -82,6 +82,25 @@ mhs_interpolate <- function(r, object) {
   v <- .Call("mhsr_tps_predict_grid", object$handle, .mhs_geom(r), c(0L, nrow(r), 0L, ncol(r)))
   terra::setValues(terra::rast(r), v)
 }
+# fields::predictSE(fit, x) for the GPU handle: var = (sigma2 / lambda) z' (-M^-1) z, i.e. predictSE.Krig with
+# rho = sigma2 / lambda.  sigma2 = NA takes the fit's own sigma^2 hat (fields' shat.GCV^2, mhs_tps_sigma2()); to
+# reproduce predictSE of a real fields object pass sigma2 = fit$best.model[2].  At most 2048 distinct stations.
+predictSE.machisplin_tps <- function(object, x, sigma2 = NA, ...)
+  .Call("mhsr_tps_predict_se_points", object$handle, as.matrix(x), as.numeric(sigma2))
+mhs_tps_sigma2 <- function(object) .Call("mhsr_tps_sigma2", object$handle)
+# terra::interpolate(r, fit, fun = predictSE): the SE at every cell centre of r
+mhs_interpolate_se <- function(r, object, sigma2 = NA) {
+  v <- .Call("mhsr_tps_predict_se_grid", object$handle, .mhs_geom(r), c(0L, nrow(r), 0L, ncol(r)), as.numeric(sigma2))
+  terra::setValues(terra::rast(r), v)
+}
+# The SE plane of mhs_tps_surface (same arguments): each tile's SE with its own sigma^2 hat, blended by the same mosaic
+# and seam feathering (an upper bound on the SE of the blended estimate); NA where only zero tiles reach.
+mhs_tps_surface_se <- function(rast_stack, dat, res.FINAL, n.covars, tile.edge = 1500L, lambda = NA_real_) {
+  xy <- as.matrix(dat[, c(n.covars, n.covars + 1)])
+  v <- .Call("mhsr_tps_surface_se", .mhs_geom(rast_stack), xy, as.numeric(res.FINAL), as.numeric(dat[, 2]),
+             as.integer(tile.edge), lambda, 0L)
+  terra::setValues(terra::rast(rast_stack[[1]]), v)
+}
 
 
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------

@@ -103,6 +103,48 @@ SEXP mhsr_tps_surface(SEXP geom, SEXP xy, SEXP resid, SEXP cov1, SEXP tile_edge,
     return out;
 }
 
+/* fields::predictSE.Krig (machisplin_hip.h "TPS standard errors"); sigma2 NA => the fit's own sigma^2 hat */
+static double sigma2_from(SEXP sigma2) {
+    double s = Rf_asReal(sigma2);
+    return ISNA(s) ? R_NaN : s;
+}
+SEXP mhsr_tps_sigma2(SEXP tps) {
+    double s2 = 0;
+    chk(mhs_tps_sigma2((mhs_tps *)R_ExternalPtrAddr(tps), &s2));
+    return Rf_ScalarReal(s2);
+}
+/* predictSE(fit, x) */
+SEXP mhsr_tps_predict_se_points(SEXP tps, SEXP xy, SEXP sigma2) {
+    R_xlen_t n = Rf_xlength(xy) / 2;
+    SEXP out = PROTECT(Rf_allocVector(REALSXP, n));
+    int rc = mhs_tps_predict_se_points((mhs_tps *)R_ExternalPtrAddr(tps), REAL(xy), (int64_t)n, sigma2_from(sigma2), REAL(out));
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+/* terra::interpolate(r, fit, fun = predictSE): values in terra cell order */
+SEXP mhsr_tps_predict_se_grid(SEXP tps, SEXP geom, SEXP win, SEXP sigma2) {
+    mhs_grid g = grid_from(geom);
+    int *w = INTEGER(win); /* r0, r1, c0, c1 (0-based, half-open) */
+    SEXP out = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)(w[1] - w[0]) * (w[3] - w[2])));
+    int rc = mhs_tps_predict_se_grid((mhs_tps *)R_ExternalPtrAddr(tps), &g, w[0], w[1], w[2], w[3], sigma2_from(sigma2), REAL(out));
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+/* the SE plane of Step 3 + Step 4 (mhsr_tps_surface's arguments) */
+SEXP mhsr_tps_surface_se(SEXP geom, SEXP xy, SEXP resid, SEXP cov1, SEXP tile_edge, SEXP lambda, SEXP mode) {
+    mhs_grid g = grid_from(geom);
+    double lam = Rf_asReal(lambda);
+    SEXP out = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)g.nrow * g.ncol));
+    int rc = mhs_tps_surface_se(&g, REAL(xy), REAL(resid), (int64_t)Rf_length(resid),
+                                Rf_isNull(cov1) ? NULL : REAL(cov1), (int64_t)Rf_asInteger(tile_edge),
+                                ISNA(lam) ? R_NaN : lam, Rf_asInteger(mode), REAL(out), NULL);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* model loaders: flat arrays pulled out of the fitted objects by R/backend_hip.R */
 SEXP mhsr_lm_load(SEXP coef) {
     mhs_model *m = NULL;

@@ -12,10 +12,10 @@ from .raster import Geometry, RasterStack
 from . import models
 from .models import predict, ensemble_predict
 from . import tps
-from .tps import Tps, fit_many, interpolate, eval_mode, EVAL_AUTO, EVAL_DIRECT, EVAL_FAR_FIELD
+from .tps import Tps, fit_many, interpolate, interpolate_se, eval_mode, EVAL_AUTO, EVAL_DIRECT, EVAL_FAR_FIELD
 from . import tiles, mltps, cv
-from .mltps import mltps as mltps_layers, mltps_predict, tps_residual_surface
+from .mltps import mltps as mltps_layers, mltps_predict, tps_residual_surface, tps_residual_surface_se
 
-__all__ = ["MhsError", "init", "Geometry", "RasterStack", "Tps", "interpolate", "eval_mode", "EVAL_AUTO", "EVAL_DIRECT", "EVAL_FAR_FIELD", "predict",
+__all__ = ["MhsError", "init", "Geometry", "RasterStack", "Tps", "interpolate", "interpolate_se", "eval_mode", "EVAL_AUTO", "EVAL_DIRECT", "EVAL_FAR_FIELD", "predict",
            "ensemble_predict", "models", "tiles", "mltps", "mltps_predict",
-           "tps_residual_surface", "_lib"]
+           "tps_residual_surface", "tps_residual_surface_se", "_lib"]

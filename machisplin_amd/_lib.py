@@ -99,6 +99,10 @@ SIGNATURES = {
     "mhs_tps_predict_grid_dev": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "mhs_tps_predict_rows_dev": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "mhs_tps_predict_points": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "mhs_tps_sigma2": (C.c_int, [_vp, _dp]),
+    "mhs_tps_predict_se_points": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp]),
+    "mhs_tps_predict_se_grid": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_double, _vp]),
+    "mhs_tps_predict_se_grid_dev": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp]),
     "mhs_tps_eval_mode": (C.c_int, [C.c_int]),
     "mhs_tps_eval_plan": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64)]),
     "mhs_lm_load": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
@@ -147,6 +151,9 @@ SIGNATURES = {
     "mhs_tps_tiles_dev": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _i64, _vp]),
     "mhs_tps_surface_dev": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _i64,
                                       _vp, _vp]),
+    "mhs_tps_surface_se": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _vp]),
+    "mhs_tps_surface_se_dev": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _i64,
+                                         _vp, _vp]),
     "mhs_init_devices": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "mhs_device_slots": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mhs_multi_stack_create": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_double, C.POINTER(_vp)]),

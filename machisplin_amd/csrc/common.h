@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -163,6 +164,9 @@ struct Knot { double u, v, cw, pad; };
 
 struct mhs_tps;
 namespace mhs {
+struct TpsPrep;   // tps_host.h
+struct SeState;   // tps_se.hip
+void se_state_free(SeState *s);   // releases its device block (the caller has synchronised)
 int upload_knots(mhs_tps *t);  // (re)build t->knots_dev from t->c / t->knots_uv
 int tps_free_quiet(mhs_tps *t);   // mhs_tps_free without its device-wide wait (the caller has synchronised)
 // rows [b0, b1) of the window [r0, r1) x [c0, c1) with the window's own plan (tps_eval.hip); out_dev holds row b0 first
@@ -208,4 +212,8 @@ struct mhs_tps {
         int64_t node_pairs = 0, cell_pairs = 0; // (node, far knot) and (cell, near knot) kernel evaluations
     } far;
     std::mutex mu;   // grid evaluations of one handle from several host threads: the plan is rebuilt under it
+    // what the prediction standard errors need (tps_se.hip): the fit's replicate collapse and weighted QR, kept by every
+    // fit route (NULL for mhs_tps_from_coef: no observations), and Q = -M^-1 with sigma^2 hat, built on first use under mu
+    std::shared_ptr<const mhs::TpsPrep> prep;
+    mhs::SeState *se = nullptr;
 };

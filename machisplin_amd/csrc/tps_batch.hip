@@ -934,6 +934,7 @@ extern "C" int mhs_tps_fit_many(const double *const *xy, const double *const *y,
         memcpy(t->d, r.d, sizeof(t->d));
         t->c.assign(c.begin() + B.jobs[(size_t)j].c_off, c.begin() + B.jobs[(size_t)j].c_off + P.n);
         t->knots_uv = P.uv;
+        t->prep = std::make_shared<const TpsPrep>(P);
         // the knot records are already on the device (natural order): device-to-device into the handle's own block
         t->knots_dev = (Knot *)pool_alloc(sizeof(Knot) * (size_t)P.n);
         if (!t->knots_dev) { tps_free_quiet(t); return MHS_ERR_ALLOC; }

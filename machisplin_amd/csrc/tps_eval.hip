@@ -672,6 +672,7 @@ int mhs::tps_free_quiet(mhs_tps *t) {
     if (!t) return MHS_OK;
     for (void *q : {(void *)t->knots_dev, (void *)t->far.sorted_dev, (void *)t->far.bin_start_dev, (void *)t->far.nodes_dev,
                     (void *)t->far.lx_dev, (void *)t->far.ly_dev}) pool_release(q);
+    se_state_free(t->se);
     delete t;
     return MHS_OK;
 }
@@ -680,7 +681,7 @@ extern "C" {
 int mhs_tps_free(mhs_tps *t) {
     if (!t) return MHS_OK;
     // evaluations are asynchronous on the caller's streams: ONE device-wide wait (hipFree made six) before the blocks go back
-    if (t->knots_dev && ctx().ready) (void)hipDeviceSynchronize();
+    if ((t->knots_dev || t->se) && ctx().ready) (void)hipDeviceSynchronize();
     return tps_free_quiet(t);
 }
 

@@ -2378,6 +2378,7 @@ int tps_fit_lane(FitLane &L, const double *xy, const double *y, int64_t N, doubl
     t->c.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) t->c[i] = sw[i] * ct[i];
     t->knots_uv = uv;
+    t->prep = std::make_shared<const TpsPrep>(prep);
     if (int rc = upload_knots(t)) { mhs_tps_free(t); return rc; }
     *out = t;
     return MHS_OK;

@@ -126,6 +126,35 @@ def tps_residual_surface(geom: Geometry, knots_xy, resid, cov1_at_stations=None,
     return tiles.mosaic_feather(geom, nRx, nCx, keep_win, bufs, merge_mode=False, out=out)
 
 
+def tps_residual_surface_se(geom: Geometry, knots_xy, resid, cov1_at_stations=None, tile_edge: int = 1500,
+                            lambda_=None, gcv_mode: str = "fields", out=None):
+    """The standard-error plane of :func:`tps_residual_surface` (mhs_tps_surface_se_dev): fields::predictSE.Krig of
+    every tile's own fit with its own sigma^2 hat on its keep window, blended by the same mosaic and seam feathering
+    (an upper bound on the SE of the blended estimate; equal if the tiles' errors were perfectly correlated).  Cells
+    that only zero tiles (fewer than 10 stations) cover are NaN.  tile_edge=None forces the global fit."""
+    import ctypes as C
+    import torch
+    dev = torch.device("cuda", _lib.init())
+    knots_xy = np.asarray(knots_xy, dtype=np.float64)
+    resid = np.ascontiguousarray(resid, dtype=np.float64)
+    if out is None:
+        out = torch.empty((geom.nrow, geom.ncol), dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1:
+        raise ValueError("out must be a 2-D float64 device tensor with unit column stride")
+    g = geom.c_struct()
+    xyf = np.asfortranarray(knots_xy)
+    cov = None if cov1_at_stations is None else np.ascontiguousarray(cov1_at_stations, dtype=np.float64)
+    nt = (C.c_int64 * 2)()
+    mode = {"fields": _lib.GCV_FIELDS, "converged": _lib.GCV_CONVERGED}[gcv_mode]
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib().mhs_tps_surface_se_dev(C.byref(g), xyf.ctypes.data, resid.ctypes.data, resid.shape[0],
+                                                 None if cov is None else cov.ctypes.data,
+                                                 0 if tile_edge is None else int(tile_edge),
+                                                 float("nan") if lambda_ is None else float(lambda_), mode,
+                                                 out.data_ptr(), out.stride(0), nt, st))
+    return out
+
+
 def complete_cases(stack: RasterStack, int_values):
     """``Mydata[complete.cases(Mydata),]`` (V73:154): the reference filters ONCE over every column of the
     joined table -- long, lat, every response layer and every extracted covariate -- so a station with an NA

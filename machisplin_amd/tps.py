@@ -3,6 +3,8 @@
 ``Tps(x, Y)``            <-> ``fields::Tps(x, Y)``                    V73:722, V73:751
 ``interpolate(geom, m)`` <-> ``terra::interpolate(terra::rast(rb), m)`` V73:726, V73:753
 ``m.predict(xy)``        <-> ``predict(m, xy)`` (predict.Krig)
+``m.predict_se(xy)``     <-> ``predictSE(m, xy)`` (predictSE.Krig)
+``interpolate_se(geom, m)`` <-> ``terra::interpolate(r, m, fun = predictSE)``
 
 All arithmetic runs in libmachisplin_hip.so (HIP, gfx950); this module only marshals
 arguments.  There is no CPU path.
@@ -84,6 +86,23 @@ class Tps:
                                                      out.ctypes.data))
         return out
 
+    @property
+    def sigma2(self) -> float:
+        """The fit's sigma^2 hat = (RSS_w(lambda) + pure_ss) / (N - eff_df) (fields' shat.GCV^2), the sigma^2 that
+        :meth:`predict_se` uses by default.  Raises for a spline built by :meth:`from_coef` (no observations)."""
+        s2 = C.c_double()
+        _lib.check(_lib.lib().mhs_tps_sigma2(self._h, C.byref(s2)))
+        return s2.value
+
+    def predict_se(self, xy, sigma2=None) -> np.ndarray:
+        """fields::predictSE(fit, xy): standard error of the prediction at arbitrary points (n x 2: LONG, LAT), with
+        rho = sigma2 / lambda; sigma2=None takes :attr:`sigma2` (required for a :meth:`from_coef` spline)."""
+        xy = np.asfortranarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+        out = np.empty(xy.shape[0])
+        s2 = math.nan if sigma2 is None else float(sigma2)
+        _lib.check(_lib.lib().mhs_tps_predict_se_points(self._h, xy.ctypes.data, xy.shape[0], s2, out.ctypes.data))
+        return out
+
     def eval_plan(self):
         """(tile_cols, tile_rows, node_pairs, cell_pairs) of this handle's last grid evaluation; tile 0 x 0 means
         the direct sum ran."""
@@ -160,6 +179,28 @@ def interpolate(geom: Geometry, model: Tps, window=None, out=None, stream=None, 
     if b1 > b0:
         _lib.check(_lib.lib().mhs_tps_predict_rows_dev(model._h, C.byref(g), r0, r1, c0, c1, b0, b1,
                                                        out.data_ptr(), out.stride(0), s))
+    return out
+
+
+def interpolate_se(geom: Geometry, model: Tps, window=None, out=None, stream=None, sigma2=None):
+    """terra::interpolate(r, fit, fun = predictSE): the standard error of the prediction at every cell centre of
+    ``geom`` (or of the window (r0, r1, c0, c1)) -- the cells :func:`interpolate` evaluates.  ``sigma2=None`` takes the
+    fit's own :attr:`Tps.sigma2`.  Returns a float64 device tensor of the window's shape (``out`` as in
+    :func:`interpolate`)."""
+    import torch
+    r0, r1, c0, c1 = window if window is not None else (0, geom.nrow, 0, geom.ncol)
+    dev = torch.device("cuda", _lib.init())
+    if out is None:
+        out = torch.empty((r1 - r0, c1 - c0), dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1:
+        raise ValueError("out must be a 2-D float64 device tensor with unit column stride")
+    if tuple(out.shape) != (r1 - r0, c1 - c0):
+        raise ValueError("out has the wrong shape for the window")
+    g = geom.c_struct()
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    s2 = math.nan if sigma2 is None else float(sigma2)
+    _lib.check(_lib.lib().mhs_tps_predict_se_grid_dev(model._h, C.byref(g), r0, r1, c0, c1, s2, out.data_ptr(),
+                                                      out.stride(0), s))
     return out
 
 
