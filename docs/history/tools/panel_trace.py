@@ -1,4 +1,4 @@
-"""Phase stamps of band_panel_reg_kernel.  Needs a library built with -DMHS_PANEL_TRACE (tps_fit.hip):
+"""Phase stamps of band_panel_reg_kernel.  Needs a library built with -DMHS_PANEL_TRACE (tps_band8.hip):
    make -C machisplin_amd/csrc CXXFLAGS+=-DMHS_PANEL_TRACE   (then rebuild without it)."""
 import ctypes as C, os, sys
 import numpy as np

@@ -29,7 +29,7 @@ constexpr int LOG_TAB_BITS = 10;
 constexpr int LOG_TAB_N = 1 << LOG_TAB_BITS;
 
 // Everything one spline fit needs to run independently of another one: two streams (the panel
-// factorisations run ahead of the trailing update, tps_fit.hip), a pool of timing-disabled events and a
+// factorisations run ahead of the trailing update, tps_band8.hip / tps_band32.hip), a pool of timing-disabled events and a
 // grow-only device arena its work buffers are carved from (no hipMalloc / hipFree -- a device-wide
 // synchronisation -- per fit).  mhs_tps_fit uses lane 0; mhs_tps_surface fits its tiles on several lanes
 // from host threads.

@@ -1,7 +1,7 @@
 // GCV route of the spline fit, round 4: fields::Tps(x, Y) (V73:722, V73:751) needs lambda = arg min GCV over B = Q2'KQ2.
 //
 // Round 1-3 reduced B to a band of width 8 with 8-column Householder panels -- n/8 panels, each a chain of three globally
-// dependent launches: 624 links at n = 5 000, 52 of the fit's 62 ms, 3 % of the FP64 peak (tps_fit.hip, kept as the
+// dependent launches: 624 links at n = 5 000, 52 of the fit's 62 ms, 3 % of the FP64 peak (tps_band8.hip, kept as the
 // fallback).  This file cuts the DEPTH of that chain:
 //
 //   stage 1   B = Q Bb Q', Bb of bandwidth 32, with 32-COLUMN panels: n/32 links.  A panel P (t x 32) is factorised by
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(256) void b32_wfin_kernel(int t, int cpb, const dou
 
 // K5: A22 -= V W' + W V' = Z Zs' with Z = [V | W] (t x 64, column-major, stride vs) and Zs = [W | V], on the 128 x 128 tiles
 // on and below the diagonal of the t x t block (round 6: the upper triangle is never read again -- the symmetric product
-// takes it from its mirror image -- so it is not updated either).  The tile loop is tps_fit.hip's band_rankk_kernel with K = 64: 4 waves
+// takes it from its mirror image -- so it is not updated either).  The tile loop is tps_band8.hip's band_rankk_kernel with K = 64: 4 waves
 // x 64 x 64, K streamed through two LDS buffers in chunks of 16, the C tile preloaded into the accumulators with a negated
 // operand.  col0_only: the first block column only (look-ahead: the next panel lives in its first 32 columns).
 constexpr int RK_T = 128, RK_KC = 16, RK_S = RK_T + 16, RK_K = 2 * NB;

@@ -1,4 +1,4 @@
-// Host-side pieces of the TPS fit (tps_gcv_host.hip), shared with tps_fit.hip.
+// Host-side pieces of the TPS fit (tps_gcv_host.hip), shared with tps_fit.hip and its routes.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -21,7 +21,7 @@ struct TridiagGcv {
 };
 
 // The same criterion on a symmetric BANDED form (bandwidth bw): the GPU reduces B only to a band
-// (blocked, BLAS-3 style; tps_fit.hip) and every GCV evaluation is a banded Cholesky, a banded
+// (blocked, BLAS-3 style; tps_band8.hip) and every GCV evaluation is a banded Cholesky, a banded
 // solve and the trace of the inverse by Takahashi's selected inversion, O(m bw^2).
 // ab: lower band, column-major: ab[d + (bw + 1) * j] = M[j + d][j], d = 0..bw.
 struct BandGcv {
