@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <chrono>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -137,6 +138,9 @@ int h2d_sync(void *dst, const void *src, size_t bytes);
 // _dev entry points launch on exactly the stream they are given; NULL is HIP's default
 // (null) stream, which is also torch's default stream.
 inline hipStream_t pick_stream(void *s) { return (hipStream_t)s; }
+inline double now_ms() {   // host wall clock, for the MHS_TIMING reports and the multi-device drivers' step records
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 // device buffer with RAII for temporaries inside one ABI call
 template <typename T>
@@ -176,7 +180,7 @@ int tps_predict_rows_dev(const mhs_tps *t, const mhs_grid *g, int64_t r0, int64_
 
 struct mhs_model;
 namespace mhs {
-// ensemble.hip: the handle's twin on device slot `slot` (built on first use; owned by the handle)
+// models.hip: the handle's twin on device slot `slot` (built on first use; owned by the handle)
 int model_on_slot(const mhs_model *m, int slot, const mhs_model **out);
 // ensemble.hip: pred.elev on grid rows [b0, b1) from a device buffer holding only those rows of every plane
 int members_rows_dev(const mhs_model *const *models, const double *weights, int n_models, int accumulate, int scale, double wt_total,

@@ -1,6 +1,8 @@
-// Internal to the ensemble translation units (ensemble.hip: lm, nnet, earth, ksvm, gbm, the member sequence and the C entry
-// points; forest.hip: randomForest): the model handle, the window / stack descriptions every member kernel takes, the
-// rank-key lookup gbm and randomForest share, and the host helpers that build their geometry-dependent tables.
+// Internal to the ensemble translation units (ensemble.hip: the kernels of lm, nnet, earth, ksvm and gbm, their launchers, the
+// member sequence and the device-pointer / points entry points; forest.hip: randomForest; models.hip: the model handle's
+// loaders, replicas and release; ensemble_host.hip: the host-pointer pipelines): the model handle, the window / stack
+// descriptions every member kernel takes, the rank-key lookup gbm and randomForest share, and the host helpers that build
+// their geometry-dependent tables.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -16,6 +18,7 @@ enum { K_LM = 0, K_NNET = 1, K_EARTH = 2, K_SVR = 3, K_GBM = 4, K_RF = 5 };
 namespace mhs {
 
 constexpr int PMAX = 12;  // predictors supported by the register-resident kernels
+constexpr double EXP_RANGE = 700.0;   // ksvm: exponents below -700 count as -700 (1e-304); folded into the support vectors at load
 
 struct PredGeom {
     double xmin, ymax, xres, yres;
@@ -155,6 +158,7 @@ constexpr int LUT_R = 4;            // cells per lane
 constexpr int LUT_CHUNK = 64;       // trees per LDS chunk
 constexpr int LUT_META_DW = 12;     // dwords of meta per tree: c[6] (float), key offset[6]
 constexpr int LUT_COARSE = 4096;    // floats of the coarse rank table (aliases the LUT chunk buffer)
+constexpr int BAND_ALIGN = 4 * LUT_R;   // row bands of a window are cut at multiples of this many grid rows (gbm_coherent_kernel's tile height)
 
 typedef float float2v __attribute__((ext_vector_type(2)));
 
@@ -224,6 +228,8 @@ static int to_device(const T *h, size_t n, T **d) {
     if (n) MHS_HIP(hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice));
     return MHS_OK;
 }
+
+inline size_t dtype_bytes(int dtype) { return dtype == MHS_F64 ? 8 : dtype == MHS_F32 ? 4 : 2; }   // of a stack's elements
 
 constexpr int TREE_R = 2;
 constexpr size_t LDS_LIMIT = 150 * 1024;     // of the 160 KiB per CU
@@ -329,9 +335,15 @@ static int publish_axis_ranks(mhs_model *m, const std::vector<std::vector<KT>> &
 }
 
 
-// ensemble.hip
+// models.hip
 int finish_trees(mhs_model *m, const std::vector<Node> &nodes, const std::vector<int> &off);
 int check_common(int p, mhs_model **out);
+// ensemble.hip: what the host-pointer pipelines (ensemble_host.hip) reach the device through
+int make_geom(const mhs_grid *g, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int64_t ld, PredGeom *pg);
+StackDev rows_stack(const void *buf, int64_t r0, int64_t r1, int n_layers, int dtype, int64_t ld, double nodata);
+int launch_members(const mhs_model *const *models, const double *weights, int n_models, const StackDev &s, const PredGeom &g,
+                   int accumulate_first, double *out, hipStream_t st, const mhs_grid *grid);
+int scale_window(double *out, int64_t nr, int64_t nc, int64_t ld, double wt_total, hipStream_t st);
 // forest.hip: randomForest on a grid window with the level-synchronous walk kernels; *launched = false: none of them applies
 // (points mode, trees too large, MHS_TREES_GENERIC) and the caller falls back to the generic node walk
 int launch_forest(const mhs_model *m, const StackDev &s, const PredGeom &g, const mhs_grid *grid, double weight, int accumulate,

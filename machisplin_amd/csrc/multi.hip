@@ -41,11 +41,7 @@ using namespace mhs;
 
 namespace {
 
-constexpr int64_t BAND_ROWS_ALIGN = 16;      // = ensemble.hip's BAND_ALIGN: bands of whole coherent-kernel tiles
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+constexpr int64_t BAND_ROWS_ALIGN = 16;      // = ensemble_int.h's BAND_ALIGN: bands of whole coherent-kernel tiles
 
 // ---------------------------------------------------------------------------------- per-slot resources --
 struct MultiSlot {
@@ -541,7 +537,7 @@ namespace {
 
 // rows [r0, r1) in sub-bands, cut at whole 16-row tiles of the grid; returns how many.  Copies up: the short ones first -- 4,
 // 16, 40, 40 %, or for float64 planes (twice the bytes per row: the copies are then only ~2 x faster than the kernels that
-// wait for them, see host_window_pipeline in ensemble.hip) 3, 6, 13, 28, 50 %.  Copies down: the short ones last, 48, 30, 14, 6, 2 %.
+// wait for them, see host_window_pipeline in ensemble_host.hip) 3, 6, 13, 28, 50 %.  Copies down: the short ones last, 48, 30, 14, 6, 2 %.
 enum { BANDS_UP = 0, BANDS_UP_F64 = 1, BANDS_DOWN = 2 };
 constexpr int MAX_SUB = 5;
 int sub_bands(int64_t r0, int64_t r1, int mode, int64_t cut[MAX_SUB + 1]) {

@@ -29,7 +29,7 @@ FIT_RESERVE_CANDIDATES = (0, 32, 64, 96)
 
 
 # Bands are cut at multiples of this many grid rows: the coherent gbm kernel sums a cell's trees in an order that depends on
-# the 16 x 16-cell tile the cell sits in (tiles anchored to the grid, csrc/ensemble.hip BAND_ALIGN), so bands of whole tiles
+# the 16 x 16-cell tile the cell sits in (tiles anchored to the grid, csrc/ensemble_int.h BAND_ALIGN), so bands of whole tiles
 # reproduce the one-GPU planes bit for bit.
 BAND_ALIGN = 16
 
