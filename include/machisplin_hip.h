@@ -270,6 +270,28 @@ MHS_API int mhs_svr_load(const double *alpha, const double *sv, int64_t nsv, int
 MHS_API int mhs_gbm_load(double init_f, int64_t n_trees, const int64_t *tree_offsets,
                          const int32_t *split_var, const double *split_val, const int32_t *left,
                          const int32_t *right, const int32_t *missing, int p, mhs_model **out);
+/* gbm::gbm / gbm.more as machisplin.gbm.step drives them -- V73:1772 (the first n.trees of every fold model), V73:1908
+ * (gbm.more in the stage loop), V73:2101 (the final model); distribution = "gaussian", no weights, no offset,
+ * train.fraction = 1 -- for `count` independent models in ONE launch, a resident workgroup per model.  The models share
+ * p, interaction_depth, n_minobsinnode and shrinkage; model k has its own rows X[k] (n[k] x p column-major, no NA:
+ * V73:154), responses y[k] and bags.  Bagging is RNG-dependent, so the bags are the caller's: bags[k] is n_new x
+ * bag_size[k] row-major, the 0-based row indices (distinct within a tree) that tree t is grown on.  Given the bags gbm's
+ * CART is deterministic: best-first, up to interaction_depth splits, a candidate between consecutive distinct values
+ * with >= n_minobsinnode bag rows on both sides, improvement nL nR / (nL + nR) (meanL - meanR)^2, ties to the first
+ * variable / lowest position / earliest terminal node; every split adds a left, a right and a missing child (the
+ * parent's mean).  F[k] (n[k], in / out) is the model's fit on ALL its rows: with first_call != 0 it is set to mean(y)
+ * and init_f[k] is written, otherwise the F of the previous call is continued (gbm.more; init_f may be NULL).
+ * Outputs per model, in mhs_gbm_load's layout and gbm's stored node order (preorder: node, left, right, missing):
+ * tree_offsets[k] (n_new + 1, from 0) and the five node arrays, each with room for n_new * (3 interaction_depth + 1)
+ * nodes; terminal SplitCodePred carries the shrinkage.  The left sums are accumulated 64 rows at a time (gbm_fit.hip),
+ * not row by row as gbm does: results are bit-reproducible, and equal gbm's up to the last bits of the improvements.
+ * MHS_ERR_INVALID: NaN / infinite X or y, a bag index outside [0, n), bag_size > n, p outside mhs_gbm_load's range.
+ * replaces gbm::gbm / gbm::gbm.more inside machisplin.gbm.step V73:1772, 1908, 2101 (called at V73:247, 493)          */
+MHS_API int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                              const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth,
+                              int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
+                              int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
+                              int32_t *const *left, int32_t *const *right, int32_t *const *missing);
 /* randomForest regression $forest (V73:517): per-tree columns concatenated
  * (leftDaughter/rightDaughter 1-based tree-local, nodestatus -1 terminal, bestvar
  * 1-based, xbestsplit, nodepred).

@@ -121,6 +121,17 @@ mhs_tps_surface_se <- function(rast_stack, dat, res.FINAL, n.covars, tile.edge =
   f <- .Call("mhsr_nnet_fit", X, as.numeric(trainNN[, 1]), runif((p + 1) * 10 + 11, -0.7, 0.7), as.integer(maxit))
   list(handle = .Call("mhsr_nnet_load", f[[1]], p, 10L, max2.resp.f, min.resp.f), wts = f[[1]], value = f[[2]], convergence = f[[4]])
 }
+# gbm::gbm / gbm::gbm.more inside machisplin.gbm.step (V73:1772 per fold, V73:1908 per stage, V73:2101 final): n.new more trees
+# for ALL the given models in one device call.  Xs / ys: lists (one per fold model: x.data[model.mask, ], y.data[model.mask]);
+# state: NULL for the first trees, else what the previous call returned.  The bags are drawn HERE with R's RNG
+# (sample.int without replacement, floor(bag.fraction * n) rows per tree), so set.seed() governs them as it governs gbm's.
+.mhs_gbm_grow <- function(Xs, ys, n.new, state = NULL, tree.complexity = 25L, learning.rate = 0.01, bag.fraction = 0.5,
+                          n.minobsinnode = 10L) {
+  Xs <- lapply(Xs, as.matrix); ys <- lapply(ys, as.numeric)
+  bags <- lapply(Xs, function(X) { b <- replicate(n.new, sample.int(nrow(X), floor(bag.fraction * nrow(X)))); storage.mode(b) <- "integer"; b })
+  Fs <- if (is.null(state)) NULL else lapply(state, function(s) s[[1]])
+  .Call("mhsr_gbm_grow", Xs, ys, bags, as.integer(tree.complexity), as.integer(n.minobsinnode), learning.rate, Fs)
+}
 # inside machisplin.gbm.step's loop (V73:1843, 1919): the hold-out predictions of fold model i for every stage at once,
 # instead of one predict.gbm per gbm.more
 .mhs_gbm_holdout_stages <- function(handle, x.holdout, step.size, n.fitted)

@@ -267,6 +267,83 @@ SEXP mhsr_nnet_fit(SEXP X, SEXP y, SEXP wts0, SEXP maxit) {
     return out;
 }
 
+/* gbm::gbm / gbm::gbm.more inside machisplin.gbm.step (V73:1772, 1908, 2101; called at V73:247, 493) for several models in one
+ * device call: Xs, ys = lists of double matrices / vectors (one per model, same ncol), bags = list of INTEGER matrices
+ * bag_size x n_new (column t = the 1-based rows tree t is grown on, e.g. replicate(n_new, sample.int(n, bag_size)): R's own
+ * RNG draws them), Fs = NULL for the first trees or the list of $F vectors a previous call returned (gbm.more).
+ * returns a list with, per model, list(F, init_f, tree_offsets, SplitVar, SplitCodePred, LeftNode, RightNode, MissingNode)
+ * in mhs_gbm_load's layout (0-based, tree-local children); init_f is NA on a gbm.more call */
+SEXP mhsr_gbm_grow(SEXP Xs, SEXP ys, SEXP bags, SEXP depth, SEXP minobs, SEXP shrinkage, SEXP Fs) {
+    if (TYPEOF(Xs) != VECSXP || TYPEOF(ys) != VECSXP || TYPEOF(bags) != VECSXP) Rf_error("mhsr_gbm_grow: Xs, ys and bags must be lists");
+    int count = Rf_length(Xs), first = Rf_isNull(Fs), d = Rf_asInteger(depth);
+    if (count < 1 || Rf_length(ys) != count || Rf_length(bags) != count || (!first && (TYPEOF(Fs) != VECSXP || Rf_length(Fs) != count)))
+        Rf_error("mhsr_gbm_grow: need one y, one bag matrix (and one F) per X");
+    if (d == NA_INTEGER || d < 1 || d > 64) Rf_error("mhsr_gbm_grow: interaction.depth must be 1..64");
+    int p = Rf_ncols(VECTOR_ELT(Xs, 0)), n_new = Rf_ncols(VECTOR_ELT(bags, 0));
+    if (n_new < 1) Rf_error("mhsr_gbm_grow: the bag matrices have no columns");
+    const double **X = (const double **)R_alloc((size_t)count, sizeof(*X)), **y = (const double **)R_alloc((size_t)count, sizeof(*y));
+    const int32_t **b = (const int32_t **)R_alloc((size_t)count, sizeof(*b));
+    int64_t *n = (int64_t *)R_alloc((size_t)count, sizeof(*n)), *bs = (int64_t *)R_alloc((size_t)count, sizeof(*bs));
+    for (int k = 0; k < count; ++k) {
+        SEXP Xk = VECTOR_ELT(Xs, k), yk = VECTOR_ELT(ys, k), bk = VECTOR_ELT(bags, k);
+        if (!Rf_isReal(Xk) || !Rf_isMatrix(Xk) || Rf_ncols(Xk) != p || !Rf_isReal(yk) || Rf_length(yk) != Rf_nrows(Xk))
+            Rf_error("mhsr_gbm_grow: model %d: X must be a double matrix with %d columns and y a double vector of nrow(X)", k + 1, p);
+        if (TYPEOF(bk) != INTSXP || !Rf_isMatrix(bk) || Rf_ncols(bk) != n_new || Rf_nrows(bk) < 1 || Rf_nrows(bk) > Rf_nrows(Xk))
+            Rf_error("mhsr_gbm_grow: model %d: bags must be an integer matrix bag_size x %d with bag_size <= nrow(X)", k + 1, n_new);
+        if (!first && (!Rf_isReal(VECTOR_ELT(Fs, k)) || Rf_length(VECTOR_ELT(Fs, k)) != Rf_nrows(Xk)))
+            Rf_error("mhsr_gbm_grow: model %d: F must be a double vector of nrow(X)", k + 1);
+        n[k] = Rf_nrows(Xk); bs[k] = Rf_nrows(bk);
+        X[k] = REAL(Xk); y[k] = REAL(yk);
+        int32_t *z = (int32_t *)R_alloc((size_t)bs[k] * n_new, sizeof(int32_t));
+        for (R_xlen_t e = 0; e < (R_xlen_t)bs[k] * n_new; ++e) {
+            if (INTEGER(bk)[e] == NA_INTEGER) Rf_error("mhsr_gbm_grow: model %d: NA in bags", k + 1);
+            z[e] = INTEGER(bk)[e] - 1;
+        }
+        b[k] = z;
+    }
+    const size_t cap = (size_t)n_new * (3 * (size_t)d + 1);
+    double **F = (double **)R_alloc((size_t)count, sizeof(*F)), **val = (double **)R_alloc((size_t)count, sizeof(*val));
+    double *init = (double *)R_alloc((size_t)count, sizeof(double));
+    int64_t **off = (int64_t **)R_alloc((size_t)count, sizeof(*off));
+    int32_t **iv[4];
+    for (int a = 0; a < 4; ++a) iv[a] = (int32_t **)R_alloc((size_t)count, sizeof(int32_t *));
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, count));
+    for (int k = 0; k < count; ++k) {
+        SEXP Fk = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)n[k]));
+        if (!first) for (int64_t i = 0; i < n[k]; ++i) REAL(Fk)[i] = REAL(VECTOR_ELT(Fs, k))[i];
+        SEXP mk = PROTECT(Rf_allocVector(VECSXP, 8));
+        SET_VECTOR_ELT(mk, 0, Fk);
+        SET_VECTOR_ELT(out, k, mk);
+        UNPROTECT(2);
+        F[k] = REAL(Fk);
+        off[k] = (int64_t *)R_alloc((size_t)n_new + 1, sizeof(int64_t));
+        val[k] = (double *)R_alloc(cap, sizeof(double));
+        for (int a = 0; a < 4; ++a) iv[a][k] = (int32_t *)R_alloc(cap, sizeof(int32_t));
+    }
+    int rc = mhs_gbm_grow_many(count, X, y, n, p, b, bs, n_new, d, Rf_asInteger(minobs), Rf_asReal(shrinkage), first, F, init, off,
+                               iv[0], val, iv[1], iv[2], iv[3]);
+    if (rc == 0)
+        for (int k = 0; k < count; ++k) {
+            SEXP mk = VECTOR_ELT(out, k);
+            const R_xlen_t nn = (R_xlen_t)off[k][n_new];
+            SEXP o = PROTECT(Rf_allocVector(REALSXP, n_new + 1)), v = PROTECT(Rf_allocVector(REALSXP, nn));
+            for (int t = 0; t <= n_new; ++t) REAL(o)[t] = (double)off[k][t];
+            for (R_xlen_t e = 0; e < nn; ++e) REAL(v)[e] = val[k][e];
+            SET_VECTOR_ELT(mk, 1, Rf_ScalarReal(first ? init[k] : R_NaReal)); SET_VECTOR_ELT(mk, 2, o); SET_VECTOR_ELT(mk, 4, v);
+            UNPROTECT(2);
+            static const int slot[4] = {3, 5, 6, 7};
+            for (int a = 0; a < 4; ++a) {
+                SEXP w = PROTECT(Rf_allocVector(INTSXP, nn));
+                for (R_xlen_t e = 0; e < nn; ++e) INTEGER(w)[e] = iv[a][k][e];
+                SET_VECTOR_ELT(mk, slot[a], w);
+                UNPROTECT(1);
+            }
+        }
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* gbm::predict.gbm(model, x.data[pred.mask, ], n.trees = k * step) for k = 1 .. in one pass (V73:1843, 1919): returns the
  * n x stages matrix machisplin.gbm.step's hold-out deviance curve is computed from */
 SEXP mhsr_gbm_staged_points(SEXP model, SEXP X, SEXP step, SEXP n_trees) {

@@ -2,7 +2,8 @@
 k-fold cross-validation (V73:225-319) on the GPU, and the ensemble weight search that consumes them
 (V73:326-393); rank 4: the tree-count search of machisplin.gbm.step over grown fold models (gbm_step_search).
 
-Fitting the fold models stays in the CRAN packages (R); what runs here is what R does with
+Fitting the fold models of earth and randomForest stays in the CRAN packages (R); the other members have device fits
+(models.py), and :func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
 ``terra::predict(model, test)`` inside the fold loop: every fold's models evaluated at that fold's hold-out
 rows through ``mhs_predict_points``, the residual vectors concatenated in fold order, and
 ``optimx(par = 0.5, lower = 0, upper = 1, method = "L-BFGS-B")`` on
@@ -95,7 +96,7 @@ def optx_weights(residuals, smooth_only: bool = False):
 def gbm_step_search(fold_models, X, y, selector, step: int = 50, tolerance: float = 0.001, max_trees: int = 10000,
                     site_weights=None):
     """The tree-count search of ``machisplin.gbm.step`` (V73:1765-1981) over fold models that gbm has grown far enough
-    (growing them -- gbm::gbm / gbm.more with bag.fraction = 0.5 -- is RNG-dependent and stays in the package):
+    (grown by gbm in R, or by :func:`models.gbm_fit_many`; :func:`gbm_step` does both the growing and this search):
 
     * fold i's model predicts its hold-out rows (``selector == i``) at n.trees = step, 2 step, ... in ONE device walk
       (:meth:`models.Gbm.staged_predict_points`; R calls predict.gbm once per stage, V73:1843, 1919);
@@ -121,20 +122,86 @@ def gbm_step_search(fold_models, X, y, selector, step: int = 50, tolerance: floa
         P = m.staged_predict_points(X[mask], step)
         d = y[mask][None, :] - P
         staged.append(np.sum(d * d, axis=1) / int(mask.sum()))
-    n_fitted = step
+
+    def stage_loss(j):
+        if j > len(staged[0]):
+            raise ValueError("fold models have fewer trees than the search needs")
+        return float(np.mean([s[j - 1] for s in staged]))
+    return _gbm_step_rule(stage_loss, tolerance_test, step, step, max_trees)
+
+
+def _gbm_step_rule(stage_loss, tolerance_test, first: int, step: int, max_trees: int):
+    """The stopping rule of machisplin.gbm.step (V73:1872-1981) shared by :func:`gbm_step_search` and :func:`gbm_step`:
+    ``stage_loss(j)`` is cv.loss.values[j] (j = 1: after the first ``first`` trees, then ``step`` more per stage), asked
+    for stage by stage.  Returns ``(target_trees, cv_loss_values, trees_fitted)`` or None on the early-rise abort."""
+    n_fitted = first
     trees = [n_fitted]
-    cv = [float(np.mean([s[0] for s in staged]))]
+    cv = [stage_loss(1)]
     delta, j = 1.0, 1
     while delta > tolerance_test and n_fitted < max_trees:
         n_fitted += step
         trees.append(n_fitted)
         j += 1
-        if j > len(staged[0]):
-            raise ValueError("fold models have fewer trees than the search needs")
-        cv.append(float(np.mean([s[j - 1] for s in staged])))
+        cv.append(stage_loss(j))
         if j < 5 and cv[j - 1] > cv[j - 2]:
             return None
         if j >= 20:
             delta = float(np.mean(cv[j - 20:j - 9]) - np.mean(cv[j - 10:j]))
     cv = np.array(cv)
     return trees[int(np.argmax(cv == cv.min()))], cv, np.array(trees)
+
+
+def gbm_step(X, y, fold_vector=None, seed=0, tree_complexity=25, learning_rate=0.01, bag_fraction=0.5, n_folds=10,
+             n_trees=50, step_size=50, max_trees=10000, tolerance=0.001, n_minobsinnode=10):
+    """``machisplin.gbm.step(tree.complexity = 25, learning.rate = 0.01, bag.fraction = 0.5)`` (V73:247, V73:493;
+    gaussian, no site weights, no prevalence stratification) with the growing on the device:
+
+    * the selector is ``fold_vector`` (1-based fold labels) or, as V73:1748-1749, ``rep(1 .. n_folds, length = n)`` in
+      a random order -- here a permutation from ``numpy.random.default_rng(seed)``, not R's ``runif`` stream;
+    * the ``n_folds`` fold models (fold i trained on ``selector != i``) grow ``n_trees`` trees (V73:1772), then
+      ``step_size`` more per stage (gbm.more, V73:1908), ALL folds in one device call per stage
+      (:func:`models.gbm_fit_many` / :func:`models.gbm_more_many`); fold i's bags come from ``default_rng([seed, i])``;
+    * after every stage each fold model predicts its hold-out rows (:meth:`models.Model.predict_points`) and the mean
+      hold-out deviance joins the loss curve; the stopping rule is the one of :func:`gbm_step_search`;
+    * the final model is grown on all rows with ``target_trees`` trees (V73:2101), bags from ``default_rng([seed, n_folds])``.
+
+    Returns ``(final_model, target_trees, cv_loss_values, trees_fitted)`` -- the final model also carries
+    ``.fold_vector`` and ``.fold_models`` (as grown when the search stopped) -- or None on the early-rise abort."""
+    from . import models as _models
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    n = y.size
+    if fold_vector is None:
+        selector = np.resize(np.arange(1, n_folds + 1), n)[np.random.default_rng(seed).permutation(n)]
+    else:
+        selector = np.asarray(fold_vector)
+        if selector.size != n:
+            raise ValueError("fold_vector needs one label per row")
+        n_folds = int(selector.max())
+    tolerance_test = float(np.sum((y - y.mean()) * (y - y.mean()))) / n * tolerance
+    hold = [np.flatnonzero(selector == i + 1) for i in range(n_folds)]
+    train = [np.flatnonzero(selector != i + 1) for i in range(n_folds)]
+    Xh = [np.ascontiguousarray(X[h]) for h in hold]
+    state = {"folds": None}
+
+    def stage_loss(j):
+        if j == 1:
+            state["folds"] = _models.gbm_fit_many([X[t] for t in train], [y[t] for t in train], n_trees, None,
+                                                  [[int(seed), i] for i in range(n_folds)], tree_complexity, learning_rate,
+                                                  bag_fraction, n_minobsinnode)
+        else:
+            state["folds"] = _models.gbm_more_many(state["folds"], step_size)
+        loss = []
+        for m, h, xh in zip(state["folds"], hold, Xh):
+            d = y[h] - m.predict_points(xh)
+            loss.append(np.sum(d * d) / h.size)
+        return float(np.mean(loss))
+
+    res = _gbm_step_rule(stage_loss, tolerance_test, n_trees, step_size, max_trees)
+    if res is None:
+        return None
+    target, cv, trees = res
+    final = _models.gbm_fit_many([X], [y], target, None, [[int(seed), n_folds]], tree_complexity, learning_rate, bag_fraction,
+                                 n_minobsinnode)[0]
+    final.fold_vector, final.fold_models = selector, state["folds"]
+    return final, target, cv, trees

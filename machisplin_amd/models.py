@@ -1,7 +1,8 @@
 """Host-side mirror of the six fitted ensemble members as the hot path sees them:
 flat parameter arrays in, ``terra::predict(rast_stack, model)`` /
-``predict(model, data.frame)`` out (V73:447-619).  Model FITTING is out of scope and stays
-in the CRAN packages; these classes wrap what the fitted R objects contain.  All
+``predict(model, data.frame)`` out (V73:447-619).  These classes wrap what the fitted R objects contain; the
+members with a device fit (gam, ksvm, nnet, gbm) have a ``fit`` classmethod, the others are fitted in their CRAN
+packages.  All
 arithmetic runs in libmachisplin_hip.so; there is no CPU path.
 """
 from __future__ import annotations
@@ -192,6 +193,123 @@ class Gbm(Model):
         if out.size:
             _lib.check(_lib.lib().mhs_gbm_staged_points(self._h, X.ctypes.data, X.shape[0], int(step), out.ctypes.data))
         return out
+
+
+    @classmethod
+    def fit(cls, X, y, n_trees, bags=None, seed=0, interaction_depth=25, shrinkage=0.01, bag_fraction=0.5,
+            n_minobsinnode=10) -> "Gbm":
+        """gbm::gbm(distribution = "gaussian", n.trees, interaction.depth, shrinkage, bag.fraction, n.minobsinnode) as
+        machisplin.gbm.step calls it (V73:1772, V73:2101; tree.complexity = 25, learning.rate = 0.01, bag.fraction = 0.5
+        at V73:247), grown on the device (mhs_gbm_grow_many).  ``bags``: (n_trees, bag_size) row indices, the rows
+        tree t is grown on; ``None`` draws ``floor(bag_fraction * n)`` rows per tree without replacement from
+        ``numpy.random.default_rng(seed)`` -- NOT R's RNG stream, so the trees are gbm's for these bags, not for
+        R's ``set.seed``.  The object carries ``.params`` (the ``kind = "gbm"`` dict of :func:`from_param_dict`),
+        ``.fit`` (the model's value on the training rows) and ``.init_f``."""
+        return gbm_fit_many([X], [y], n_trees, None if bags is None else [bags], seed, interaction_depth, shrinkage,
+                            bag_fraction, n_minobsinnode)[0]
+
+    def more(self, n_trees, bags=None) -> "Gbm":
+        """gbm::gbm.more(model, n_trees) (V73:1908): a NEW model with n_trees further trees grown from this one's
+        ``.fit``; bags as in :meth:`fit` (``None`` continues this model's generator)."""
+        return gbm_more_many([self], n_trees, None if bags is None else [bags])[0]
+
+
+def _gbm_bags(bags, rngs, ns, n_trees, bag_fraction):
+    out = []
+    for k, n in enumerate(ns):
+        if bags is not None:
+            b = _i32(bags[k])
+            if b.ndim != 2 or b.shape[0] != n_trees:
+                raise ValueError("bags must be n_trees x bag_size row indices")
+        else:
+            size = int(np.floor(bag_fraction * n))
+            b = _i32(np.stack([rngs[k].permutation(n)[:size] for _ in range(n_trees)]))
+        out.append(b)
+    return out
+
+
+def _gbm_grow(Xs, ys, Fs, bags, n_trees, depth, minobs, shrinkage):
+    """mhs_gbm_grow_many; Fs None = the first call.  Returns per model (F, init_f, offsets, var, val, left, right, missing)."""
+    count = len(Xs)
+    p = Xs[0].shape[1]
+    cap = n_trees * (3 * depth + 1)
+    first = Fs is None
+    Fs = [np.empty(X.shape[0]) for X in Xs] if first else [_f64(F).copy() for F in Fs]
+    init = np.zeros(count)
+    off = [np.zeros(n_trees + 1, dtype=np.int64) for _ in range(count)]
+    var, left, right, miss = ([np.zeros(cap, dtype=np.int32) for _ in range(count)] for _ in range(4))
+    val = [np.zeros(cap) for _ in range(count)]
+    pa = lambda arrs: (C.c_void_p * count)(*[a.ctypes.data for a in arrs])
+    ns = _i64([X.shape[0] for X in Xs])
+    bs = _i64([b.shape[1] for b in bags])
+    _lib.init()
+    _lib.check(_lib.lib().mhs_gbm_grow_many(count, pa(Xs), pa(ys), ns.ctypes.data, p, pa(bags), bs.ctypes.data, int(n_trees),
+                                            int(depth), int(minobs), float(shrinkage), int(first), pa(Fs), init.ctypes.data,
+                                            pa(off), pa(var), pa(val), pa(left), pa(right), pa(miss)))
+    out = []
+    for k in range(count):
+        nn = int(off[k][-1])
+        out.append((Fs[k], float(init[k]), off[k], var[k][:nn], val[k][:nn], left[k][:nn], right[k][:nn], miss[k][:nn]))
+    return out
+
+
+def _gbm_object(params, F, state):
+    m = from_param_dict(params)
+    m.params, m.fit, m.init_f, m._grow = params, F, params["init_f"], state
+    return m
+
+
+def gbm_fit_many(Xs, ys, n_trees, bags=None, seed=0, interaction_depth=25, shrinkage=0.01, bag_fraction=0.5,
+                 n_minobsinnode=10):
+    """:meth:`Gbm.fit` for several models (each its own rows) in ONE device call, a workgroup per model: the shape of
+    machisplin.gbm.step's ten fold models (V73:1816-1919).  ``bags``: one (n_trees, bag_size) array per model; ``seed``:
+    an int (model k draws from ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or one per model."""
+    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
+    ys = [_f64(y) for y in ys]
+    if not Xs or len(Xs) != len(ys):
+        raise ValueError("need one response vector per predictor matrix")
+    for X, y in zip(Xs, ys):
+        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
+            raise ValueError("every X must be n x p with one response per row and the same p")
+    if np.ndim(seed) == 0:
+        seeds = [seed] if len(Xs) == 1 else [[int(seed), k] for k in range(len(Xs))]
+    else:
+        seeds = list(seed)
+    rngs = [np.random.default_rng(s) for s in seeds] if bags is None else [None] * len(Xs)
+    bags = _gbm_bags(bags, rngs, [X.shape[0] for X in Xs], int(n_trees), bag_fraction)
+    res = _gbm_grow(Xs, ys, None, bags, int(n_trees), interaction_depth, n_minobsinnode, shrinkage)
+    out = []
+    for k, (F, init_f, off, var, val, left, right, miss) in enumerate(res):
+        params = {"kind": "gbm", "init_f": init_f, "tree_offsets": off, "split_var": var, "split_val": val, "left": left,
+                  "right": right, "missing": miss, "p": Xs[k].shape[1]}
+        state = {"X": Xs[k], "y": ys[k], "rng": rngs[k], "depth": interaction_depth, "minobs": n_minobsinnode,
+                 "shrinkage": shrinkage, "bag_fraction": bag_fraction}
+        out.append(_gbm_object(params, F, state))
+    return out
+
+
+def gbm_more_many(models, n_trees, bags=None):
+    """:meth:`Gbm.more` for several grown models (the same depth, shrinkage and n.minobsinnode) in ONE device call."""
+    st = [getattr(m, "_grow", None) for m in models]
+    if not st or any(s is None for s in st):
+        raise ValueError("gbm.more needs models grown by Gbm.fit / gbm_fit_many")
+    key = lambda s: (s["depth"], s["minobs"], s["shrinkage"], s["X"].shape[1])
+    if any(key(s) != key(st[0]) for s in st):
+        raise ValueError("the models must share p, interaction_depth, n_minobsinnode and shrinkage")
+    if bags is None and any(s["rng"] is None for s in st):
+        raise ValueError("a model grown from explicit bags needs explicit bags to continue")
+    bags = _gbm_bags(bags, [s["rng"] for s in st], [s["X"].shape[0] for s in st], int(n_trees), st[0]["bag_fraction"])
+    res = _gbm_grow([s["X"] for s in st], [s["y"] for s in st], [m.fit for m in models], bags, int(n_trees), st[0]["depth"],
+                    st[0]["minobs"], st[0]["shrinkage"])
+    out = []
+    for m, s, (F, _, off, var, val, left, right, miss) in zip(models, st, res):
+        q = m.params
+        params = {"kind": "gbm", "init_f": q["init_f"], "tree_offsets": np.concatenate([q["tree_offsets"], q["tree_offsets"][-1] + off[1:]]),
+                  "split_var": np.concatenate([q["split_var"], var]), "split_val": np.concatenate([q["split_val"], val]),
+                  "left": np.concatenate([q["left"], left]), "right": np.concatenate([q["right"], right]),
+                  "missing": np.concatenate([q["missing"], miss]), "p": q["p"]}
+        out.append(_gbm_object(params, F, s))
+    return out
 
 
 class RandomForest(Model):
