@@ -299,6 +299,47 @@ MHS_API int mhs_gbm_grow_many(int count, const double *const *X, const double *c
 MHS_API int mhs_rf_load(int64_t n_trees, const int64_t *tree_offsets, const int32_t *left,
                         const int32_t *right, const int32_t *status, const int32_t *best_var,
                         const double *split, const double *node_pred, int p, mhs_model **out);
+/* randomForest::randomForest(mod.form, data = train) -- V73:248 (once per CV fold), V73:517 (the final model) -- as its
+ * defaults drive a regression forest (n_trees = 500, mtry = max(floor(p / 3), 1), nodesize = 5, bootstrap of n rows with
+ * replacement, numeric predictors, no NA: V73:154), for `count` independent forests in ONE launch, a resident workgroup
+ * per tree.  The forests share p, n_trees, mtry and nodesize; forest k has its own rows X[k] (n[k] x p column-major),
+ * responses y[k], bags and seeds.  The randomness is the caller's:
+ *   inbag[k]  n_trees x n[k] row-major int32: how many times row i is in tree t's bootstrap (a row with count c weighs c
+ *             in every sum and population count: the same tree as duplicating the row);
+ *   seeds[k]  n_trees uint64: tree t's seed s drives the variable draw of its node k (0-based creation index) with
+ *             mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *             z ^ z >> 31 -- ind = [0 .. p-1], last = p-1; for j in 0 .. mtry-1: i = mix(mix(s + k) + j) mod (last + 1),
+ *             take ind[i], ind[i] = ind[last], last -= 1.  The modulo bias is accepted (p <= 64).
+ * R's Mersenne-Twister stream is NOT reproduced: the forest is randomForest's for these bags and draws, not for R's
+ * set.seed (the caveat of mhs_gbm_grow_many).  Growth rule: nodes are numbered in creation order (splitting node k
+ * appends its left and then its right child); a non-root node of population <= nodesize is terminal; for every drawn
+ * variable in draw order the node's in-bag rows are walked in ascending order of the variable (stable), a candidate lies
+ * between consecutive distinct values with criterion sl^2 / nl + sr^2 / nr - tot^2 / m, only a strictly greater
+ * criterion replaces the best (lowest position within a variable, first drawn variable among variables) and a best that
+ * is not > 0 leaves the node terminal.  The RANDOM tie-break of recent randomForest releases is not reproduced.  The
+ * split value is 0.5 (a + b), or a when that is not < b; x <= split goes left (mhs_rf_load's rule), so walking a
+ * training row reproduces the training partition.  nodepred = tot / m.  The sums are added 64 rows at a time
+ * (rf_fit.hip): bit-reproducible, independent of what else shares the launch, and equal to row-by-row sums up to the
+ * last bits of the criteria.
+ * Outputs per forest: models_out[k], an ordinary mhs_model (mhs_rf_load's path; mhs_rf_get returns its arrays);
+ * oob_pred[k] (n[k]): the mean, in tree order, of the predictions of the trees with inbag == 0 for the row, NaN where
+ * there is none; oob_count[k] (n[k]): how many there are; inc_node_purity[k] (p): the winning criteria summed per
+ * variable over all trees / n_trees (IncNodePurity).  Permutation importance (importance = TRUE's %IncMSE) is out of
+ * scope: it needs a second source of randomness.  Any of the three output arrays (not models_out) may be NULL.
+ * MHS_ERR_INVALID: NaN / infinite X or y, a negative count, a tree whose counts are all zero, mtry outside 1 .. p, p
+ * outside mhs_rf_load's range, nodesize < 1, NULL arguments.
+ * replaces randomForest::randomForest(mod.form, data = train) V73:248, V73:517                                       */
+MHS_API int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                            int n_trees, int mtry, int nodesize, const int32_t *const *inbag,
+                            const uint64_t *const *seeds, mhs_model **models_out, double *const *oob_pred,
+                            int32_t *const *oob_count, double *const *inc_node_purity);
+/* the $forest arrays of a forest FITTED by mhs_rf_fit_many (MHS_ERR_INVALID for any other handle), in mhs_rf_load's
+ * layout and the growth's own node numbering: *n_nodes first (always written), then -- each may be NULL, e.g. on a first
+ * call that only asks for the size -- leftDaughter / rightDaughter (1-based, tree-local, 0 at terminals), nodestatus
+ * (-3 split / -1 terminal), bestvar (1-based, 0 at terminals), xbestsplit, nodepred (n_nodes each) and tree_offsets
+ * (n_trees + 1, from 0)                                                                                                */
+MHS_API int mhs_rf_get(const mhs_model *m, int64_t *n_nodes, int32_t *left, int32_t *right, int32_t *status,
+                       int32_t *best_var, double *split, double *node_pred, int64_t *tree_offsets);
 MHS_API int mhs_model_free(mhs_model *m);
 
 /* the covariate layers of rast_stack, planar; LONG and LAT are generated from the grid */

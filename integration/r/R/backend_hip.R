@@ -132,6 +132,20 @@ mhs_tps_surface_se <- function(rast_stack, dat, res.FINAL, n.covars, tile.edge =
   Fs <- if (is.null(state)) NULL else lapply(state, function(s) s[[1]])
   .Call("mhsr_gbm_grow", Xs, ys, bags, as.integer(tree.complexity), as.integer(n.minobsinnode), learning.rate, Fs)
 }
+# randomForest::randomForest(mod.form, data = train) (V73:248 per CV fold, V73:517 final), regression defaults, grown on the
+# device.  The bootstrap counts and the per-tree seeds of the variable draws are drawn HERE with R's RNG, so set.seed() governs
+# them; they are not randomForest's own C-level draws, so the forest is randomForest's for these bags and draws, not for the
+# same seed (and the random tie-break of recent releases is not reproduced).  Returns the handle for the "r" slot plus the
+# $forest arrays, the OOB predictions, mse and rsq.
+.mhs_rf <- function(dat, ntree = 500L, mtry = max(floor((ncol(dat) - 1) / 3), 1), nodesize = 5L) {
+  X <- as.matrix(dat[, -1, drop = FALSE]); storage.mode(X) <- "double"
+  n <- nrow(X)
+  inbag <- replicate(ntree, tabulate(sample.int(n, n, replace = TRUE), n)); storage.mode(inbag) <- "integer"
+  f <- .Call("mhsr_rf_fit", X, as.numeric(dat[, 1]), inbag, floor(runif(ntree) * 2^53), as.integer(mtry), as.integer(nodesize))
+  names(f) <- c("handle", "tree_offsets", "leftDaughter", "rightDaughter", "nodestatus", "bestvar", "xbestsplit", "nodepred",
+                "predicted", "oob.times", "mse", "rsq", "IncNodePurity")
+  f
+}
 # inside machisplin.gbm.step's loop (V73:1843, 1919): the hold-out predictions of fold model i for every stage at once,
 # instead of one predict.gbm per gbm.more
 .mhs_gbm_holdout_stages <- function(handle, x.holdout, step.size, n.fitted)

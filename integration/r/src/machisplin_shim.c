@@ -344,6 +344,72 @@ SEXP mhsr_gbm_grow(SEXP Xs, SEXP ys, SEXP bags, SEXP depth, SEXP minobs, SEXP sh
     return out;
 }
 
+/* randomForest::randomForest(mod.form, data = train) (V73:248 per CV fold, V73:517 final) on the device: X = double matrix
+ * n x p, y = double vector, inbag = INTEGER matrix n x ntree (column t = how many times every row is in tree t's bootstrap,
+ * e.g. tabulate(sample.int(n, n, replace = TRUE), n): R's own RNG draws it), seeds = double vector, one whole number in
+ * [0, 2^53) per tree (e.g. floor(runif(ntree) * 2^53)) that drives the per-node variable draw.
+ * returns list(handle, tree_offsets, leftDaughter, rightDaughter, nodestatus, bestvar, xbestsplit, nodepred, predicted,
+ * oob.times, mse, rsq, IncNodePurity): the $forest arrays per tree concatenated (mhs_rf_load's layout), the out-of-bag
+ * predictions (NA where no tree left the row out) and mse / rsq over the rows some tree left out */
+SEXP mhsr_rf_fit(SEXP X, SEXP y, SEXP inbag, SEXP seeds, SEXP mtry, SEXP nodesize) {
+    if (!Rf_isReal(X) || !Rf_isMatrix(X) || !Rf_isReal(y) || Rf_length(y) != Rf_nrows(X))
+        Rf_error("mhsr_rf_fit: X must be a double matrix and y a double vector of nrow(X)");
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    if (TYPEOF(inbag) != INTSXP || !Rf_isMatrix(inbag) || Rf_nrows(inbag) != n || Rf_ncols(inbag) < 1)
+        Rf_error("mhsr_rf_fit: inbag must be an integer matrix nrow(X) x ntree");
+    const int nt = Rf_ncols(inbag);
+    if (!Rf_isReal(seeds) || Rf_length(seeds) != nt) Rf_error("mhsr_rf_fit: seeds must be a double vector of ntree whole numbers");
+    uint64_t *sd = (uint64_t *)R_alloc((size_t)nt, sizeof(uint64_t));
+    for (int t = 0; t < nt; ++t) {
+        const double v = REAL(seeds)[t];
+        if (!(v >= 0.0 && v < 9007199254740992.0)) Rf_error("mhsr_rf_fit: seeds must lie in [0, 2^53)");
+        sd[t] = (uint64_t)v;
+    }
+    for (R_xlen_t e = 0; e < (R_xlen_t)n * nt; ++e)
+        if (INTEGER(inbag)[e] == NA_INTEGER) Rf_error("mhsr_rf_fit: NA in inbag");
+    const double *Xp = REAL(X), *yp = REAL(y);
+    const int32_t *bp = INTEGER(inbag);
+    const uint64_t *sp = sd;
+    int64_t nn64 = n, nodes = 0;
+    mhs_model *m = NULL;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 13));
+    SEXP pred = PROTECT(Rf_allocVector(REALSXP, n)), times = PROTECT(Rf_allocVector(INTSXP, n)), pur = PROTECT(Rf_allocVector(REALSXP, p));
+    SET_VECTOR_ELT(out, 8, pred); SET_VECTOR_ELT(out, 9, times); SET_VECTOR_ELT(out, 12, pur);
+    UNPROTECT(3);
+    double *predp = REAL(pred), *purp = REAL(pur);
+    int32_t *timesp = INTEGER(times);
+    int rc = mhs_rf_fit_many(1, &Xp, &yp, &nn64, p, nt, Rf_asInteger(mtry), Rf_asInteger(nodesize), &bp, &sp, &m, &predp, &timesp, &purp);
+    if (rc == 0) {
+        SET_VECTOR_ELT(out, 0, wrap(m, model_finalizer));
+        rc = mhs_rf_get(m, &nodes, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+    }
+    if (rc == 0) {
+        SEXP off = PROTECT(Rf_allocVector(REALSXP, nt + 1)), l = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nodes));
+        SEXP r = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nodes)), st = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nodes));
+        SEXP bv = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nodes)), xs = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)nodes));
+        SEXP np = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)nodes));
+        SET_VECTOR_ELT(out, 1, off); SET_VECTOR_ELT(out, 2, l); SET_VECTOR_ELT(out, 3, r); SET_VECTOR_ELT(out, 4, st);
+        SET_VECTOR_ELT(out, 5, bv); SET_VECTOR_ELT(out, 6, xs); SET_VECTOR_ELT(out, 7, np);
+        UNPROTECT(7);
+        int64_t *to = (int64_t *)R_alloc((size_t)nt + 1, sizeof(int64_t));
+        rc = mhs_rf_get(m, &nodes, INTEGER(l), INTEGER(r), INTEGER(st), INTEGER(bv), REAL(xs), REAL(np), to);
+        for (int t = 0; t <= nt && rc == 0; ++t) REAL(off)[t] = (double)to[t];
+        double se = 0.0, sy = 0.0, ss = 0.0;
+        int seen = 0;
+        for (int i = 0; i < n; ++i)
+            if (timesp[i] > 0) { const double d = yp[i] - predp[i]; se += d * d; sy += yp[i]; ++seen; }
+        for (int i = 0; i < n; ++i)
+            if (timesp[i] > 0) { const double d = yp[i] - sy / seen; ss += d * d; }
+        for (int i = 0; i < n; ++i)
+            if (timesp[i] == 0) predp[i] = R_NaReal;
+        SET_VECTOR_ELT(out, 10, Rf_ScalarReal(seen ? se / seen : R_NaReal));
+        SET_VECTOR_ELT(out, 11, Rf_ScalarReal(seen ? 1.0 - se / ss : R_NaReal));
+    }
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* gbm::predict.gbm(model, x.data[pred.mask, ], n.trees = k * step) for k = 1 .. in one pass (V73:1843, 1919): returns the
  * n x stages matrix machisplin.gbm.step's hold-out deviance curve is computed from */
 SEXP mhsr_gbm_staged_points(SEXP model, SEXP X, SEXP step, SEXP n_trees) {

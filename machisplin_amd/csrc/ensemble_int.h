@@ -46,6 +46,13 @@ struct __attribute__((aligned(16))) Node {
 
 struct TreeChunk { int first_tree, n_trees, node_begin, node_count; };
 
+// the $forest arrays of a forest grown by mhs_rf_fit_many (rf_fit.hip), in mhs_rf_load's layout: what mhs_rf_get returns
+struct RfFitted {
+    std::vector<int64_t> tree_offsets;
+    std::vector<int32_t> left, right, status, best_var;
+    std::vector<double> split, node_pred;
+};
+
 }  // namespace mhs
 
 struct mhs_model {
@@ -123,6 +130,7 @@ struct mhs_model {
     // first use (model_on_slot); replicas are owned by the handle and freed with it.
     int slot = 0, device = -1;               // where the buffers above live
     std::function<int(mhs_model **)> reload;
+    std::shared_ptr<const mhs::RfFitted> rf_fitted;   // set by mhs_rf_fit_many only
     mhs_model *replica[mhs::MAX_SLOTS] = {};
 };
 

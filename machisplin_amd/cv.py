@@ -2,8 +2,8 @@
 k-fold cross-validation (V73:225-319) on the GPU, and the ensemble weight search that consumes them
 (V73:326-393); rank 4: the tree-count search of machisplin.gbm.step over grown fold models (gbm_step_search).
 
-Fitting the fold models of earth and randomForest stays in the CRAN packages (R); the other members have device fits
-(models.py), and :func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
+Fitting the fold models of earth stays in its CRAN package (R); the other five members have device fits
+(models.py; :func:`fit_forest_folds` grows all fold forests in one call), and :func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
 ``terra::predict(model, test)`` inside the fold loop: every fold's models evaluated at that fold's hold-out
 rows through ``mhs_predict_points``, the residual vectors concatenated in fold order, and
 ``optimx(par = 0.5, lower = 0, upper = 1, method = "L-BFGS-B")`` on
@@ -48,6 +48,21 @@ def fit_linear_folds(X, resp, kfolds):
         tr = train_rows(kfolds, v, X.shape[0])
         out.append(Gam.fit(X[tr], resp[tr]))
     return out
+
+
+def fit_forest_folds(X, resp, kfolds, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0):
+    """``mod.rf.tps.elev <- randomForest::randomForest(mod.form, data = train)`` for every fold (V73:248), ALL fold
+    forests in ONE device call (:func:`models.rf_fit_many`: a workgroup per tree, folds x n_trees trees in one launch).
+    Fold v is trained on :func:`train_rows`, so the > 4000-row rule of V73:228-232 holds.  ``inbag`` / ``seeds``: one
+    array per fold (over that fold's training rows); ``None`` draws fold v's from ``default_rng([seed, v - 1])``.
+    Returns the fold models in fold order, ready for the ``r`` slot of ``fold_models`` in :func:`cv_residuals`."""
+    from .models import rf_fit_many
+    X = np.asarray(X, dtype=np.float64)
+    resp = np.asarray(resp, dtype=np.float64)
+    nfolds = int(np.max(kfolds))
+    rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
+    gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
+    return rf_fit_many([X[r] for r in rows], [resp[r] for r in rows], n_trees, mtry, nodesize, inbag, seeds, gen)
 
 
 def cv_residuals(fold_models, X, resp, kfolds, labels: str = ORDER_ALL):

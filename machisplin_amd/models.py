@@ -1,8 +1,8 @@
 """Host-side mirror of the six fitted ensemble members as the hot path sees them:
 flat parameter arrays in, ``terra::predict(rast_stack, model)`` /
 ``predict(model, data.frame)`` out (V73:447-619).  These classes wrap what the fitted R objects contain; the
-members with a device fit (gam, ksvm, nnet, gbm) have a ``fit`` classmethod, the others are fitted in their CRAN
-packages.  All
+members with a device fit (gam, ksvm, nnet, gbm, randomForest) have a ``fit`` classmethod, earth is fitted in its CRAN
+package.  All
 arithmetic runs in libmachisplin_hip.so; there is no CPU path.
 """
 from __future__ import annotations
@@ -326,6 +326,92 @@ class RandomForest(Model):
         _lib.check(_lib.lib().mhs_rf_load(off.size - 1, off.ctypes.data, l.ctypes.data, r.ctypes.data, st.ctypes.data,
                                           bv.ctypes.data, sp.ctypes.data, npred.ctypes.data, p, C.byref(h)))
         super().__init__(h, p)
+
+    @classmethod
+    def fit(cls, X, y, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0) -> "RandomForest":
+        """randomForest::randomForest(mod.form, data = train) (V73:248 per CV fold, V73:517 the final model) with the
+        package's regression defaults (ntree = 500, mtry = max(floor(p / 3), 1), nodesize = 5, bootstrap of n rows with
+        replacement), grown on the device (mhs_rf_fit_many, a workgroup per tree).  ``inbag``: (n_trees, n) int32, how
+        many times row i is in tree t's bootstrap; ``None`` draws n rows with replacement per tree from
+        ``numpy.random.default_rng(seed)``.  ``seeds``: one uint64 per tree, driving the per-node variable draw;
+        ``None`` draws them from the same generator (after the bags).  NOT R's RNG stream: the forest is randomForest's
+        for these bags and draws, not for R's ``set.seed``; the random tie-break of recent randomForest releases and
+        permutation importance are not reproduced (include/machisplin_hip.h).  The object carries ``.params`` (the
+        ``kind = "rf"`` dict of :func:`from_param_dict`), ``.oob_pred`` / ``.oob_count`` (the out-of-bag mean of every
+        row, NaN where no tree left it out), ``.mse`` and ``.rsq`` (mean squared OOB error and
+        ``1 - mse / mean((y - mean(y))^2)`` over the rows with ``oob_count > 0``), ``.inc_node_purity`` (IncNodePurity),
+        ``.inbag`` and ``.seeds``."""
+        return rf_fit_many([X], [y], n_trees, mtry, nodesize, None if inbag is None else [inbag],
+                           None if seeds is None else [seeds], seed)[0]
+
+
+def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0):
+    """:meth:`RandomForest.fit` for several forests (each its own rows, bags and seeds; the same p, n_trees, mtry and
+    nodesize) in ONE device call: the shape of the ten fold forests of V73:248.  ``inbag`` / ``seeds``: one array per
+    model; ``seed``: an int (model k draws from ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or
+    one per model."""
+    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
+    ys = [_f64(y) for y in ys]
+    if not Xs or len(Xs) != len(ys):
+        raise ValueError("need one response vector per predictor matrix")
+    for X, y in zip(Xs, ys):
+        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
+            raise ValueError("every X must be n x p with one response per row and the same p")
+    count, p, n_trees = len(Xs), Xs[0].shape[1], int(n_trees)
+    mtry = max(p // 3, 1) if mtry is None else int(mtry)
+    if np.ndim(seed) == 0:
+        gen = [seed] if count == 1 else [[int(seed), k] for k in range(count)]
+    else:
+        gen = list(seed)
+    bags, sds = [], []
+    for k, X in enumerate(Xs):
+        n = X.shape[0]
+        rng = np.random.default_rng(gen[k]) if inbag is None or seeds is None else None
+        if inbag is None:
+            b = np.stack([np.bincount(rng.integers(0, n, size=n), minlength=n) for _ in range(n_trees)])
+        else:
+            b = np.asarray(inbag[k])
+            if b.shape != (n_trees, n):
+                raise ValueError("inbag must be n_trees x n in-bag counts")
+        if seeds is None:
+            s = rng.integers(0, 2 ** 64, size=n_trees, dtype=np.uint64)
+        else:
+            s = np.asarray(seeds[k], dtype=np.uint64)
+            if s.shape != (n_trees,):
+                raise ValueError("seeds must hold one uint64 per tree")
+        bags.append(_i32(b))
+        sds.append(np.ascontiguousarray(s))
+    hs = (C.c_void_p * count)()
+    oobp = [np.empty(X.shape[0]) for X in Xs]
+    oobc = [np.zeros(X.shape[0], dtype=np.int32) for X in Xs]
+    pur = [np.empty(p) for _ in Xs]
+    pa = lambda arrs: (C.c_void_p * count)(*[a.ctypes.data for a in arrs])
+    ns = _i64([X.shape[0] for X in Xs])
+    _lib.init()
+    _lib.check(_lib.lib().mhs_rf_fit_many(count, pa(Xs), pa(ys), ns.ctypes.data, p, n_trees, mtry, int(nodesize), pa(bags), pa(sds),
+                                          hs, pa(oobp), pa(oobc), pa(pur)))
+    out = []
+    for k in range(count):
+        m = RandomForest.__new__(RandomForest)
+        Model.__init__(m, C.c_void_p(hs[k]), p)
+        nn = C.c_int64()
+        _lib.check(_lib.lib().mhs_rf_get(m._h, C.byref(nn), None, None, None, None, None, None, None))
+        l, r, st, bv = (np.empty(nn.value, dtype=np.int32) for _ in range(4))
+        sp, npred, off = np.empty(nn.value), np.empty(nn.value), np.empty(n_trees + 1, dtype=np.int64)
+        _lib.check(_lib.lib().mhs_rf_get(m._h, C.byref(nn), l.ctypes.data, r.ctypes.data, st.ctypes.data, bv.ctypes.data,
+                                         sp.ctypes.data, npred.ctypes.data, off.ctypes.data))
+        m.params = {"kind": "rf", "tree_offsets": off, "left": l, "right": r, "status": st, "best_var": bv, "split": sp,
+                    "node_pred": npred, "p": p}
+        m.oob_pred, m.oob_count, m.inc_node_purity, m.inbag, m.seeds = oobp[k], oobc[k], pur[k], bags[k], sds[k]
+        m.n_trees, m.mtry, m.nodesize = n_trees, mtry, int(nodesize)
+        seen = oobc[k] > 0
+        d = ys[k][seen] - oobp[k][seen]
+        m.mse = float(np.mean(d * d)) if seen.any() else float("nan")
+        dy = ys[k][seen] - np.mean(ys[k][seen]) if seen.any() else np.zeros(0)
+        var = float(np.mean(dy * dy)) if seen.any() else 0.0
+        m.rsq = 1.0 - m.mse / var if var > 0.0 else float("nan")
+        out.append(m)
+    return out
 
 
 def from_param_dict(m: dict) -> Model:
