@@ -340,6 +340,65 @@ MHS_API int mhs_rf_fit_many(int count, const double *const *X, const double *con
  * (n_trees + 1, from 0)                                                                                                */
 MHS_API int mhs_rf_get(const mhs_model *m, int64_t *n_nodes, int32_t *left, int32_t *right, int32_t *status,
                        int32_t *best_var, double *split, double *node_pred, int64_t *tree_offsets);
+/* earth::earth(mod.form, data, nfold = 10) -- V73:250 (once per CV fold), V73:539 (the final model) -- as that call
+ * drives it: degree = 1, pmethod = "backward", penalty = 2, thresh = 0.001, nk = min(200, max(20, 2 p)) + 1, minspan =
+ * endspan = 0 (automatic), numeric predictors, no weights, no NA rows (V73:154); for `count` independent models in ONE
+ * launch, a resident workgroup per model (forward pass, pruning and coefficients on the device).  The models share p, nk,
+ * thresh, penalty and the span arguments; model k has its own rows X[k] (n[k] x p column-major) and responses y[k].  The
+ * earth package is not ported; THE RULE, with RSS0 = sum (y - mean y)^2:
+ *   Basis and spans.  Term 0 is the intercept.  With degree 1 the intercept is the only parent, so fast-MARS (fast.k) has
+ *     nothing to rank and is not implemented.  Automatic spans: minspan = max(1, (int)(-log2(-(1 / (p n)) ln(1 - 0.05)) /
+ *     2.5)), endspan = max(1, (int)(3 - log2(0.05 / p))); a positive argument overrides them.
+ *   Eligible knots of variable v.  Rows in ascending stable order of x_v, sorted values xs; the positions j = endspan,
+ *     endspan + minspan, ... < n - endspan (0-based); position j is eligible only if xs[j] > xs[j-1] (an ineligible position
+ *     is skipped, not shifted); the cut is xs[j].  DEPARTURE: earth centres its knot grid differently.
+ *   One forward step.  Q an orthonormal basis of the current terms, r = y - Q Q'y.  Each variable offers (a) if x_v is not
+ *     in the span (|x - QQ'x|^2 > 1e-10 |x|^2) the linear term x_v (dirs 2), reduction (q_x . r)^2; (b) for every eligible
+ *     knot t the hinge h = max(0, x_v - t) orthogonalised against Q and against q_x where q_x exists, admissible if the
+ *     remainder's squared norm is > 1e-10 |h|^2, reduction = the linear reduction (or 0) + (h_o . r')^2 / |h_o|^2.  A (b)
+ *     candidate adds the pair max(0, x - t), max(0, t - x) when x_v was not yet in the span (with the intercept the pair
+ *     spans {x, h}), the single hinge max(0, x - t) otherwise.  Candidates are ordered variables ascending, linear before
+ *     knots, knots by position; only a strictly greater reduction replaces the best.
+ *   Stopping, checked in this order, the reason recorded (MHS_EARTH_STOP_*): 1. RSS0 == 0: CONSTANT; 2. nterms + 2 > nk:
+ *     NK; 3. a best reduction that is not > 0: NONE; 4. best / RSS0 < thresh: THRESH, the term is not added; 5. the term is
+ *     added; 6. 1 - RSS / RSS0 > 1 - thresh: RSQ; 7. GRSq < -10: GRSQ.
+ *   GCV(k) = (RSS / n) / (1 - C / n)^2 with C = k + penalty (k - 1) / 2, +inf when C >= n; GRSq = 1 - GCV / GCV(intercept
+ *     only).
+ *   Pruning.  From the full forward basis, repeatedly drop the non-intercept term whose removal raises the RSS least (the
+ *     lowest term index on a tie): rss_per_subset[k] and the terms of each size, k = M .. 1.  The selected size has the
+ *     smallest GCV (the smaller size on a tie).  The arithmetic works on the triangular factor and Q'y of the forward
+ *     pass, never on the normal equations (hinge bases are ill-conditioned; earth prunes on a QR as well): dropping term
+ *     j raises the RSS by beta_j^2 / |row j of R^-1|^2, and the column leaves R by Givens rotations.
+ *   Coefficients: least squares on the selected terms, from that same factor.
+ * DEPARTURES from earth's C code besides the knot grid: no fast-MARS, no "newvar" penalty, no linpreds, no weights; the
+ * tie-breaks are the ones stated here.  The sums run in 64-row steps (earth_fit.hip states the order): a model is
+ * bit-identical from call to call and whatever else shares the launch, and equal to a sequential evaluation of the rule up to
+ * the last bits of the reductions.  Parity with R is not pinned.
+ * nk <= 0: the default, which must not exceed MHS_EARTH_MAX_NK (p <= 32; a larger p must pass an nk).  models_out[k] is an
+ * ordinary mhs_model made through mhs_earth_load's path from the selected terms; mhs_earth_get returns the record.
+ * MHS_ERR_INVALID: NaN or infinite X or y, n < 2, p outside mhs_earth_load's range, nk > MHS_EARTH_MAX_NK, thresh < 0,
+ * penalty < 0, NULL arguments.  replaces earth::earth(mod.form, data, nfold = 10) V73:250, V73:539                      */
+#define MHS_EARTH_MAX_NK 65
+#define MHS_EARTH_STOP_CONSTANT 1
+#define MHS_EARTH_STOP_NK 2
+#define MHS_EARTH_STOP_NONE 3
+#define MHS_EARTH_STOP_THRESH 4
+#define MHS_EARTH_STOP_RSQ 5
+#define MHS_EARTH_STOP_GRSQ 6
+MHS_API int mhs_earth_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                               int nk /* <= 0: default */, double thresh, double penalty, int minspan, int endspan,
+                               mhs_model **models_out);
+/* the record of a model FITTED by mhs_earth_fit_many (MHS_ERR_INVALID for any other handle).  *n_selected and *n_forward
+ * first (always written), then -- each may be NULL, e.g. on a first call that only asks for the sizes -- the stop reason;
+ * coef (n_selected), dirs and cuts (n_selected x p) of the selected terms in mhs_earth_load's layout and in forward
+ * order; the forward terms' dirs and cuts (n_forward x p) and the RSS after the step that added each term (n_forward; entry
+ * 0 is RSS0, the two terms of a pair carry the same value); selected (n_forward, 0 / 1); rss_per_subset and gcv_per_subset
+ * (n_forward each, entry k-1 for size k); prune_terms (n_forward x n_forward row-major, row k-1 = the forward indices kept
+ * at size k in forward order, then -1); stats = {rss, gcv, rsq, grsq} of the selected model                              */
+MHS_API int mhs_earth_get(const mhs_model *m, int *n_selected, int *n_forward, int *stop_reason, double *coef,
+                          int32_t *dirs, double *cuts, int32_t *forward_dirs, double *forward_cuts, double *forward_rss,
+                          int32_t *selected, double *rss_per_subset, double *gcv_per_subset, int32_t *prune_terms,
+                          double *stats);
 MHS_API int mhs_model_free(mhs_model *m);
 
 /* the covariate layers of rast_stack, planar; LONG and LAT are generated from the grid */

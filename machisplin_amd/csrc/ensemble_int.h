@@ -53,6 +53,14 @@ struct RfFitted {
     std::vector<double> split, node_pred;
 };
 
+// the record of a model fitted by mhs_earth_fit_many (earth_fit.hip): what mhs_earth_get returns
+struct EarthFitted {
+    int p = 0, n_forward = 0, n_selected = 0, stop = 0;
+    std::vector<double> coef, cuts, fwd_cuts, fwd_rss, rss_sub, gcv_sub;      // cuts n_selected x p, fwd_cuts n_forward x p
+    std::vector<int32_t> dirs, fwd_dirs, selected, prune_terms;              // prune_terms n_forward x n_forward, -1 = unused
+    double stats[4] = {0, 0, 0, 0};                                          // rss, gcv, rsq, grsq of the selected model
+};
+
 }  // namespace mhs
 
 struct mhs_model {
@@ -131,6 +139,7 @@ struct mhs_model {
     int slot = 0, device = -1;               // where the buffers above live
     std::function<int(mhs_model **)> reload;
     std::shared_ptr<const mhs::RfFitted> rf_fitted;   // set by mhs_rf_fit_many only
+    std::shared_ptr<const mhs::EarthFitted> earth_fitted;   // set by mhs_earth_fit_many only
     mhs_model *replica[mhs::MAX_SLOTS] = {};
 };
 

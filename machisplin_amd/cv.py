@@ -2,8 +2,9 @@
 k-fold cross-validation (V73:225-319) on the GPU, and the ensemble weight search that consumes them
 (V73:326-393); rank 4: the tree-count search of machisplin.gbm.step over grown fold models (gbm_step_search).
 
-Fitting the fold models of earth stays in its CRAN package (R); the other five members have device fits
-(models.py; :func:`fit_forest_folds` grows all fold forests in one call), and :func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
+All six members have device fits (models.py; :func:`fit_forest_folds` grows all fold forests and
+:func:`fit_earth_folds` fits all fold earth models, with their nfold sub-models, in one call each), and
+:func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
 ``terra::predict(model, test)`` inside the fold loop: every fold's models evaluated at that fold's hold-out
 rows through ``mhs_predict_points``, the residual vectors concatenated in fold order, and
 ``optimx(par = 0.5, lower = 0, upper = 1, method = "L-BFGS-B")`` on
@@ -63,6 +64,22 @@ def fit_forest_folds(X, resp, kfolds, n_trees=500, mtry=None, nodesize=5, inbag=
     rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
     gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
     return rf_fit_many([X[r] for r in rows], [resp[r] for r in rows], n_trees, mtry, nodesize, inbag, seeds, gen)
+
+
+def fit_earth_folds(X, resp, kfolds, nfold=10, seed=0, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspan=0):
+    """``mod.mars.tps.elev <- earth::earth(mod.form, data = train, nfold = 10)`` for every fold (V73:250), ALL fold
+    models in ONE device call (:func:`models.earth_fit_many`: a workgroup per model); with ``nfold > 0`` that call covers
+    folds x (1 + nfold) models, the sub-models behind every fold model's ``.cv_rsq``.  Fold v is trained on
+    :func:`train_rows`, so the > 4000-row rule of V73:228-232 holds.  Fold v's sub-model folds come from
+    ``default_rng([seed, v - 1])``.  Returns the fold models in fold order, ready for the ``m`` slot of ``fold_models`` in
+    :func:`cv_residuals`."""
+    from .models import earth_fit_many
+    X = np.asarray(X, dtype=np.float64)
+    resp = np.asarray(resp, dtype=np.float64)
+    nfolds = int(np.max(kfolds))
+    rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
+    gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
+    return earth_fit_many([X[r] for r in rows], [resp[r] for r in rows], nk, thresh, penalty, minspan, endspan, nfold, None, gen)
 
 
 def cv_residuals(fold_models, X, resp, kfolds, labels: str = ORDER_ALL):

@@ -1,8 +1,7 @@
 """Host-side mirror of the six fitted ensemble members as the hot path sees them:
 flat parameter arrays in, ``terra::predict(rast_stack, model)`` /
 ``predict(model, data.frame)`` out (V73:447-619).  These classes wrap what the fitted R objects contain; the
-members with a device fit (gam, ksvm, nnet, gbm, randomForest) have a ``fit`` classmethod, earth is fitted in its CRAN
-package.  All
+six members all have a ``fit`` classmethod that runs on the device (gam, ksvm, nnet, gbm, randomForest, earth).  All
 arithmetic runs in libmachisplin_hip.so; there is no CPU path.
 """
 from __future__ import annotations
@@ -126,6 +125,116 @@ class Earth(Model):
         h = C.c_void_p()
         _lib.check(_lib.lib().mhs_earth_load(c.ctypes.data, d.ctypes.data, k.ctypes.data, d.shape[0], d.shape[1], C.byref(h)))
         super().__init__(h, d.shape[1])
+
+    @classmethod
+    def fit(cls, X, y, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspan=0, nfold=0, fold=None, seed=0) -> "Earth":
+        """earth::earth(mod.form, data, nfold = 10) (V73:250 per CV fold, V73:539 the final model) as that call drives
+        it -- degree 1, backward pruning, penalty 2, thresh 0.001, nk = min(200, max(20, 2 p)) + 1, automatic spans --
+        fitted on the device (mhs_earth_fit_many, a workgroup per model; the rule is stated in
+        include/machisplin_hip.h, parity with R is not pinned).  The object carries ``.params`` (the ``kind = "earth"``
+        dict of :func:`from_param_dict`), ``.forward`` (``dirs``, ``cuts``, ``rss``, ``stop``), ``.selected``,
+        ``.rss_per_subset``, ``.gcv_per_subset``, ``.prune_terms`` (row k-1 = the forward terms kept at size k, -1
+        padded), ``.rss``, ``.gcv``, ``.rsq`` and ``.grsq``.
+
+        ``nfold > 0``: the ``nfold`` sub-models ride in the SAME launch as the main fit; sub-model f is trained on
+        ``fold != f``.  ``fold``: 1-based labels, one per row; ``None`` draws a permutation of ``rep(1 .. nfold)`` from
+        ``numpy.random.default_rng(seed)`` -- NOT R's RNG stream.  The model then carries ``.fold``, ``.cv_models``,
+        ``.cv_rsq_folds`` (per fold ``1 - sum (y - yhat)^2 / sum (y - mean of the hold-out y)^2`` on the hold-out rows,
+        through :meth:`predict_points`) and ``.cv_rsq`` (their mean).  This mirrors earth's ``cv.rsq`` in DEFINITION
+        only: the folds are not earth's."""
+        return earth_fit_many([X], [y], nk, thresh, penalty, minspan, endspan, nfold, None if fold is None else [fold], seed)[0]
+
+
+EARTH_STOPS = {1: "constant", 2: "nk", 3: "none", 4: "thresh", 5: "rsq", 6: "grsq"}      # MHS_EARTH_STOP_*
+
+
+def _earth_record(h, p):
+    """mhs_earth_get: the sizes first, then every array"""
+    lib = _lib.lib()
+    ns, nf, stop = C.c_int(), C.c_int(), C.c_int()
+    none = [None] * 11
+    _lib.check(lib.mhs_earth_get(h, C.byref(ns), C.byref(nf), C.byref(stop), *none))
+    S, M = ns.value, nf.value
+    coef, cuts, fcuts = np.empty(S), np.empty((S, p)), np.empty((M, p))
+    dirs, fdirs = np.empty((S, p), dtype=np.int32), np.empty((M, p), dtype=np.int32)
+    frss, rss_sub, gcv_sub, stats = np.empty(M), np.empty(M), np.empty(M), np.empty(4)
+    sel, pt = np.empty(M, dtype=np.int32), np.empty((M, M), dtype=np.int32)
+    _lib.check(lib.mhs_earth_get(h, C.byref(ns), C.byref(nf), C.byref(stop), coef.ctypes.data, dirs.ctypes.data, cuts.ctypes.data,
+                                 fdirs.ctypes.data, fcuts.ctypes.data, frss.ctypes.data, sel.ctypes.data, rss_sub.ctypes.data,
+                                 gcv_sub.ctypes.data, pt.ctypes.data, stats.ctypes.data))
+    return {"params": {"kind": "earth", "coef": coef, "dirs": dirs, "cuts": cuts},
+            "forward": {"dirs": fdirs, "cuts": fcuts, "rss": frss, "stop": EARTH_STOPS[stop.value]},
+            "selected": sel.astype(bool), "rss_per_subset": rss_sub, "gcv_per_subset": gcv_sub, "prune_terms": pt,
+            "rss": float(stats[0]), "gcv": float(stats[1]), "rsq": float(stats[2]), "grsq": float(stats[3])}
+
+
+def earth_fit_many(Xs, ys, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspan=0, nfold=0, fold=None, seed=0):
+    """:meth:`Earth.fit` for several models (each its own rows; the same p and arguments) in ONE device call, a workgroup
+    per model: the shape of the ten fold models of V73:250.  With ``nfold > 0`` the call covers ``len(Xs) * (1 + nfold)``
+    models.  ``fold``: one label vector per model; ``seed``: an int (model k draws its folds from
+    ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or one per model."""
+    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
+    ys = [_f64(y) for y in ys]
+    if not Xs or len(Xs) != len(ys):
+        raise ValueError("need one response vector per predictor matrix")
+    for X, y in zip(Xs, ys):
+        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
+            raise ValueError("every X must be n x p with one response per row and the same p")
+    count, p, nfold = len(Xs), Xs[0].shape[1], int(nfold)
+    folds = [None] * count
+    if nfold > 0:
+        if nfold < 2:
+            raise ValueError("nfold must be 0 or at least 2")
+        if np.ndim(seed) == 0:
+            gen = [seed] if count == 1 else [[int(seed), k] for k in range(count)]
+        else:
+            gen = list(seed)
+        for k, X in enumerate(Xs):
+            n = X.shape[0]
+            if fold is None:
+                f = np.resize(np.arange(1, nfold + 1), n)[np.random.default_rng(gen[k]).permutation(n)]
+            else:
+                f = np.asarray(fold[k])
+                if f.shape != (n,) or f.min() < 1 or f.max() > nfold:
+                    raise ValueError("fold must hold one label in 1 .. nfold per row")
+            folds[k] = f
+    # the launch list: every main model, then its nfold sub-models
+    LX, Ly, owner = [], [], []
+    for k in range(count):
+        LX.append(Xs[k]); Ly.append(ys[k]); owner.append((k, 0))
+        for f in range(1, nfold + 1):
+            tr = np.flatnonzero(folds[k] != f)
+            LX.append(np.asfortranarray(Xs[k][tr])); Ly.append(np.ascontiguousarray(ys[k][tr])); owner.append((k, f))
+    total = len(LX)
+    hs = (C.c_void_p * total)()
+    pa = lambda arrs: (C.c_void_p * total)(*[a.ctypes.data for a in arrs])
+    ns = _i64([X.shape[0] for X in LX])
+    _lib.init()
+    _lib.check(_lib.lib().mhs_earth_fit_many(total, pa(LX), pa(Ly), ns.ctypes.data, p, 0 if nk is None else int(nk), float(thresh),
+                                             float(penalty), int(minspan), int(endspan), hs))
+    fitted = []
+    for e in range(total):
+        m = Earth.__new__(Earth)
+        Model.__init__(m, C.c_void_p(hs[e]), p)
+        for key, val in _earth_record(m._h, p).items():
+            setattr(m, key, val)
+        fitted.append(m)
+    out = []
+    for k in range(count):
+        m = fitted[k * (1 + nfold)]
+        if nfold > 0:
+            m.fold, m.cv_models = folds[k], fitted[k * (1 + nfold) + 1:(k + 1) * (1 + nfold)]
+            Xc = np.ascontiguousarray(Xs[k])
+            r2 = []
+            for f, sub in enumerate(m.cv_models, start=1):
+                ho = np.flatnonzero(folds[k] == f)
+                d = ys[k][ho] - sub.predict_points(Xc[ho])
+                dy = ys[k][ho] - np.mean(ys[k][ho])
+                r2.append(1.0 - float(d @ d) / float(dy @ dy))
+            m.cv_rsq_folds = np.array(r2)
+            m.cv_rsq = float(np.mean(r2))
+        out.append(m)
+    return out
 
 
 class Ksvm(Model):
