@@ -44,11 +44,9 @@
 // it is fixed by n, p and nk alone: a model is bit-identical from call to call and whatever else shares the launch; there
 // are no floating-point atomics.  The sums differ from sequential ones in the last bits, which is why the tests follow
 // the device's own choices with a certificate (earth_ref.check_model) instead of comparing structures.
-#include <algorithm>
-#include <cmath>
-#include <numeric>
 #include <vector>
 #include "ensemble_int.h"
+#include "fit_common.h"
 
 namespace mhs {
 
@@ -74,27 +72,9 @@ struct EarthModelDev {
     int n, minspan, endspan, pad;
 };
 
-static __host__ __device__ inline size_t earth_align(size_t b) { return (b + 15) & ~(size_t)15; }
-
-__device__ __forceinline__ double earth_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ double earth_scan(double v) {            // inclusive, over the 64 lanes
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_up(v, o);
-        if (lane >= o) v = v + t;
-    }
-    return v;
-}
-
 // the block's sum of one value per thread: waves in order.  Every thread calls it and gets the same value.
 __device__ __forceinline__ double earth_block_sum(double v, double *part) {
-    v = earth_wave_sum(v);
+    v = fit_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -120,7 +100,7 @@ __device__ __forceinline__ EarthBest earth_search(const EarthModelDev &Md, int v
     const int *od = Md.ord + (size_t)v * n;
     double s2 = 0.0, sr = 0.0;
     for (int i = lane; i < n; i += 64) { const double a = xo[i]; s2 = s2 + a * a; sr = sr + a * r[i]; }
-    s2 = earth_wave_sum(s2); sr = earth_wave_sum(sr);
+    s2 = fit_wave_sum(s2); sr = fit_wave_sum(sr);
     const bool has_lin = s2 > EARTH_SPAN_TOL * xn2;
     const double inv = has_lin ? 1.0 / sqrt(s2) : 0.0;
     const double cx = sr * inv, lin = has_lin ? cx * cx : 0.0;
@@ -140,20 +120,20 @@ __device__ __forceinline__ EarthBest earth_search(const EarthModelDev &Md, int v
         if (lane == 0) xp = xlast;
         const double d = (ok && u > 0) ? xp - x : 0.0;
         const double cnt = (double)u;
-        const double H1 = H1c + earth_scan(d * cnt);
+        const double H1 = H1c + fit_wave_scan(d * cnt);
         double H1p = __shfl_up(H1, 1);
         if (lane == 0) H1p = H1c;
-        const double H2 = H2c + earth_scan(d * (2.0 * H1p + d * cnt));
+        const double H2 = H2c + fit_wave_scan(d * (2.0 * H1p + d * cnt));
         H1c = __shfl(H1, 63); H2c = __shfl(H2, 63);
         double den = H2;
         const double *qrow = Md.Q + (size_t)row * ldq;
         for (int k = 0; k < M; ++k) {
             const double q = ok ? qrow[k] : 0.0;
-            const double si = earth_scan(q);
+            const double si = fit_wave_scan(q);
             double se = __shfl_up(si, 1);
             if (lane == 0) se = 0.0;
             const double sk = __shfl(Sc, k);
-            const double G = __shfl(Gc, k) + earth_scan(d * (sk + se));
+            const double G = __shfl(Gc, k) + fit_wave_scan(d * (sk + se));
             den = den - G * G;
             const double ns = sk + __shfl(si, 63), ng = __shfl(G, 63);
             if (lane == k) { Sc = ns; Gc = ng; }
@@ -161,20 +141,20 @@ __device__ __forceinline__ EarthBest earth_search(const EarthModelDev &Md, int v
         double gx = 0.0;
         if (has_lin) {
             const double q = ok ? xo[row] * inv : 0.0;
-            const double si = earth_scan(q);
+            const double si = fit_wave_scan(q);
             double se = __shfl_up(si, 1);
             if (lane == 0) se = 0.0;
-            gx = Gx + earth_scan(d * (Sx + se));
+            gx = Gx + fit_wave_scan(d * (Sx + se));
             den = den - gx * gx;
             Sx = Sx + __shfl(si, 63); Gx = __shfl(gx, 63);
         }
         double gr;
         {
             const double q = ok ? r[row] : 0.0;
-            const double si = earth_scan(q);
+            const double si = fit_wave_scan(q);
             double se = __shfl_up(si, 1);
             if (lane == 0) se = 0.0;
-            gr = Gr + earth_scan(d * (Sr + se));
+            gr = Gr + fit_wave_scan(d * (Sr + se));
             Sr = Sr + __shfl(si, 63); Gr = __shfl(gr, 63);
         }
         bool elig = ok && j >= es && j < n - es && (j - es) % ms == 0;
@@ -251,11 +231,11 @@ __global__ __launch_bounds__(EARTH_T) void earth_fit_kernel(const EarthModelDev 
         double *xo = Md.XO + (size_t)v * n;
         double s = 0.0, s2 = 0.0;
         for (int i = lane; i < n; i += 64) { const double a = xc[i]; s = s + a; s2 = s2 + a * a; }
-        s = earth_wave_sum(s); s2 = earth_wave_sum(s2);
+        s = fit_wave_sum(s); s2 = fit_wave_sum(s2);
         const double m1 = s / (double)n;
         double t = 0.0;
         for (int i = lane; i < n; i += 64) { const double a = xc[i] - m1; xo[i] = a; t = t + a; }
-        t = earth_wave_sum(t);
+        t = fit_wave_sum(t);
         const double m2 = t / (double)n;
         for (int i = lane; i < n; i += 64) xo[i] = xo[i] - m2;
         if (lane == 0) xn2[v] = s2;
@@ -302,7 +282,7 @@ __global__ __launch_bounds__(EARTH_T) void earth_fit_kernel(const EarthModelDev 
                 for (int k = wave; k < Mc; k += EARTH_W) {
                     double s = 0.0;
                     for (int i = lane; i < n; i += 64) s = s + Md.Q[(size_t)i * ldq + k] * b[i];
-                    s = earth_wave_sum(s);
+                    s = fit_wave_sum(s);
                     if (lane == 0) {
                         ck[k] = s;
                         double *rk = Md.R + (size_t)Mc * nk + k;
@@ -339,7 +319,7 @@ __global__ __launch_bounds__(EARTH_T) void earth_fit_kernel(const EarthModelDev 
                 double *xo = Md.XO + (size_t)v * n;
                 double s = 0.0;
                 for (int i = lane; i < n; i += 64) s = s + b[i] * xo[i];
-                s = earth_wave_sum(s);
+                s = fit_wave_sum(s);
                 for (int i = lane; i < n; i += 64) xo[i] = xo[i] - b[i] * s;
             }
             __syncthreads();
@@ -471,8 +451,7 @@ int mhs_earth_fit_many(int count, const double *const *X, const double *const *y
                        double penalty, int minspan, int endspan, mhs_model **models_out) {
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(X && y && n && models_out, "NULL argument");
-    MHS_REQUIRE(count >= 1 && count <= 65535, "count out of range");
-    MHS_REQUIRE(p >= 2 && p <= EARTH_MAXP, "p (covariates + LONG + LAT) out of range");
+    if (int rc = fit_check_batch(__func__, count, p, EARTH_MAXP)) return rc;
     if (nk <= 0) nk = std::min(200, std::max(20, 2 * p)) + 1;
     MHS_REQUIRE(nk <= MHS_EARTH_MAX_NK, "nk exceeds MHS_EARTH_MAX_NK (p > 32 must pass an nk)");
     MHS_REQUIRE(thresh >= 0.0 && penalty >= 0.0, "thresh and penalty must not be negative");       // (false for NaN)
@@ -481,25 +460,24 @@ int mhs_earth_fit_many(int count, const double *const *X, const double *const *y
     struct Lay { size_t X, y, ord, Q, XO, rg, bg, R, z, od, oi; };
     std::vector<Lay> lay((size_t)count);
     std::vector<EarthModelDev> hm((size_t)count);
-    size_t pos = 0, wpos = 0, dpos = 0, ipos = 0;
+    FitCarve in, work;
+    size_t dpos = 0, ipos = 0;
     int64_t n_max = 0;
     const size_t od_len = 4 * (size_t)nk + (size_t)nk * nk + 4, oi_len = 2 * (size_t)nk + (size_t)nk * nk + 4;
     for (int k = 0; k < count; ++k) {
-        MHS_REQUIRE(X[k] && y[k], "NULL array of a model");
         MHS_REQUIRE(n[k] >= 2 && n[k] * (int64_t)std::max(p, nk) < (1LL << 31), "n out of range");
+        if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
         const int64_t nn = n[k];
         n_max = std::max(n_max, nn);
-        for (int64_t e = 0; e < nn * p; ++e) MHS_REQUIRE(std::isfinite(X[k][e]), "NaN or infinite predictor (the training rows have no NA, V73:154)");
-        for (int64_t i = 0; i < nn; ++i) MHS_REQUIRE(std::isfinite(y[k][i]), "non-finite response");
-        lay[k].X = pos; pos += earth_align(sizeof(double) * (size_t)nn * p);
-        lay[k].y = pos; pos += earth_align(sizeof(double) * (size_t)nn);
-        lay[k].ord = pos; pos += earth_align(sizeof(int) * (size_t)nn * p);
-        lay[k].Q = wpos; wpos += earth_align(sizeof(double) * (size_t)nn * nk);
-        lay[k].XO = wpos; wpos += earth_align(sizeof(double) * (size_t)nn * p);
-        lay[k].rg = wpos; wpos += earth_align(sizeof(double) * (size_t)nn);
-        lay[k].bg = wpos; wpos += earth_align(sizeof(double) * (size_t)nn);
-        lay[k].R = wpos; wpos += earth_align(sizeof(double) * (size_t)nk * nk);
-        lay[k].z = wpos; wpos += earth_align(sizeof(double) * (size_t)nk);
+        lay[k].X = in(sizeof(double) * (size_t)nn * p);
+        lay[k].y = in(sizeof(double) * (size_t)nn);
+        lay[k].ord = in(sizeof(int) * (size_t)nn * p);
+        lay[k].Q = work(sizeof(double) * (size_t)nn * nk);
+        lay[k].XO = work(sizeof(double) * (size_t)nn * p);
+        lay[k].rg = work(sizeof(double) * (size_t)nn);
+        lay[k].bg = work(sizeof(double) * (size_t)nn);
+        lay[k].R = work(sizeof(double) * (size_t)nk * nk);
+        lay[k].z = work(sizeof(double) * (size_t)nk);
         lay[k].od = dpos; dpos += od_len;
         lay[k].oi = ipos; ipos += oi_len;
         hm[k].n = (int)nn; hm[k].pad = 0;
@@ -508,25 +486,19 @@ int mhs_earth_fit_many(int count, const double *const *X, const double *const *y
         hm[k].minspan = minspan > 0 ? minspan : std::max(1, ms);
         hm[k].endspan = endspan > 0 ? endspan : std::max(1, es);
     }
-    std::vector<char> host(pos);
+    std::vector<char> host(in.at);
     for (int k = 0; k < count; ++k) {
         const int64_t nn = n[k];
         std::copy_n(X[k], (size_t)nn * p, (double *)(host.data() + lay[k].X));
         std::copy_n(y[k], (size_t)nn, (double *)(host.data() + lay[k].y));
-        int *ho = (int *)(host.data() + lay[k].ord);
-        for (int v = 0; v < p; ++v) {
-            int *o = ho + (size_t)v * nn;
-            const double *col = X[k] + (size_t)v * nn;
-            std::iota(o, o + nn, 0);
-            std::stable_sort(o, o + nn, [col](int a, int b) { return col[a] < col[b]; });
-        }
+        fit_sorted_orders(X[k], nn, p, (int *)(host.data() + lay[k].ord));
     }
     hipStream_t s = ctx().stream;
     DevBuf<char> din, dwork;
     DevBuf<double> dod;
     DevBuf<int> doi;
     DevBuf<EarthModelDev> dmod;
-    MHS_HIP(din.alloc(pos)); MHS_HIP(dwork.alloc(wpos)); MHS_HIP(dod.alloc(dpos)); MHS_HIP(doi.alloc(ipos)); MHS_HIP(dmod.alloc((size_t)count));
+    MHS_HIP(din.alloc(in.at)); MHS_HIP(dwork.alloc(work.at)); MHS_HIP(dod.alloc(dpos)); MHS_HIP(doi.alloc(ipos)); MHS_HIP(dmod.alloc((size_t)count));
     for (int k = 0; k < count; ++k) {
         EarthModelDev &m = hm[k];
         m.X = (const double *)(din.p + lay[k].X); m.y = (const double *)(din.p + lay[k].y); m.ord = (const int *)(din.p + lay[k].ord);
@@ -535,14 +507,14 @@ int mhs_earth_fit_many(int count, const double *const *X, const double *const *y
         m.R = (double *)(dwork.p + lay[k].R); m.z = (double *)(dwork.p + lay[k].z);
         m.out_d = dod.p + lay[k].od; m.out_i = doi.p + lay[k].oi;
     }
-    MHS_HIP(hipMemcpyAsync(din.p, host.data(), pos, hipMemcpyHostToDevice, s));
+    MHS_HIP(hipMemcpyAsync(din.p, host.data(), in.at, hipMemcpyHostToDevice, s));
     MHS_HIP(hipMemcpyAsync(dmod.p, hm.data(), sizeof(EarthModelDev) * (size_t)count, hipMemcpyHostToDevice, s));
     MHS_HIP(hipMemsetAsync(dod.p, 0, sizeof(double) * dpos, s));
     MHS_HIP(hipMemsetAsync(doi.p, 0, sizeof(int) * ipos, s));
     // the LDS of a block: the fixed part, then the larger of (r, the column) for the call's largest model and (R, rows of R^-1)
     const int lds_rows = (int)std::min<int64_t>(n_max, EARTH_LDS_ROWS);
     const size_t fixed = sizeof(double) * (8 + 2 * EARTH_MAXP + 3 * (MHS_EARTH_MAX_NK + 1)) + sizeof(int) * (2 * EARTH_MAXP + MHS_EARTH_MAX_NK + 3 + 8);
-    const size_t lds_bytes = earth_align(fixed) + sizeof(double) * std::max<size_t>(2 * (size_t)lds_rows, 2 * (size_t)nk * nk) + 16;
+    const size_t lds_bytes = fit_align(fixed) + sizeof(double) * std::max<size_t>(2 * (size_t)lds_rows, 2 * (size_t)nk * nk) + 16;
     MHS_HIP(hipFuncSetAttribute((const void *)earth_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(earth_fit_kernel, dim3((unsigned)count), dim3(EARTH_T), lds_bytes, s, (const EarthModelDev *)dmod.p, p, nk, thresh, penalty,
                        lds_rows);

@@ -1,0 +1,129 @@
+// What the device fits (gbm_fit.hip, rf_fit.hip, earth_fit.hip) share: the wave primitives whose lane order fixes the
+// last bits of every sum -- the fits promise models that are bit-identical from call to call and independent of what
+// shares the launch, and that promise is the order written HERE -- and the host's staging of a batch (argument checks,
+// the rows sorted per variable, the 16-byte layout of the device blocks).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include "common.h"
+
+namespace mhs {
+
+// ---------------------------------------------------------------- device: one wave of 64 lanes
+
+// The wave's sum by an xor butterfly: every lane adds the same pairs, so all lanes hold one value.  NOT devmath.h's
+// wave_sum, which adds in another order.
+template <typename T>
+__device__ __forceinline__ T fit_wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+    return v;
+}
+
+// Inclusive prefix sum over the lanes (Hillis-Steele): lane l gets v_0 + ... + v_l, added in log depth.
+template <typename T>
+__device__ __forceinline__ T fit_wave_scan(T v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o);
+        if (lane >= o) v = v + t;
+    }
+    return v;
+}
+
+// The wave's best of every lane's (val, pos): the greater value wins, equal positive values go to the lower position;
+// val = 0 means none.  In: a lane's own best (its positions are unique over the wave); out, in every lane: the wave's.
+// Returns the lane that owns the winner (0 without one), from which the caller fetches the payload with __shfl.
+__device__ __forceinline__ int fit_wave_argbest(double &val, int &pos) {
+    const double mine = val;
+    const int mpos = pos;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v2 = __shfl_xor(val, o);
+        const int p2 = __shfl_xor(pos, o);
+        if (v2 > val || (v2 == val && v2 > 0.0 && p2 < pos)) { val = v2; pos = p2; }
+    }
+    const unsigned long long own = __ballot(val > 0.0 && mine == val && mpos == pos);
+    return own ? __ffsll((long long)own) - 1 : 0;
+}
+
+// dst[0 .. cap) <- the rows of src[0 .. n) with flag[row] > 0, in src's order (ballot / popcount; the whole wave calls).
+template <typename F>
+__device__ __forceinline__ void fit_compact_order(const int *src, int n, const F *flag, int *dst, int cap) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int at = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int j = base + lane;
+        const int row = j < n ? src[j] : 0;
+        const bool f = j < n && flag[row] > 0;
+        const unsigned long long bl = __ballot(f);
+        const int to = at + __popcll(bl & lt);
+        if (f && to < cap) dst[to] = row;
+        at += __popcll(bl);
+    }
+}
+
+// Stable partition of src[0 .. m) into dst[0 .. m): the nl rows with mark[row] != 0 first, the others behind them, both
+// in src's order (the whole wave calls).
+__device__ __forceinline__ void fit_partition(const int *src, int *dst, int m, int nl, const unsigned char *mark) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int cl = 0, cr = 0;
+    for (int base = 0; base < m; base += 64) {
+        const int j = base + lane;
+        const int row = j < m ? src[j] : 0;
+        const bool f = j < m && mark[row], g = j < m && !mark[row];
+        const unsigned long long bl = __ballot(f), br = __ballot(g);
+        const int tl = cl + __popcll(bl & lt), tr = nl + cr + __popcll(br & lt);
+        if (f && tl < nl) dst[tl] = row;
+        if (g && tr < m) dst[tr] = row;
+        cl += __popcll(bl); cr += __popcll(br);
+    }
+}
+
+// ---------------------------------------------------------------- host: staging a batch of models
+
+static __host__ __device__ inline size_t fit_align(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// Offsets into one block, every piece 16-byte aligned: carve(bytes) is where the piece starts, carve.at the bytes so far.
+struct FitCarve {
+    size_t at = 0;
+    size_t operator()(size_t bytes) { const size_t o = at; at += fit_align(bytes); return o; }
+};
+
+// out (p x n) <- the rows in ascending order of every column of X (n x p column-major), ties in row order
+inline void fit_sorted_orders(const double *X, int64_t n, int p, int *out) {
+    for (int v = 0; v < p; ++v) {
+        int *o = out + (size_t)v * n;
+        const double *col = X + (size_t)v * n;
+        std::iota(o, o + n, 0);
+        std::stable_sort(o, o + n, [col](int a, int b) { return col[a] < col[b]; });
+    }
+}
+
+// The arguments every batched fit takes, checked as MHS_REQUIRE would in the entry point fn: the batch (count, p), then,
+// model by model, its X (n x p column-major) and y (n) -- present, n in range, every value finite.
+#define FIT_REQUIRE(cond, msg)                                               \
+    do {                                                                     \
+        if (!(cond)) { set_error("%s: %s", fn, msg); return MHS_ERR_INVALID; } \
+    } while (0)
+
+inline int fit_check_batch(const char *fn, int count, int p, int max_p) {
+    FIT_REQUIRE(count >= 1 && count <= 65535, "count out of range");
+    FIT_REQUIRE(p >= 2 && p <= max_p, "p (covariates + LONG + LAT) out of range");
+    return MHS_OK;
+}
+
+inline int fit_check_model(const char *fn, const double *X, const double *y, int64_t n, int p) {
+    FIT_REQUIRE(X && y, "NULL array of a model");
+    FIT_REQUIRE(n >= 1 && n * (int64_t)p < (1LL << 31), "n out of range");
+    for (int64_t e = 0; e < n * p; ++e) FIT_REQUIRE(std::isfinite(X[e]), "NaN or infinite predictor (the training rows have no NA, V73:154)");
+    for (int64_t i = 0; i < n; ++i) FIT_REQUIRE(std::isfinite(y[i]), "non-finite response");
+    return MHS_OK;
+}
+#undef FIT_REQUIRE
+
+}  // namespace mhs

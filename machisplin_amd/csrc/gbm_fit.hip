@@ -28,11 +28,8 @@
 // to call and do not depend on which other models share the launch -- but the left sums differ from gbm's sequential
 // ones in the last bits, and two candidate splits whose improvements agree to ~1e-13 relative may be ordered
 // differently.  Split VALUES are 0.5 * (x_prev + x) of the data and are bit-equal whenever the same candidate wins.
-#include <algorithm>
-#include <cmath>
-#include <numeric>
 #include <vector>
-#include "common.h"
+#include "fit_common.h"
 
 namespace mhs {
 
@@ -73,12 +70,7 @@ __device__ __forceinline__ GfBest gf_search(const int *seg, int m, const double 
         const bool ok = j < m;
         const int row = ok ? seg[j] : 0;
         const double zz = ok ? z[row] : 0.0, x = ok ? xcol[row] : 0.0;
-        double inc = zz;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double t = __shfl_up(inc, o);
-            if (lane >= o) inc = inc + t;
-        }
+        const double inc = fit_wave_scan(zz);
         double pinc = __shfl_up(inc, 1), px = __shfl_up(x, 1);
         if (lane == 0) { pinc = 0.0; px = xlast; }
         if (ok && j >= minobs && m - j >= minobs && j >= 1 && px < x) {
@@ -90,19 +82,9 @@ __device__ __forceinline__ GfBest gf_search(const int *seg, int m, const double 
         carry = carry + __shfl(inc, 63);
         xlast = __shfl(x, 63);
     }
-    double wimp = bimp;
-    int wpos = bpos;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double i2 = __shfl_xor(wimp, o);
-        const int p2 = __shfl_xor(wpos, o);
-        if (i2 > wimp || (i2 == wimp && i2 > 0.0 && p2 < wpos)) { wimp = i2; wpos = p2; }
-    }
     GfBest b;
-    b.imp = wimp; b.pos = wpos; b.var = -1;
-    // the payload comes from the lane that holds the winner (positions are unique over the lanes)
-    const unsigned long long own = __ballot(wimp > 0.0 && bimp == wimp && bpos == wpos);
-    const int src = own ? __ffsll((long long)own) - 1 : 0;
+    b.imp = bimp; b.pos = bpos; b.var = -1;
+    const int src = fit_wave_argbest(b.imp, b.pos);         // the payload comes from the lane that holds the winner
     b.ls = __shfl(bls, src);
     b.sv = __shfl(bsv, src);
     return b;
@@ -124,7 +106,6 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
     double *z = in_lds ? gf_dyn : M.zg;
     unsigned char *inbag = in_lds ? (unsigned char *)(gf_dyn + lds_rows) : M.fg;
     unsigned char *mark = inbag + n;
-    const unsigned long long lt = (1ull << lane) - 1ull;
     long long node_off = 0;
     if (tid == 0) M.toff[0] = 0;
 
@@ -135,32 +116,14 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
         for (int b = tid; b < B; b += GF_T) inbag[M.bags[(size_t)t * B + b]] = 1;
         __syncthreads();
         // ---- every variable's order, bag rows only
-        for (int v = wave; v < p; v += GF_W) {
-            const int *src = M.ord + (size_t)v * n;
-            int *dst = M.idx + (size_t)v * B;
-            int c = 0;
-            for (int base = 0; base < n; base += 64) {
-                const int j = base + lane;
-                const int row = j < n ? src[j] : 0;
-                const bool f = j < n && inbag[row];
-                const unsigned long long bl = __ballot(f);
-                if (f) dst[c + __popcll(bl & lt)] = row;
-                c += __popcll(bl);
-            }
-        }
+        for (int v = wave; v < p; v += GF_W) fit_compact_order(M.ord + (size_t)v * n, n, inbag, M.idx + (size_t)v * B, B);
         __syncthreads();
         // ---- root: sum of z over the bag in variable 0's order, 64 rows at a time
         if (wave == 0) {
             double carry = 0.0;
             for (int base = 0; base < B; base += 64) {
                 const int j = base + lane;
-                double s = j < B ? z[M.idx[j]] : 0.0;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const double u = __shfl_up(s, o);
-                    if (lane >= o) s = s + u;
-                }
-                carry = carry + __shfl(s, 63);
+                carry = carry + __shfl(fit_wave_scan(j < B ? z[M.idx[j]] : 0.0), 63);
             }
             if (lane == 0) {
                 t_node[0] = 0; t_start[0] = 0; t_cnt[0] = B; t_sum[0] = carry;
@@ -204,21 +167,8 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
             }
             __syncthreads();
             // ---- stable partition of the parent's segment in every other variable's order
-            for (int u = wave; u < p; u += GF_W) {
-                if (u == v) continue;
-                const int *src = M.idx + (size_t)u * B + s0;
-                int *dst = M.scr + (size_t)u * B + s0;
-                int cl = 0, cr = 0;
-                for (int base = 0; base < m; base += 64) {
-                    const int j = base + lane;
-                    const int row = j < m ? src[j] : 0;
-                    const bool f = j < m && mark[row], g = j < m && !mark[row];
-                    const unsigned long long bl = __ballot(f), br = __ballot(g);
-                    if (f) dst[cl + __popcll(bl & lt)] = row;
-                    if (g) dst[nL + cr + __popcll(br & lt)] = row;
-                    cl += __popcll(bl); cr += __popcll(br);
-                }
-            }
+            for (int u = wave; u < p; u += GF_W)
+                if (u != v) fit_partition(M.idx + (size_t)u * B + s0, M.scr + (size_t)u * B + s0, m, nL, mark);
             __syncthreads();
             for (int e = tid; e < p * m; e += GF_T) {
                 const int u = e / m, j = e - u * m;
@@ -277,8 +227,6 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
     }
 }
 
-static size_t gf_align(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace mhs
 
 using namespace mhs;
@@ -291,10 +239,9 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
                       int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
                       int32_t *const *left, int32_t *const *right, int32_t *const *missing) {
     if (int rc = require_ready()) return rc;
-    MHS_REQUIRE(count >= 1 && count <= 65535, "count out of range");
     MHS_REQUIRE(X && y && n && bags && bag_size && F && tree_offsets && split_var && split_val && left && right && missing,
                 "NULL argument");
-    MHS_REQUIRE(p >= 2 && p <= GF_MAXP, "p (covariates + LONG + LAT) out of range");
+    if (int rc = fit_check_batch(__func__, count, p, GF_MAXP)) return rc;
     MHS_REQUIRE(n_new >= 1 && n_new < (1 << 24), "n_new out of range");
     MHS_REQUIRE(interaction_depth >= 1 && interaction_depth <= GF_MAXDEPTH, "interaction_depth must be 1..64");
     MHS_REQUIRE(n_minobsinnode >= 1, "n_minobsinnode must be positive");
@@ -304,36 +251,36 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
     // ---- checks, and the layout of the one device block: [uploaded | F | outputs | work]
     struct Lay { size_t X, y, bags, ord, F, toff, sval, svar, left, right, miss, idx, scr, zg, fg; };
     std::vector<Lay> lay((size_t)count);
-    size_t pos = 0;
+    FitCarve carve;
     for (int k = 0; k < count; ++k) {
-        MHS_REQUIRE(X[k] && y[k] && bags[k] && F[k] && tree_offsets[k] && split_var[k] && split_val[k] && left[k] && right[k] && missing[k],
+        MHS_REQUIRE(bags[k] && F[k] && tree_offsets[k] && split_var[k] && split_val[k] && left[k] && right[k] && missing[k],
                     "NULL array of a model");
-        MHS_REQUIRE(n[k] >= 1 && n[k] * (int64_t)p < (1LL << 31), "n out of range");
+        if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
         MHS_REQUIRE(bag_size[k] >= 1 && bag_size[k] <= n[k], "bag_size must be between 1 and n");
-        lay[k].X = pos; pos += gf_align(sizeof(double) * (size_t)n[k] * p);
-        lay[k].y = pos; pos += gf_align(sizeof(double) * (size_t)n[k]);
-        lay[k].bags = pos; pos += gf_align(sizeof(int) * (size_t)n_new * (size_t)bag_size[k]);
-        lay[k].ord = pos; pos += gf_align(sizeof(int) * (size_t)n[k] * p);
+        lay[k].X = carve(sizeof(double) * (size_t)n[k] * p);
+        lay[k].y = carve(sizeof(double) * (size_t)n[k]);
+        lay[k].bags = carve(sizeof(int) * (size_t)n_new * (size_t)bag_size[k]);
+        lay[k].ord = carve(sizeof(int) * (size_t)n[k] * p);
     }
-    const size_t in_bytes = pos;
-    for (int k = 0; k < count; ++k) { lay[k].F = pos; pos += gf_align(sizeof(double) * (size_t)n[k]); }
-    const size_t up_bytes = pos;
+    const size_t in_bytes = carve.at;
+    for (int k = 0; k < count; ++k) lay[k].F = carve(sizeof(double) * (size_t)n[k]);
+    const size_t up_bytes = carve.at;
     for (int k = 0; k < count; ++k) {
-        lay[k].toff = pos; pos += gf_align(sizeof(long long) * ((size_t)n_new + 1));
-        lay[k].sval = pos; pos += gf_align(sizeof(double) * cap);
-        lay[k].svar = pos; pos += gf_align(sizeof(int) * cap);
-        lay[k].left = pos; pos += gf_align(sizeof(int) * cap);
-        lay[k].right = pos; pos += gf_align(sizeof(int) * cap);
-        lay[k].miss = pos; pos += gf_align(sizeof(int) * cap);
+        lay[k].toff = carve(sizeof(long long) * ((size_t)n_new + 1));
+        lay[k].sval = carve(sizeof(double) * cap);
+        lay[k].svar = carve(sizeof(int) * cap);
+        lay[k].left = carve(sizeof(int) * cap);
+        lay[k].right = carve(sizeof(int) * cap);
+        lay[k].miss = carve(sizeof(int) * cap);
     }
-    const size_t down_end = pos;
+    const size_t down_end = carve.at;
     for (int k = 0; k < count; ++k) {
-        lay[k].idx = pos; pos += gf_align(sizeof(int) * (size_t)bag_size[k] * p);
-        lay[k].scr = pos; pos += gf_align(sizeof(int) * (size_t)bag_size[k] * p);
-        lay[k].zg = pos; pos += gf_align(sizeof(double) * (size_t)n[k]);
-        lay[k].fg = pos; pos += gf_align(2 * (size_t)n[k]);
+        lay[k].idx = carve(sizeof(int) * (size_t)bag_size[k] * p);
+        lay[k].scr = carve(sizeof(int) * (size_t)bag_size[k] * p);
+        lay[k].zg = carve(sizeof(double) * (size_t)n[k]);
+        lay[k].fg = carve(2 * (size_t)n[k]);
     }
-    const size_t total = pos;
+    const size_t total = carve.at;
     std::vector<char> host(std::max(up_bytes, down_end - in_bytes));
     int64_t n_max = 0;
     for (int k = 0; k < count; ++k) {
@@ -341,12 +288,10 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
         n_max = std::max(n_max, nk);
         double *hX = (double *)(host.data() + lay[k].X), *hy = (double *)(host.data() + lay[k].y), *hF = (double *)(host.data() + lay[k].F);
         int *hb = (int *)(host.data() + lay[k].bags), *ho = (int *)(host.data() + lay[k].ord);
-        for (int64_t e = 0; e < nk * p; ++e) {
-            MHS_REQUIRE(std::isfinite(X[k][e]), "NaN or infinite predictor (the training rows have no NA, V73:154)");
-            hX[e] = X[k][e];
-        }
+        std::copy_n(X[k], (size_t)nk * p, hX);
+        std::copy_n(y[k], (size_t)nk, hy);
         double sum = 0.0;
-        for (int64_t i = 0; i < nk; ++i) { MHS_REQUIRE(std::isfinite(y[k][i]), "non-finite response"); hy[i] = y[k][i]; sum += y[k][i]; }
+        for (int64_t i = 0; i < nk; ++i) sum += y[k][i];
         if (first_call) {
             init_f[k] = sum / (double)nk;
             for (int64_t i = 0; i < nk; ++i) hF[i] = init_f[k];
@@ -362,12 +307,7 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
                 stamp[(size_t)r] = t;
                 hb[(size_t)t * bk + b] = r;
             }
-        for (int v = 0; v < p; ++v) {
-            int *o = ho + (size_t)v * nk;
-            const double *col = X[k] + (size_t)v * nk;
-            std::iota(o, o + nk, 0);
-            std::stable_sort(o, o + nk, [col](int a, int b) { return col[a] < col[b]; });
-        }
+        fit_sorted_orders(X[k], nk, p, ho);
     }
     hipStream_t s = ctx().stream;
     DevBuf<char> dev;
@@ -388,7 +328,7 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
     MHS_HIP(hipMemcpyAsync(dev.p, host.data(), up_bytes, hipMemcpyHostToDevice, s));
     MHS_HIP(hipMemcpyAsync(dmod.p, hm.data(), sizeof(GfModel) * (size_t)count, hipMemcpyHostToDevice, s));
     const int lds_rows = (int)std::min<int64_t>(n_max, GF_LDS_ROWS);
-    const size_t lds_bytes = gf_align((size_t)lds_rows * 10);
+    const size_t lds_bytes = fit_align((size_t)lds_rows * 10);
     MHS_HIP(hipFuncSetAttribute((const void *)gbm_grow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(gbm_grow_kernel, dim3((unsigned)count), dim3(GF_T), lds_bytes, s, (const GfModel *)dmod.p, p, n_new,
                        interaction_depth, n_minobsinnode, shrinkage, lds_rows);

@@ -16,7 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
-#include "common.h"
+#include "fit_common.h"
 
 namespace mhs {
 
@@ -337,16 +337,13 @@ __device__ __forceinline__ void nn_eval(const double *__restrict__ X, const doub
     }
     // fixed-order sums: butterfly inside a wave, then the four waves in order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) val = val + __shfl_xor(val, o);
+    val = fit_wave_sum(val);
     __syncthreads();
     if (lane == 0) part[wave] = val;
     if (GRAD) {
 #pragma unroll
         for (int q = 0; q < NW; ++q) {
-            double v = ga[q];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+            const double v = fit_wave_sum(ga[q]);
             if (lane == 0) part[4 + wave * NW + q] = v;
         }
     }

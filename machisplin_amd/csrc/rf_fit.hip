@@ -45,11 +45,9 @@
 // candidates whose criteria agree to ~1e-13 relative may be ordered differently (with nodesize 5 small nodes offer
 // such pairs all the time: two variables that cut off the same rows).  Split VALUES are 0.5 (a + b) of the data (or a)
 // and are bit-equal whenever the same candidate wins.
-#include <algorithm>
-#include <cmath>
-#include <numeric>
 #include <vector>
 #include "ensemble_int.h"
+#include "fit_common.h"
 
 namespace mhs {
 
@@ -109,18 +107,6 @@ __device__ __forceinline__ int rf_draw(unsigned long long seed, int k, int j, in
     return take;
 }
 
-__device__ __forceinline__ double rf_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);      // every lane adds the same pairs: one value in all lanes
-    return v;
-}
-
-__device__ __forceinline__ int rf_wave_count(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 struct RfBest { double crit, sv; int pos; };
 
 // Best split of one node along one variable: seg[0 .. m) are the node's in-bag rows in ascending order of xcol, tot its
@@ -139,14 +125,8 @@ __device__ __forceinline__ RfBest rf_search(const int *seg, int m, const double 
         const int row = ok ? seg[j] : 0;
         const int cc = ok ? c[row] : 0;
         const double x = ok ? xcol[row] : 0.0;
-        double inc = ok ? (double)cc * y[row] : 0.0;
-        int ic = cc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double t = __shfl_up(inc, o);
-            const int u = __shfl_up(ic, o);
-            if (lane >= o) { inc = inc + t; ic += u; }
-        }
+        const double inc = fit_wave_scan(ok ? (double)cc * y[row] : 0.0);
+        const int ic = fit_wave_scan(cc);
         double pinc = __shfl_up(inc, 1), px = __shfl_up(x, 1);
         int pic = __shfl_up(ic, 1);
         if (lane == 0) { pinc = 0.0; pic = 0; px = xlast; }
@@ -164,22 +144,11 @@ __device__ __forceinline__ RfBest rf_search(const int *seg, int m, const double 
         ccarry += __shfl(ic, 63);
         xlast = __shfl(x, 63);
     }
-    double wcrit = bcrit;
-    int wpos = bpos;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double c2 = __shfl_xor(wcrit, o);
-        const int p2 = __shfl_xor(wpos, o);
-        if (c2 > wcrit || (c2 == wcrit && c2 > 0.0 && p2 < wpos)) { wcrit = c2; wpos = p2; }
-    }
     RfBest b;
-    b.crit = wcrit; b.pos = wpos;
-    const unsigned long long own = __ballot(wcrit > 0.0 && bcrit == wcrit && bpos == wpos);   // positions are unique over the lanes
-    b.sv = __shfl(bsv, own ? __ffsll((long long)own) - 1 : 0);
+    b.crit = bcrit; b.pos = bpos;
+    b.sv = __shfl(bsv, fit_wave_argbest(b.crit, b.pos));           // the payload comes from the lane that holds the winner
     return b;
 }
-
-static __host__ __device__ inline size_t rf_align(size_t b) { return (b + 15) & ~(size_t)15; }
 
 __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restrict__ models, const RfTree *__restrict__ trees, RfWork S,
                                                        int p, int mtry, int nodesize, int lds_rows) {
@@ -191,9 +160,9 @@ __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restr
     const unsigned long long lt = (1ull << lane) - 1ull;
     // ---- LDS: [y | counts | marks | the pair results | the level's state], every piece 16-byte aligned
     char *q0 = rf_dyn;
-    double *ly = (double *)q0;                  q0 += rf_align(sizeof(double) * (size_t)lds_rows);
-    int *lc = (int *)q0;                        q0 += rf_align(sizeof(int) * (size_t)lds_rows);
-    unsigned char *lm = (unsigned char *)q0;    q0 += rf_align((size_t)lds_rows);
+    double *ly = (double *)q0;                  q0 += fit_align(sizeof(double) * (size_t)lds_rows);
+    int *lc = (int *)q0;                        q0 += fit_align(sizeof(int) * (size_t)lds_rows);
+    unsigned char *lm = (unsigned char *)q0;    q0 += fit_align((size_t)lds_rows);
     double *r_crit = (double *)q0;              q0 += sizeof(double) * RF_PAIRS;
     double *r_sv = (double *)q0;                q0 += sizeof(double) * RF_PAIRS;
     int *r_pos = (int *)q0;                     q0 += sizeof(int) * RF_PAIRS;
@@ -215,20 +184,7 @@ __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restr
     if (tid == 0) { start[0] = 0; cnt[0] = B; s_lev[0] = 0; s_lev[1] = 1; }
     __syncthreads();
     // ---- every variable's order, in-bag rows only
-    for (int v = wave; v < p; v += RF_W) {
-        const int *src = M.ord + (size_t)v * n;
-        int *dst = cur + (size_t)v * B;
-        int at = 0;
-        for (int base = 0; base < n; base += 64) {
-            const int j = base + lane;
-            const int row = j < n ? src[j] : 0;
-            const bool f = j < n && c[row] > 0;
-            const unsigned long long bl = __ballot(f);
-            const int to = at + __popcll(bl & lt);
-            if (f && to < B) dst[to] = row;
-            at += __popcll(bl);
-        }
-    }
+    for (int v = wave; v < p; v += RF_W) fit_compact_order(M.ord + (size_t)v * n, n, c, cur + (size_t)v * B, B);
     __syncthreads();
     const int per_batch = RF_PAIRS / mtry;          // nodes of a level searched between two barriers
     for (;;) {
@@ -244,8 +200,8 @@ __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restr
                 const int j = base + lane;
                 const int row = j < m ? seg[j] : 0;
                 const int cc = j < m ? c[row] : 0;
-                s = s + rf_wave_sum(j < m ? (double)cc * y[row] : 0.0);
-                w += rf_wave_count(cc);
+                s = s + fit_wave_sum(j < m ? (double)cc * y[row] : 0.0);
+                w += fit_wave_sum(cc);
             }
             if (lane == 0) {
                 pop[k] = w; tot[k] = s; pred[k] = s / (double)w;
@@ -315,20 +271,8 @@ __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restr
         for (int q = wave; q < (le - lb) * p; q += RF_W) {
             const int kk = q / p, u = q - kk * p, k = lb + kk;
             if (var[k] < 0) continue;
-            const int s0 = start[k], m = cnt[k], nl = cnt[left[k]];
-            const int *src = cur + (size_t)u * B + s0;
-            int *dst = oth + (size_t)u * B + s0;
-            int cl = 0, cr = 0;
-            for (int base = 0; base < m; base += 64) {
-                const int j = base + lane;
-                const int row = j < m ? src[j] : 0;
-                const bool f = j < m && mark[row], g = j < m && !mark[row];
-                const unsigned long long bl = __ballot(f), br = __ballot(g);
-                const int tl = cl + __popcll(bl & lt), tr = nl + cr + __popcll(br & lt);
-                if (f && tl < nl) dst[tl] = row;
-                if (g && tr < m) dst[tr] = row;
-                cl += __popcll(bl); cr += __popcll(br);
-            }
+            const size_t at = (size_t)u * B + start[k];
+            fit_partition(cur + at, oth + at, cnt[k], cnt[left[k]], mark);
         }
         __syncthreads();
         int *sw = cur; cur = oth; oth = sw;
@@ -348,7 +292,7 @@ __global__ __launch_bounds__(RF_T) void rf_grow_kernel(const RfModelDev *__restr
         double s = 0.0;
         for (int base = 0; base < nn; base += 64) {
             const int k = base + lane;
-            s = s + rf_wave_sum(k < nn && var[k] == v ? crit[k] : 0.0);
+            s = s + fit_wave_sum(k < nn && var[k] == v ? crit[k] : 0.0);
         }
         if (lane == 0) S.purity[(size_t)blockIdx.x * p + v] = s;
     }
@@ -415,8 +359,7 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
                     double *const *oob_pred, int32_t *const *oob_count, double *const *inc_node_purity) {
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(X && y && n && inbag && seeds && models_out, "NULL argument");
-    MHS_REQUIRE(count >= 1 && count <= 65535, "count out of range");
-    MHS_REQUIRE(p >= 2 && p <= RF_MAXP, "p (covariates + LONG + LAT) out of range");
+    if (int rc = fit_check_batch(__func__, count, p, RF_MAXP)) return rc;
     MHS_REQUIRE(n_trees >= 1 && n_trees < (1 << 20), "n_trees out of range");
     MHS_REQUIRE(mtry >= 1 && mtry <= p, "mtry must be 1..p");
     MHS_REQUIRE(nodesize >= 1, "nodesize must be positive");
@@ -429,21 +372,19 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
     std::vector<RfTree> ht(total_trees);
     std::vector<RfModelDev> hm((size_t)count);
     std::vector<long long> out_base((size_t)count + 1, 0), res_off((size_t)count + 1, 0);
-    size_t pos = 0;
+    FitCarve in;
     long long idx_total = 0, node_total = 0, row_total = 0;
     int64_t n_max = 0;
     for (int k = 0; k < count; ++k) {
-        MHS_REQUIRE(X[k] && y[k] && inbag[k] && seeds[k], "NULL array of a model");
-        MHS_REQUIRE(n[k] >= 1 && n[k] * (int64_t)p < (1LL << 31), "n out of range");
+        MHS_REQUIRE(inbag[k] && seeds[k], "NULL array of a model");
+        if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
         const int64_t nk = n[k];
         n_max = std::max(n_max, nk);
-        for (int64_t e = 0; e < nk * p; ++e) MHS_REQUIRE(std::isfinite(X[k][e]), "NaN or infinite predictor (the training rows have no NA, V73:154)");
-        for (int64_t i = 0; i < nk; ++i) MHS_REQUIRE(std::isfinite(y[k][i]), "non-finite response");
-        lay[k].X = pos; pos += rf_align(sizeof(double) * (size_t)nk * p);
-        lay[k].y = pos; pos += rf_align(sizeof(double) * (size_t)nk);
-        lay[k].ord = pos; pos += rf_align(sizeof(int) * (size_t)nk * p);
-        lay[k].inbag = pos; pos += rf_align(sizeof(int) * (size_t)nk * n_trees);
-        lay[k].seeds = pos; pos += rf_align(sizeof(unsigned long long) * (size_t)n_trees);
+        lay[k].X = in(sizeof(double) * (size_t)nk * p);
+        lay[k].y = in(sizeof(double) * (size_t)nk);
+        lay[k].ord = in(sizeof(int) * (size_t)nk * p);
+        lay[k].inbag = in(sizeof(int) * (size_t)nk * n_trees);
+        lay[k].seeds = in(sizeof(unsigned long long) * (size_t)n_trees);
         hm[k].n = (int)nk; hm[k].first_tree = k * n_trees; hm[k].row_base = row_total;
         long long out_nodes = 0;
         for (int t = 0; t < n_trees; ++t) {
@@ -466,7 +407,7 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         out_base[k + 1] = out_base[k] + out_nodes;
         res_off[k + 1] = res_off[k] + nk;
     }
-    const size_t in_bytes = pos;
+    const size_t in_bytes = in.at;
     std::vector<char> host(in_bytes);
     for (int k = 0; k < count; ++k) {
         const int64_t nk = n[k];
@@ -474,33 +415,26 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         std::copy_n(y[k], (size_t)nk, (double *)(host.data() + lay[k].y));
         std::copy_n(inbag[k], (size_t)nk * n_trees, (int *)(host.data() + lay[k].inbag));
         std::copy_n(seeds[k], (size_t)n_trees, (unsigned long long *)(host.data() + lay[k].seeds));
-        int *ho = (int *)(host.data() + lay[k].ord);
-        for (int v = 0; v < p; ++v) {
-            int *o = ho + (size_t)v * nk;
-            const double *col = X[k] + (size_t)v * nk;
-            std::iota(o, o + nk, 0);
-            std::stable_sort(o, o + nk, [col](int a, int b) { return col[a] < col[b]; });
-        }
+        fit_sorted_orders(X[k], nk, p, (int *)(host.data() + lay[k].ord));
     }
     // ---- device memory: [uploaded] [work: index buffers, node slabs, per-tree rows] [results]
     const size_t NT = total_trees, NN = (size_t)node_total, NR = (size_t)row_total, NO = (size_t)out_base[count], NS = (size_t)res_off[count];
-    size_t w = 0;
-    auto carve = [&w](size_t bytes) { const size_t at = w; w += rf_align(bytes); return at; };
-    const size_t w_idx = carve(sizeof(int) * (size_t)idx_total), w_scr = carve(sizeof(int) * (size_t)idx_total);
+    FitCarve work;
+    const size_t w_idx = work(sizeof(int) * (size_t)idx_total), w_scr = work(sizeof(int) * (size_t)idx_total);
     size_t w_int[6], w_dbl[4];
-    for (size_t &a : w_int) a = carve(sizeof(int) * NN);
-    for (size_t &a : w_dbl) a = carve(sizeof(double) * NN);
-    const size_t w_oob = carve(sizeof(double) * NR), w_mark = carve(NR), w_pur = carve(sizeof(double) * NT * p);
-    const size_t w_nn = carve(sizeof(int) * NT), w_flag = carve(sizeof(int) * NT);
-    const size_t work_bytes = w;
-    w = 0;
-    const size_t r_toff = carve(sizeof(long long) * (size_t)count * ((size_t)n_trees + 1)), r_flag = carve(sizeof(int) * NT);
-    const size_t r_oobp = carve(sizeof(double) * NS), r_oobc = carve(sizeof(int) * NS), r_pur = carve(sizeof(double) * (size_t)count * p);
-    const size_t small_bytes = w;
+    for (size_t &a : w_int) a = work(sizeof(int) * NN);
+    for (size_t &a : w_dbl) a = work(sizeof(double) * NN);
+    const size_t w_oob = work(sizeof(double) * NR), w_mark = work(NR), w_pur = work(sizeof(double) * NT * p);
+    const size_t w_nn = work(sizeof(int) * NT), w_flag = work(sizeof(int) * NT);
+    const size_t work_bytes = work.at;
+    FitCarve res;
+    const size_t r_toff = res(sizeof(long long) * (size_t)count * ((size_t)n_trees + 1)), r_flag = res(sizeof(int) * NT);
+    const size_t r_oobp = res(sizeof(double) * NS), r_oobc = res(sizeof(int) * NS), r_pur = res(sizeof(double) * (size_t)count * p);
+    const size_t small_bytes = res.at;
     size_t r_int[4], r_dbl[2];
-    for (size_t &a : r_int) a = carve(sizeof(int) * NO);
-    for (size_t &a : r_dbl) a = carve(sizeof(double) * NO);
-    const size_t res_bytes = w;
+    for (size_t &a : r_int) a = res(sizeof(int) * NO);
+    for (size_t &a : r_dbl) a = res(sizeof(double) * NO);
+    const size_t res_bytes = res.at;
     hipStream_t s = ctx().stream;
     DevBuf<char> din, dwork, dres;
     DevBuf<RfModelDev> dmod;
@@ -528,7 +462,7 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
     MHS_HIP(hipMemsetAsync(S.flag, 0, sizeof(int) * NT, s));
     // the LDS of a block is sized by the rows of the call's largest model (up to RF_LDS_ROWS), so small trees share a compute unit
     const int lds_rows = (int)std::min<int64_t>(n_max, RF_LDS_ROWS);
-    const size_t lds_bytes = rf_align(sizeof(double) * (size_t)lds_rows) + rf_align(sizeof(int) * (size_t)lds_rows) + rf_align((size_t)lds_rows) +
+    const size_t lds_bytes = fit_align(sizeof(double) * (size_t)lds_rows) + fit_align(sizeof(int) * (size_t)lds_rows) + fit_align((size_t)lds_rows) +
                              (2 * sizeof(double) + 2 * sizeof(int)) * RF_PAIRS + 16;
     MHS_HIP(hipFuncSetAttribute((const void *)rf_grow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(rf_grow_kernel, dim3((unsigned)NT), dim3(RF_T), lds_bytes, s, (const RfModelDev *)dmod.p, (const RfTree *)dtree.p, S, p,

@@ -52,6 +52,39 @@ class Model:
             self._h = None
 
 
+def _fit_inputs(Xs, ys):
+    """The batch of a ``*_fit_many``: every X as float64 in column-major order, every y as float64; one response vector
+    per matrix, one response per row, the same p throughout."""
+    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
+    ys = [_f64(y) for y in ys]
+    if not Xs or len(Xs) != len(ys):
+        raise ValueError("need one response vector per predictor matrix")
+    for X, y in zip(Xs, ys):
+        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
+            raise ValueError("every X must be n x p with one response per row and the same p")
+    return Xs, ys
+
+
+def _fit_generators(seed, count):
+    """What seeds ``default_rng`` of each of ``count`` models: an int gives model k ``[seed, k]`` (a single model ``seed``
+    itself); anything else is taken as one seed per model."""
+    if np.ndim(seed) == 0:
+        return [seed] if count == 1 else [[int(seed), k] for k in range(count)]
+    return list(seed)
+
+
+def _ptrs(arrs):
+    """the addresses of a list of numpy arrays, as the ``T *const *`` arguments of the batched entry points take them"""
+    return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+
+
+def _adopt(cls, handle, p):
+    """a ``cls`` around an ``mhs_model*`` that the library returned (``cls.__init__``, the loader, is not run)"""
+    m = cls.__new__(cls)
+    Model.__init__(m, C.c_void_p(handle), p)
+    return m
+
+
 class Gam(Model):
     """mgcv::gam(resp ~ a + b + ...): no smooth terms (V73:195,600) => coefficients[p+1]."""
     label = "g"
@@ -173,22 +206,13 @@ def earth_fit_many(Xs, ys, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspa
     per model: the shape of the ten fold models of V73:250.  With ``nfold > 0`` the call covers ``len(Xs) * (1 + nfold)``
     models.  ``fold``: one label vector per model; ``seed``: an int (model k draws its folds from
     ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or one per model."""
-    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
-    ys = [_f64(y) for y in ys]
-    if not Xs or len(Xs) != len(ys):
-        raise ValueError("need one response vector per predictor matrix")
-    for X, y in zip(Xs, ys):
-        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
-            raise ValueError("every X must be n x p with one response per row and the same p")
+    Xs, ys = _fit_inputs(Xs, ys)
     count, p, nfold = len(Xs), Xs[0].shape[1], int(nfold)
     folds = [None] * count
     if nfold > 0:
         if nfold < 2:
             raise ValueError("nfold must be 0 or at least 2")
-        if np.ndim(seed) == 0:
-            gen = [seed] if count == 1 else [[int(seed), k] for k in range(count)]
-        else:
-            gen = list(seed)
+        gen = _fit_generators(seed, count)
         for k, X in enumerate(Xs):
             n = X.shape[0]
             if fold is None:
@@ -207,15 +231,13 @@ def earth_fit_many(Xs, ys, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspa
             LX.append(np.asfortranarray(Xs[k][tr])); Ly.append(np.ascontiguousarray(ys[k][tr])); owner.append((k, f))
     total = len(LX)
     hs = (C.c_void_p * total)()
-    pa = lambda arrs: (C.c_void_p * total)(*[a.ctypes.data for a in arrs])
     ns = _i64([X.shape[0] for X in LX])
     _lib.init()
-    _lib.check(_lib.lib().mhs_earth_fit_many(total, pa(LX), pa(Ly), ns.ctypes.data, p, 0 if nk is None else int(nk), float(thresh),
+    _lib.check(_lib.lib().mhs_earth_fit_many(total, _ptrs(LX), _ptrs(Ly), ns.ctypes.data, p, 0 if nk is None else int(nk), float(thresh),
                                              float(penalty), int(minspan), int(endspan), hs))
     fitted = []
     for e in range(total):
-        m = Earth.__new__(Earth)
-        Model.__init__(m, C.c_void_p(hs[e]), p)
+        m = _adopt(Earth, hs[e], p)
         for key, val in _earth_record(m._h, p).items():
             setattr(m, key, val)
         fitted.append(m)
@@ -348,13 +370,12 @@ def _gbm_grow(Xs, ys, Fs, bags, n_trees, depth, minobs, shrinkage):
     off = [np.zeros(n_trees + 1, dtype=np.int64) for _ in range(count)]
     var, left, right, miss = ([np.zeros(cap, dtype=np.int32) for _ in range(count)] for _ in range(4))
     val = [np.zeros(cap) for _ in range(count)]
-    pa = lambda arrs: (C.c_void_p * count)(*[a.ctypes.data for a in arrs])
     ns = _i64([X.shape[0] for X in Xs])
     bs = _i64([b.shape[1] for b in bags])
     _lib.init()
-    _lib.check(_lib.lib().mhs_gbm_grow_many(count, pa(Xs), pa(ys), ns.ctypes.data, p, pa(bags), bs.ctypes.data, int(n_trees),
-                                            int(depth), int(minobs), float(shrinkage), int(first), pa(Fs), init.ctypes.data,
-                                            pa(off), pa(var), pa(val), pa(left), pa(right), pa(miss)))
+    _lib.check(_lib.lib().mhs_gbm_grow_many(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, _ptrs(bags), bs.ctypes.data, int(n_trees),
+                                            int(depth), int(minobs), float(shrinkage), int(first), _ptrs(Fs), init.ctypes.data,
+                                            _ptrs(off), _ptrs(var), _ptrs(val), _ptrs(left), _ptrs(right), _ptrs(miss)))
     out = []
     for k in range(count):
         nn = int(off[k][-1])
@@ -373,18 +394,8 @@ def gbm_fit_many(Xs, ys, n_trees, bags=None, seed=0, interaction_depth=25, shrin
     """:meth:`Gbm.fit` for several models (each its own rows) in ONE device call, a workgroup per model: the shape of
     machisplin.gbm.step's ten fold models (V73:1816-1919).  ``bags``: one (n_trees, bag_size) array per model; ``seed``:
     an int (model k draws from ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or one per model."""
-    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
-    ys = [_f64(y) for y in ys]
-    if not Xs or len(Xs) != len(ys):
-        raise ValueError("need one response vector per predictor matrix")
-    for X, y in zip(Xs, ys):
-        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
-            raise ValueError("every X must be n x p with one response per row and the same p")
-    if np.ndim(seed) == 0:
-        seeds = [seed] if len(Xs) == 1 else [[int(seed), k] for k in range(len(Xs))]
-    else:
-        seeds = list(seed)
-    rngs = [np.random.default_rng(s) for s in seeds] if bags is None else [None] * len(Xs)
+    Xs, ys = _fit_inputs(Xs, ys)
+    rngs = [np.random.default_rng(s) for s in _fit_generators(seed, len(Xs))] if bags is None else [None] * len(Xs)
     bags = _gbm_bags(bags, rngs, [X.shape[0] for X in Xs], int(n_trees), bag_fraction)
     res = _gbm_grow(Xs, ys, None, bags, int(n_trees), interaction_depth, n_minobsinnode, shrinkage)
     out = []
@@ -459,19 +470,10 @@ def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=No
     nodesize) in ONE device call: the shape of the ten fold forests of V73:248.  ``inbag`` / ``seeds``: one array per
     model; ``seed``: an int (model k draws from ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or
     one per model."""
-    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
-    ys = [_f64(y) for y in ys]
-    if not Xs or len(Xs) != len(ys):
-        raise ValueError("need one response vector per predictor matrix")
-    for X, y in zip(Xs, ys):
-        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
-            raise ValueError("every X must be n x p with one response per row and the same p")
+    Xs, ys = _fit_inputs(Xs, ys)
     count, p, n_trees = len(Xs), Xs[0].shape[1], int(n_trees)
     mtry = max(p // 3, 1) if mtry is None else int(mtry)
-    if np.ndim(seed) == 0:
-        gen = [seed] if count == 1 else [[int(seed), k] for k in range(count)]
-    else:
-        gen = list(seed)
+    gen = _fit_generators(seed, count)
     bags, sds = [], []
     for k, X in enumerate(Xs):
         n = X.shape[0]
@@ -494,15 +496,13 @@ def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=No
     oobp = [np.empty(X.shape[0]) for X in Xs]
     oobc = [np.zeros(X.shape[0], dtype=np.int32) for X in Xs]
     pur = [np.empty(p) for _ in Xs]
-    pa = lambda arrs: (C.c_void_p * count)(*[a.ctypes.data for a in arrs])
     ns = _i64([X.shape[0] for X in Xs])
     _lib.init()
-    _lib.check(_lib.lib().mhs_rf_fit_many(count, pa(Xs), pa(ys), ns.ctypes.data, p, n_trees, mtry, int(nodesize), pa(bags), pa(sds),
-                                          hs, pa(oobp), pa(oobc), pa(pur)))
+    _lib.check(_lib.lib().mhs_rf_fit_many(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, n_trees, mtry, int(nodesize), _ptrs(bags),
+                                          _ptrs(sds), hs, _ptrs(oobp), _ptrs(oobc), _ptrs(pur)))
     out = []
     for k in range(count):
-        m = RandomForest.__new__(RandomForest)
-        Model.__init__(m, C.c_void_p(hs[k]), p)
+        m = _adopt(RandomForest, hs[k], p)
         nn = C.c_int64()
         _lib.check(_lib.lib().mhs_rf_get(m._h, C.byref(nn), None, None, None, None, None, None, None))
         l, r, st, bv = (np.empty(nn.value, dtype=np.int32) for _ in range(4))
