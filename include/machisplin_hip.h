@@ -242,9 +242,41 @@ MHS_API int mhs_svr_fit(const double *X, const double *y, int64_t n, int p, doub
  * defaults) in one resident kernel.  wts: IN the initial weights (nnet draws runif(-0.7, 0.7): RNG-dependent, so
  * they are the caller's), OUT the fitted ones, nnet order (mhs_nnet_load).  X: n x p column-major, y as the caller
  * scaled it (V73:455-459).  value: final objective; counts[2]: function / gradient evaluations; fail: 1 = maxit
- * reached.  size must be 10.  replaces nnet::nnet V73:249, V73:463                                              */
+ * reached.  size must be 10; n p < 2^31 (the bound every batched fit puts on a model, mhs_nnet_fit_many's too).
+ * replaces nnet::nnet V73:249, V73:463                                                                           */
 MHS_API int mhs_nnet_fit(const double *X, const double *y, int64_t n, int p, int size, double *wts, int maxit,
                          double abstol, double reltol, double *value, int *counts, int *fail);
+/* mhs_svr_fit for `count` models in one call: the ten fold models of a layer (V73:251) and its final model (V73:560) are
+ * eleven fits of the same shape.  Model k has its own X[k] (n[k] x p column-major), y[k] and sigma[k]; C, epsilon, tol and
+ * max_iter are the batch's.  Every model is scaled on the host exactly as mhs_svr_fit scales it.
+ *   - Models with n[k] <= 8 192 are fitted together: their Gram matrices lie in one arena and each stage (Gram, SMO, rho)
+ *     is ONE launch with the model in the block index.  The SMO is a block per model -- no grid barrier, no cooperative
+ *     launch, blocks never wait for each other.  The block is sized to the launch's largest model (256 threads up to
+ *     2 048 stations, 1 024 above); the SMO iterate does not depend on how stations are dealt over threads, so every
+ *     result equals mhs_svr_fit's bit for bit and does not depend on what shares the launch.
+ *   - gram_budget_bytes bounds the arena: the models are packed, in batch order, into as few launches as keep the sum
+ *     of 8 n[k]^2 bytes within it; 0 = half of the free device memory; a single model above the budget goes alone.
+ *     Results do not depend on the packing.
+ *   - Models with n[k] > 8 192 go one after another through mhs_svr_fit's cooperative grid, inside the same call.
+ * Outputs per model: beta[k] (n[k]), b[k], x_center[k] / x_scale[k] (p each), y_center[k], y_scale[k], n_iter[k] and
+ * status[k] (1 = max_iter reached; n_iter / status may be NULL).  A model that hits max_iter does not stop the others:
+ * every output is filled and the call returns MHS_ERR_NUMERIC with the first such model named in mhs_last_error.
+ * replaces the loop over kernlab::ksvm V73:251 and the fit at V73:560                                            */
+MHS_API int mhs_svr_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                             const double *sigma, double C, double epsilon, double tol, int64_t max_iter,
+                             int64_t gram_budget_bytes, double *const *beta, double *b, double *const *x_center,
+                             double *const *x_scale, double *y_center, double *y_scale, int64_t *n_iter, int *status);
+/* mhs_nnet_fit for `count` models (1 .. 65 535) in ONE launch, a block per model: the ten fold models of a layer (V73:249)
+ * and its final model (V73:463).  Model k has its own X[k] (n[k] x p column-major), y[k] (as the caller scaled it) and
+ * wts[k] (IN the initial weights, OUT the fitted ones); p, size, maxit, abstol and reltol are the batch's.  Block k runs
+ * the vmmin of mhs_nnet_fit on model k with the same dealing of rows over threads and the same order of every sum, so
+ * its result is mhs_nnet_fit's bit for bit and does not depend on what shares the launch; blocks never wait for each
+ * other.  value[count], counts[2 count] (function, gradient evaluations of model k at 2k, 2k + 1), fail[count]; any of
+ * the three may be NULL.  A non-finite initial value sets fail = 2 for that model, the others are fitted and the call
+ * returns MHS_ERR_NUMERIC naming the first.  replaces the loop over nnet::nnet V73:249 and the fit at V73:463    */
+MHS_API int mhs_nnet_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p, int size,
+                              double *const *wts, int maxit, double abstol, double reltol, double *value, int *counts,
+                              int *fail);
 /* nnet::nnet(size, linout=TRUE) (V73:463): wts in nnet order -- per hidden unit its bias
  * then p input weights, then output bias and `size` hidden->output weights.  The
  * response un-scaling pred*max2.resp.f + min.resp.f (V73:469-470) is y_scale/y_shift.

@@ -110,6 +110,9 @@ SIGNATURES = {
     "mhs_svr_fit": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp]),
     "mhs_nnet_fit": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mhs_svr_fit_many": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_double, C.c_double, _i64, _i64, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp]),
+    "mhs_nnet_fit_many": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp]),
     "mhs_nnet_load": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(_vp)]),
     "mhs_earth_load": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mhs_earth_fit_many": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp]),

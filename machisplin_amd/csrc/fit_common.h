@@ -105,15 +105,16 @@ inline void fit_sorted_orders(const double *X, int64_t n, int p, int *out) {
 }
 
 // The arguments every batched fit takes, checked as MHS_REQUIRE would in the entry point fn: the batch (count, p), then,
-// model by model, its X (n x p column-major) and y (n) -- present, n in range, every value finite.
+// model by model, its X (n x p column-major) and y (n) -- present, n in range, every value finite.  FIT_REQUIRE is for
+// the host code of a fit that has the entry point's name in `fn`.
 #define FIT_REQUIRE(cond, msg)                                               \
     do {                                                                     \
         if (!(cond)) { set_error("%s: %s", fn, msg); return MHS_ERR_INVALID; } \
     } while (0)
 
-inline int fit_check_batch(const char *fn, int count, int p, int max_p) {
+inline int fit_check_batch(const char *fn, int count, int p, int max_p, int min_p = 2) {
     FIT_REQUIRE(count >= 1 && count <= 65535, "count out of range");
-    FIT_REQUIRE(p >= 2 && p <= max_p, "p (covariates + LONG + LAT) out of range");
+    FIT_REQUIRE(p >= min_p && p <= max_p, "p (covariates + LONG + LAT) out of range");
     return MHS_OK;
 }
 
@@ -124,6 +125,5 @@ inline int fit_check_model(const char *fn, const double *X, const double *y, int
     for (int64_t i = 0; i < n; ++i) FIT_REQUIRE(std::isfinite(y[i]), "non-finite response");
     return MHS_OK;
 }
-#undef FIT_REQUIRE
 
 }  // namespace mhs

@@ -13,6 +13,10 @@
 //     keeps its partial gradient in registers, a fixed-order tree adds them (the iteration path of a quasi-Newton
 //     method amplifies any run-to-run difference, so no atomics), the BFGS matrix lives in LDS (packed lower
 //     triangle) and the line search / update logic of vmmin is evaluated redundantly by every thread.
+//
+// Both are fitted eleven times per layer (ten CV folds and the final model), and a single fit leaves all but one compute
+// unit idle, so mhs_nnet_fit_many / mhs_svr_fit_many run a layer's models side by side, a block per model: the same
+// device bodies (nn_vmmin, svr_smo_body), no block ever waiting for another, every model bit-identical to its single fit.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -25,14 +29,37 @@ constexpr int SMO_T = 1024;     // threads per block
 constexpr int SMO_E = 8;        // stations per thread
 constexpr int SMO_MAXB = 64;    // blocks (n <= 524 288; the n^2 Gram matrix gives out long before)
 
-__global__ __launch_bounds__(256) void rbf_gram_kernel(const double *__restrict__ Z, int n, int p, double sigma,
-                                                       double *__restrict__ K) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+// entry e of a model's Gram matrix (row-major n x n) from its scaled rows Z (n x p row-major)
+__device__ __forceinline__ void rbf_gram_entry(const double *__restrict__ Z, int n, int p, double sigma, double *__restrict__ K,
+                                               int64_t e) {
     if (e >= (int64_t)n * n) return;
     const int i = (int)(e / n), j = (int)(e - (int64_t)i * n);
     double d2 = 0.0;
     for (int k = 0; k < p; ++k) { const double d = Z[(int64_t)i * p + k] - Z[(int64_t)j * p + k]; d2 = fma(d, d, d2); }
     K[e] = exp(-sigma * d2);
+}
+
+__global__ __launch_bounds__(256) void rbf_gram_kernel(const double *__restrict__ Z, int n, int p, double sigma,
+                                                       double *__restrict__ K) {
+    rbf_gram_entry(Z, n, p, sigma, K, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// One model of a batched launch (mhs_svr_fit_many): where its pieces lie in the launch's arenas.
+struct SvrJob {
+    const double *Z, *t;           // scaled rows (n x p row-major), scaled response
+    double *K;                     // n x n, in the Gram arena
+    double *al, *as, *kb, *beta;   // n each
+    double sigma;
+    long long max_iter;
+    int n, pad;
+};
+
+// blockIdx.y = the model, blockIdx.x strides over its n^2 entries (the grid's x extent is capped, the models differ in n)
+__global__ __launch_bounds__(256) void rbf_gram_many_kernel(const SvrJob *__restrict__ jobs, int p) {
+    const SvrJob j = jobs[blockIdx.y];
+    const int64_t nn = (int64_t)j.n * j.n;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nn; e += (int64_t)gridDim.x * 256)
+        rbf_gram_entry(j.Z, j.n, p, j.sigma, j.K, e);
 }
 
 __device__ __forceinline__ void st_u64(unsigned long long *p, unsigned long long v) {
@@ -62,6 +89,7 @@ __device__ __forceinline__ void grid_barrier(unsigned long long *counter, unsign
 
 // arg-max of (key, idx) over the block, ties to the LARGER idx (libsvm's select_working_set scans t = 0 .. 2n-1 with
 // '>=' / '<=': the last of equal candidates wins; SMO_NONE = -1 loses every tie); every thread returns the winner
+template <int T>
 __device__ __forceinline__ void block_argmax(double &key, int &idx, double *skey, int *sidx) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -75,7 +103,7 @@ __device__ __forceinline__ void block_argmax(double &key, int &idx, double *skey
     __syncthreads();
     key = skey[0]; idx = sidx[0];
 #pragma unroll
-    for (int w = 1; w < SMO_T / 64; ++w) {
+    for (int w = 1; w < T / 64; ++w) {
         const double k2 = skey[w];
         const int i2 = sidx[w];
         if (k2 > key || (k2 == key && i2 > idx)) { key = k2; idx = i2; }
@@ -87,16 +115,19 @@ constexpr int SLOT_W = 8;
 constexpr int SMO_NONE = -1;      // "no candidate": below every variable index, so it never wins a tie
 struct SmoOut { double rho; long long iters; double violation; int status; };
 
-__global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict__ K, const double *__restrict__ y, int n,
-                                                        double C, double eps, double tol, long long max_iter,
-                                                        unsigned long long *slots, unsigned long long *counter,
-                                                        double *__restrict__ al_out, double *__restrict__ as_out,
-                                                        double *__restrict__ kb_out, SmoOut *out) {
-    __shared__ double skey[SMO_T / 64], spay[4];
-    __shared__ int sidx[SMO_T / 64];
-    const unsigned nb = gridDim.x;
-    const int stride = (int)nb * SMO_T;
-    const int g0 = (int)blockIdx.x * SMO_T + (int)threadIdx.x;
+// The SMO on one model: T threads per block, SMO_E stations per thread, block bid of nb (nb > 1: the cooperative grid of
+// mhs_svr_fit's large models; the batched kernel runs every model as block 0 of 1).  The iterate does not depend on T
+// or on how the stations are dealt: the arg-reductions are exact with ties to the larger index and kb is updated
+// station by station, so T = 256 and T = 1024 give the same bits.
+template <int T>
+__device__ __forceinline__ void svr_smo_body(const double *__restrict__ K, const double *__restrict__ y, const int n, const double C,
+                                             const double eps, const double tol, const long long max_iter, unsigned long long *slots,
+                                             unsigned long long *counter, double *__restrict__ al_out, double *__restrict__ as_out,
+                                             double *__restrict__ kb_out, SmoOut *out, const unsigned nb, const unsigned bid) {
+    __shared__ double skey[T / 64], spay[4];
+    __shared__ int sidx[T / 64];
+    const int stride = (int)nb * T;
+    const int g0 = (int)bid * T + (int)threadIdx.x;
     const double TAU = 1e-12, NEG = -INFINITY;
     double kb[SMO_E], al[SMO_E], as[SMO_E], yk[SMO_E];
 #pragma unroll
@@ -109,7 +140,8 @@ __global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict
     long long it = 0;
     double viol = INFINITY;
     int status = 0;
-    unsigned long long *slotI = slots, *slotJ = slots + 2 * SMO_MAXB * SLOT_W;
+    // the exchange slots exist only for a cooperative grid: the batched kernel passes none and forms no address from them
+    unsigned long long *slotI = slots, *slotJ = nb > 1 ? slots + 2 * SMO_MAXB * SLOT_W : nullptr;
     for (;; ++it) {
         const int par = (int)(it & 1);
         // ---- i = argmax over I_up of -s G ; gmax2 = max over I_low of s G
@@ -126,13 +158,13 @@ __global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict
                 if (as[r] < C) low = fmax(low, -gd);
             }
         }
-        block_argmax(best, bi, skey, sidx);
+        block_argmax<T>(best, bi, skey, sidx);
         {
             int dummy = 0;
-            block_argmax(low, dummy, skey, sidx);
+            block_argmax<T>(low, dummy, skey, sidx);
         }
         if (nb > 1) {
-            unsigned long long *s = slotI + ((size_t)par * SMO_MAXB + blockIdx.x) * SLOT_W;
+            unsigned long long *s = slotI + ((size_t)par * SMO_MAXB + bid) * SLOT_W;
             if (threadIdx.x == 0) { st_f64(s + 0, best); st_u64(s + 2, (unsigned long long)(unsigned)bi); st_f64(s + 3, low); }
         }
         // the owner of the block's candidate publishes its alpha (one block: through LDS)
@@ -142,7 +174,7 @@ __global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict
             for (int r = 0; r < SMO_E; ++r)
                 if (g0 + r * stride == st && bi != SMO_NONE) {
                     const double ai_local = bi < n ? al[r] : as[r];
-                    if (nb > 1) st_f64(slotI + ((size_t)par * SMO_MAXB + blockIdx.x) * SLOT_W + 1, ai_local);
+                    if (nb > 1) st_f64(slotI + ((size_t)par * SMO_MAXB + bid) * SLOT_W + 1, ai_local);
                     else spay[0] = ai_local;
                 }
         }
@@ -190,9 +222,9 @@ __global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict
         }
         {
             const int mine = jx;
-            block_argmax(jb, jx, skey, sidx);
+            block_argmax<T>(jb, jx, skey, sidx);
             // the thread that holds the winner publishes its payload
-            unsigned long long *s = slotJ + ((size_t)par * SMO_MAXB + blockIdx.x) * SLOT_W;
+            unsigned long long *s = nb > 1 ? slotJ + ((size_t)par * SMO_MAXB + bid) * SLOT_W : nullptr;
             if (mine == jx && jx != SMO_NONE) {
                 if (nb > 1) { st_f64(s + 0, jb); st_f64(s + 1, ja); st_f64(s + 2, jg); st_f64(s + 3, jk); st_u64(s + 4, (unsigned long long)(unsigned)jx); }
                 else { spay[1] = ja; spay[2] = jg; spay[3] = jk; }
@@ -254,13 +286,28 @@ __global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict
         const int k = g0 + r * stride;
         if (k < n) { al_out[k] = al[r]; as_out[k] = as[r]; kb_out[k] = kb[r]; }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out->iters = it; out->violation = viol; out->status = status; }
+    if (bid == 0 && threadIdx.x == 0) { out->iters = it; out->violation = viol; out->status = status; }
+}
+
+__global__ __launch_bounds__(SMO_T) void svr_smo_kernel(const double *__restrict__ K, const double *__restrict__ y, int n,
+                                                        double C, double eps, double tol, long long max_iter,
+                                                        unsigned long long *slots, unsigned long long *counter,
+                                                        double *__restrict__ al_out, double *__restrict__ as_out,
+                                                        double *__restrict__ kb_out, SmoOut *out) {
+    svr_smo_body<SMO_T>(K, y, n, C, eps, tol, max_iter, slots, counter, al_out, as_out, kb_out, out, gridDim.x, blockIdx.x);
+}
+
+// A block per model, no grid barrier, no cooperative launch: blocks never wait for each other.
+template <int T>
+__global__ __launch_bounds__(T) void svr_smo_many_kernel(const SvrJob *__restrict__ jobs, double C, double eps, double tol, SmoOut *out) {
+    const SvrJob j = jobs[blockIdx.x];
+    svr_smo_body<T>(j.K, j.t, j.n, C, eps, tol, j.max_iter, nullptr, nullptr, j.al, j.as, j.kb, out + blockIdx.x, 1u, 0u);
 }
 
 // libsvm Solver::calculate_rho on the 2n variables, one block, fixed order
-__global__ __launch_bounds__(256) void svr_rho_kernel(const double *__restrict__ alpha, const double *__restrict__ alpha_s,
-                                                      const double *__restrict__ kb, const double *__restrict__ y, int n,
-                                                      double C, double eps, double *__restrict__ beta, SmoOut *out) {
+__device__ __forceinline__ void svr_rho_body(const double *__restrict__ alpha, const double *__restrict__ alpha_s,
+                                             const double *__restrict__ kb, const double *__restrict__ y, int n, double C, double eps,
+                                             double *__restrict__ beta, SmoOut *out) {
     __shared__ double ssum[256], sub[256], slb[256];
     __shared__ int scnt[256];
     double sum = 0.0, ub = INFINITY, lb = -INFINITY;
@@ -281,6 +328,17 @@ __global__ __launch_bounds__(256) void svr_rho_kernel(const double *__restrict__
         for (int t = 1; t < 256; ++t) { sum += ssum[t]; cnt += scnt[t]; ub = fmin(ub, sub[t]); lb = fmax(lb, slb[t]); }
         out->rho = cnt > 0 ? sum / (double)cnt : 0.5 * (ub + lb);
     }
+}
+
+__global__ __launch_bounds__(256) void svr_rho_kernel(const double *__restrict__ alpha, const double *__restrict__ alpha_s,
+                                                      const double *__restrict__ kb, const double *__restrict__ y, int n,
+                                                      double C, double eps, double *__restrict__ beta, SmoOut *out) {
+    svr_rho_body(alpha, alpha_s, kb, y, n, C, eps, beta, out);
+}
+
+__global__ __launch_bounds__(256) void svr_rho_many_kernel(const SvrJob *__restrict__ jobs, double C, double eps, SmoOut *out) {
+    const SvrJob j = jobs[blockIdx.x];
+    svr_rho_body(j.al, j.as, j.kb, j.t, j.n, C, eps, j.beta, out + blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------ nnet (vmmin) --
@@ -356,10 +414,16 @@ __device__ __forceinline__ void nn_eval(const double *__restrict__ X, const doub
     __syncthreads();
 }
 
-// R's vmmin (src/appl/optim.c), one block; B = packed lower triangle in LDS
+// One model of a launch (mhs_nnet_fit_many; mhs_nnet_fit is a launch of one): its rows (n x p row-major), its response and
+// its weights (IN the initial ones, OUT the fitted), all in the launch's device block.
+struct NnJob { const double *X, *y; double *wts; int n, pad; };
+
+// R's vmmin (src/appl/optim.c) on one model by one block; B = packed lower triangle in LDS.  Every return is taken by the
+// whole block (f, maxit and the counters are the same in every thread), and nothing here reads blockIdx or another
+// block's memory: a model's iterates do not depend on what shares the launch.
 template <int P>
-__global__ __launch_bounds__(NN_T) void nnet_bfgs_kernel(const double *__restrict__ X, const double *__restrict__ y, int n,
-                                                         double *__restrict__ wts, int maxit, double abstol, double reltol, NnOut *out) {
+__device__ __forceinline__ void nn_vmmin(const double *__restrict__ X, const double *__restrict__ y, const int n,
+                                         double *__restrict__ wts, const int maxit, const double abstol, const double reltol, NnOut *out) {
     constexpr int NW = (P + 1) * NN_H + NN_H + 1;
     static_assert(NW <= NN_T, "one thread per weight");
     extern __shared__ double sm[];
@@ -455,13 +519,227 @@ __global__ __launch_bounds__(NN_T) void nnet_bfgs_kernel(const double *__restric
     if (q == 0) { out->value = fmin; out->fncount = funcount; out->grcount = gradcount; out->fail = fail; }
 }
 
+// a block per model; blocks never wait for each other, so any grid runs to its end whatever is resident
 template <int P>
-static int launch_nnet_fit(const double *X, const double *y, int n, double *w, int maxit, double abstol, double reltol, NnOut *out, hipStream_t s) {
+__global__ __launch_bounds__(NN_T) void nnet_bfgs_kernel(const NnJob *__restrict__ jobs, int maxit, double abstol, double reltol, NnOut *out) {
+    const NnJob j = jobs[blockIdx.x];
+    nn_vmmin<P>(j.X, j.y, j.n, j.wts, maxit, abstol, reltol, out + blockIdx.x);
+}
+
+template <int P>
+static int launch_nnet_fit(const NnJob *jobs, int count, int maxit, double abstol, double reltol, NnOut *out, hipStream_t s) {
     constexpr int NW = (P + 1) * NN_H + NN_H + 1;
     const size_t bytes = sizeof(double) * (size_t)(6 * NW + 4 + 4 * NW + 2 + NW * (NW + 1) / 2);
     MHS_HIP(hipFuncSetAttribute((const void *)nnet_bfgs_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((nnet_bfgs_kernel<P>), dim3(1), dim3(NN_T), bytes, s, X, y, n, w, maxit, abstol, reltol, out);
+    hipLaunchKernelGGL((nnet_bfgs_kernel<P>), dim3((unsigned)count), dim3(NN_T), bytes, s, jobs, maxit, abstol, reltol, out);
     MHS_HIP(hipGetLastError());
+    return MHS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------ host side --
+// scaled = TRUE: columns and response to zero mean, unit standard deviation (n - 1).  Z: n x p row-major, t: n.
+static int svr_scale(const char *fn, const double *X, const double *y, int64_t n, int p, double *Z, double *t, double *x_center,
+                     double *x_scale, double *y_center, double *y_scale) {
+    for (int j = 0; j < p; ++j) {
+        const double *col = X + (size_t)j * n;
+        double m = 0.0;
+        for (int64_t k = 0; k < n; ++k) { FIT_REQUIRE(std::isfinite(col[k]), "non-finite predictor"); m += col[k]; }
+        m /= (double)n;
+        double ss = 0.0;
+        for (int64_t k = 0; k < n; ++k) ss += (col[k] - m) * (col[k] - m);
+        const double sd = sqrt(ss / (double)(n - 1));
+        FIT_REQUIRE(sd > 0, "a predictor is constant");
+        x_center[j] = m; x_scale[j] = sd;
+        for (int64_t k = 0; k < n; ++k) Z[(size_t)k * p + j] = (col[k] - m) / sd;
+    }
+    double m = 0.0;
+    for (int64_t k = 0; k < n; ++k) { FIT_REQUIRE(std::isfinite(y[k]), "non-finite response"); m += y[k]; }
+    m /= (double)n;
+    double ss = 0.0;
+    for (int64_t k = 0; k < n; ++k) ss += (y[k] - m) * (y[k] - m);
+    const double sd = sqrt(ss / (double)(n - 1));
+    FIT_REQUIRE(sd > 0, "the response is constant");
+    *y_center = m; *y_scale = sd;
+    for (int64_t k = 0; k < n; ++k) t[(size_t)k] = (y[k] - m) / sd;
+    return MHS_OK;
+}
+
+static long long svr_iter_limit(int64_t max_iter, int64_t n) {       // libsvm's max(10^7, 100 n)
+    return max_iter > 0 ? (long long)max_iter : std::max<long long>(10000000LL, 100LL * n);
+}
+
+// One model on scaled data, any n: Gram, SMO (a cooperative grid when n needs more than one block), rho.
+static int svr_fit_one(const double *Z, const double *t, int64_t n, int p, double sigma, double C, double epsilon, double tol,
+                       int64_t max_iter, double *beta, SmoOut *h) {
+    hipStream_t s = ctx().stream;
+    DevBuf<double> dZ, dt, dK, dbeta, dkb, dal, das;
+    DevBuf<unsigned long long> dslots;
+    DevBuf<unsigned long long> dcount;
+    DevBuf<SmoOut> dout;
+    MHS_HIP(dZ.alloc((size_t)n * p)); MHS_HIP(dt.alloc((size_t)n)); MHS_HIP(dK.alloc((size_t)n * n));
+    MHS_HIP(dbeta.alloc((size_t)n)); MHS_HIP(dkb.alloc((size_t)n)); MHS_HIP(dal.alloc((size_t)n)); MHS_HIP(das.alloc((size_t)n));
+    MHS_HIP(dslots.alloc((size_t)4 * SMO_MAXB * SLOT_W)); MHS_HIP(dcount.alloc(1)); MHS_HIP(dout.alloc(1));
+    MHS_HIP(hipMemcpyAsync(dZ.p, Z, sizeof(double) * (size_t)n * p, hipMemcpyHostToDevice, s));
+    MHS_HIP(hipMemcpyAsync(dt.p, t, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    MHS_HIP(hipMemsetAsync(dslots.p, 0, sizeof(unsigned long long) * 4 * SMO_MAXB * SLOT_W, s));
+    MHS_HIP(hipMemsetAsync(dcount.p, 0, sizeof(unsigned long long), s));
+    MHS_HIP(hipMemsetAsync(dout.p, 0, sizeof(SmoOut), s));
+    hipLaunchKernelGGL(rbf_gram_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, s, dZ.p, (int)n, p, sigma, dK.p);
+    MHS_HIP(hipGetLastError());
+    const unsigned nb = (unsigned)((n + (int64_t)SMO_T * SMO_E - 1) / ((int64_t)SMO_T * SMO_E));
+    {
+        const double *Kp = dK.p, *yp = dt.p;
+        int nn = (int)n;
+        long long mi = svr_iter_limit(max_iter, n);
+        unsigned long long *sl = dslots.p;
+        unsigned long long *cn = dcount.p;
+        double *ao = dal.p, *so = das.p, *ko = dkb.p;
+        SmoOut *oo = dout.p;
+        void *args[] = {&Kp, &yp, &nn, &C, &epsilon, &tol, &mi, &sl, &cn, &ao, &so, &ko, &oo};
+        if (nb > 1) MHS_HIP(hipLaunchCooperativeKernel((const void *)svr_smo_kernel, dim3(nb), dim3(SMO_T), args, 0, s));
+        else MHS_HIP(hipLaunchKernel((const void *)svr_smo_kernel, dim3(1), dim3(SMO_T), args, 0, s));
+    }
+    hipLaunchKernelGGL(svr_rho_kernel, dim3(1), dim3(256), 0, s, dal.p, das.p, dkb.p, dt.p, (int)n, C, epsilon, dbeta.p, dout.p);
+    MHS_HIP(hipGetLastError());
+    MHS_HIP(hipMemcpyAsync(beta, dbeta.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+    MHS_HIP(hipMemcpyAsync(h, dout.p, sizeof(SmoOut), hipMemcpyDeviceToHost, s));
+    MHS_HIP(hipStreamSynchronize(s));
+    return MHS_OK;
+}
+
+// The models pack[0 .. m) (indices into the batch, every n <= SMO_T * SMO_E) in three launches: their Gram matrices into one
+// arena, a block per model for the SMO, a block per model for rho.  The rows are scaled straight into the staging block.
+static int svr_fit_pack(const char *fn, const int *pack, int m, const double *const *X, const double *const *y, const int64_t *n, int p,
+                        const double *sigma, double C, double epsilon, double tol, int64_t max_iter, double *const *beta,
+                        double *const *x_center, double *const *x_scale, double *y_center, double *y_scale, SmoOut *h) {
+    hipStream_t s = ctx().stream;
+    FitCarve carve;
+    std::vector<size_t> oZ(m), ot(m), oal(m), oas(m), okb(m);
+    size_t rows = 0, gram = 0;
+    int64_t nmax = 0;
+    for (int e = 0; e < m; ++e) {
+        const size_t nk = (size_t)n[pack[e]];
+        oZ[e] = carve(sizeof(double) * nk * p); ot[e] = carve(sizeof(double) * nk);
+        rows += nk; gram += nk * nk; nmax = std::max<int64_t>(nmax, (int64_t)nk);
+    }
+    const size_t ojobs = carve(sizeof(SvrJob) * (size_t)m);
+    const size_t upload = carve.at;                                     // what the host fills: Z, t, the job records
+    for (int e = 0; e < m; ++e) {
+        const size_t nk = (size_t)n[pack[e]];
+        oal[e] = carve(sizeof(double) * nk); oas[e] = carve(sizeof(double) * nk); okb[e] = carve(sizeof(double) * nk);
+    }
+    const size_t obeta = carve(sizeof(double) * rows);                  // the betas back to back, then the records: one copy home
+    const size_t oout = carve(sizeof(SmoOut) * (size_t)m);
+    std::vector<char> host(upload, 0);
+    for (int e = 0; e < m; ++e) {
+        const int k = pack[e];
+        if (int rc = svr_scale(fn, X[k], y[k], n[k], p, reinterpret_cast<double *>(host.data() + oZ[e]),
+                               reinterpret_cast<double *>(host.data() + ot[e]), x_center[k], x_scale[k], y_center + k, y_scale + k)) return rc;
+    }
+    DevBuf<char> blk;
+    DevBuf<double> dK;
+    MHS_HIP(blk.alloc(carve.at)); MHS_HIP(dK.alloc(gram));
+    SvrJob *jobs = reinterpret_cast<SvrJob *>(host.data() + ojobs);
+    size_t kat = 0, bat = 0;
+    for (int e = 0; e < m; ++e) {
+        const int k = pack[e];
+        const size_t nk = (size_t)n[k];
+        SvrJob &j = jobs[e];
+        j.Z = reinterpret_cast<const double *>(blk.p + oZ[e]); j.t = reinterpret_cast<const double *>(blk.p + ot[e]);
+        j.K = dK.p + kat;
+        j.al = reinterpret_cast<double *>(blk.p + oal[e]); j.as = reinterpret_cast<double *>(blk.p + oas[e]);
+        j.kb = reinterpret_cast<double *>(blk.p + okb[e]); j.beta = reinterpret_cast<double *>(blk.p + obeta) + bat;
+        j.sigma = sigma[k]; j.max_iter = svr_iter_limit(max_iter, (int64_t)nk); j.n = (int)nk; j.pad = 0;
+        kat += nk * nk; bat += nk;
+    }
+    MHS_HIP(hipMemcpyAsync(blk.p, host.data(), upload, hipMemcpyHostToDevice, s));
+    MHS_HIP(hipMemsetAsync(blk.p + oout, 0, sizeof(SmoOut) * (size_t)m, s));
+    const SvrJob *dj = reinterpret_cast<const SvrJob *>(blk.p + ojobs);
+    SmoOut *dout = reinterpret_cast<SmoOut *>(blk.p + oout);
+    const unsigned gx = (unsigned)std::min<int64_t>((nmax * nmax + 255) / 256, 2048);
+    hipLaunchKernelGGL(rbf_gram_many_kernel, dim3(gx, (unsigned)m), dim3(256), 0, s, dj, p);
+    MHS_HIP(hipGetLastError());
+    // the block sized to the launch's largest model: four waves hold 2 048 stations and make the two arg-reductions of
+    // every iteration a quarter as wide as sixteen do
+    if (nmax <= 256 * SMO_E) hipLaunchKernelGGL((svr_smo_many_kernel<256>), dim3((unsigned)m), dim3(256), 0, s, dj, C, epsilon, tol, dout);
+    else hipLaunchKernelGGL((svr_smo_many_kernel<SMO_T>), dim3((unsigned)m), dim3(SMO_T), 0, s, dj, C, epsilon, tol, dout);
+    MHS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(svr_rho_many_kernel, dim3((unsigned)m), dim3(256), 0, s, dj, C, epsilon, dout);
+    MHS_HIP(hipGetLastError());
+    std::vector<char> back(carve.at - obeta);
+    MHS_HIP(hipMemcpyAsync(back.data(), blk.p + obeta, back.size(), hipMemcpyDeviceToHost, s));
+    MHS_HIP(hipStreamSynchronize(s));
+    const double *hb = reinterpret_cast<const double *>(back.data());
+    const SmoOut *ho = reinterpret_cast<const SmoOut *>(back.data() + (oout - obeta));
+    bat = 0;
+    for (int e = 0; e < m; ++e) {
+        const size_t nk = (size_t)n[pack[e]];
+        std::copy(hb + bat, hb + bat + nk, beta[pack[e]]);
+        h[pack[e]] = ho[e];
+        bat += nk;
+    }
+    return MHS_OK;
+}
+
+// count models in ONE launch, a block each (mhs_nnet_fit: count = 1)
+static int nnet_fit_batch(const char *fn, int count, const double *const *X, const double *const *y, const int64_t *n, int p, int size,
+                          double *const *wts, int maxit, double abstol, double reltol, double *value, int *counts, int *fail) {
+    if (int rc = require_ready()) return rc;
+    if (int rc = fit_check_batch(fn, count, p, 12, 1)) return rc;
+    FIT_REQUIRE(X && y && n && wts, "NULL argument");
+    FIT_REQUIRE(size == NN_H, "this build fits nnet(size = 10) only (V73:249, V73:463)");
+    const int NW = (p + 1) * NN_H + NN_H + 1;
+    FitCarve carve;
+    std::vector<size_t> oX(count), oy(count);
+    for (int k = 0; k < count; ++k) {
+        FIT_REQUIRE(wts[k], "NULL weights of a model");
+        if (int rc = fit_check_model(fn, X[k], y[k], n[k], p)) return rc;
+        oX[k] = carve(sizeof(double) * (size_t)n[k] * p); oy[k] = carve(sizeof(double) * (size_t)n[k]);
+    }
+    const size_t ojobs = carve(sizeof(NnJob) * (size_t)count);
+    const size_t ow = carve(sizeof(double) * (size_t)NW * count);      // the weights back to back, then the records: one copy home
+    const size_t upload = carve.at;
+    const size_t oout = carve(sizeof(NnOut) * (size_t)count);
+    DevBuf<char> blk;
+    MHS_HIP(blk.alloc(carve.at));
+    std::vector<char> host(upload, 0);
+    NnJob *jobs = reinterpret_cast<NnJob *>(host.data() + ojobs);
+    for (int k = 0; k < count; ++k) {
+        // rows in the kernel's order (row-major) from R's column-major matrix
+        double *Xr = reinterpret_cast<double *>(host.data() + oX[k]);
+        for (int j = 0; j < p; ++j)
+            for (int64_t r = 0; r < n[k]; ++r) Xr[(size_t)r * p + j] = X[k][(size_t)j * n[k] + r];
+        std::copy(y[k], y[k] + n[k], reinterpret_cast<double *>(host.data() + oy[k]));
+        std::copy(wts[k], wts[k] + NW, reinterpret_cast<double *>(host.data() + ow) + (size_t)k * NW);
+        jobs[k].X = reinterpret_cast<const double *>(blk.p + oX[k]); jobs[k].y = reinterpret_cast<const double *>(blk.p + oy[k]);
+        jobs[k].wts = reinterpret_cast<double *>(blk.p + ow) + (size_t)k * NW; jobs[k].n = (int)n[k]; jobs[k].pad = 0;
+    }
+    hipStream_t s = ctx().stream;
+    MHS_HIP(hipMemcpyAsync(blk.p, host.data(), upload, hipMemcpyHostToDevice, s));
+    MHS_HIP(hipMemsetAsync(blk.p + oout, 0, sizeof(NnOut) * (size_t)count, s));
+    const NnJob *dj = reinterpret_cast<const NnJob *>(blk.p + ojobs);
+    NnOut *dout = reinterpret_cast<NnOut *>(blk.p + oout);
+    int rc = MHS_OK;
+    switch (p) {
+#define MHS_NNF(P_) case P_: rc = launch_nnet_fit<P_>(dj, count, maxit, abstol, reltol, dout, s); break;
+        MHS_NNF(1) MHS_NNF(2) MHS_NNF(3) MHS_NNF(4) MHS_NNF(5) MHS_NNF(6) MHS_NNF(7) MHS_NNF(8) MHS_NNF(9) MHS_NNF(10) MHS_NNF(11) MHS_NNF(12)
+#undef MHS_NNF
+    }
+    if (rc) return rc;
+    std::vector<char> back(carve.at - ow);
+    MHS_HIP(hipMemcpyAsync(back.data(), blk.p + ow, back.size(), hipMemcpyDeviceToHost, s));
+    MHS_HIP(hipStreamSynchronize(s));
+    const double *hw = reinterpret_cast<const double *>(back.data());
+    const NnOut *ho = reinterpret_cast<const NnOut *>(back.data() + (oout - ow));
+    int bad = -1;
+    for (int k = 0; k < count; ++k) {
+        std::copy(hw + (size_t)k * NW, hw + (size_t)(k + 1) * NW, wts[k]);
+        if (value) value[k] = ho[k].value;
+        if (counts) { counts[2 * k] = ho[k].fncount; counts[2 * k + 1] = ho[k].grcount; }
+        if (fail) fail[k] = ho[k].fail;
+        if (ho[k].fail == 2 && bad < 0) bad = k;
+    }
+    if (bad >= 0) { set_error("%s: model %d: the initial value is not finite", fn, bad); return MHS_ERR_NUMERIC; }
     return MHS_OK;
 }
 
@@ -478,68 +756,68 @@ int mhs_svr_fit(const double *X, const double *y, int64_t n, int p, double sigma
     MHS_REQUIRE(X && y && beta && b && x_center && x_scale && y_center && y_scale, "NULL argument");
     MHS_REQUIRE(n >= 2 && n <= (int64_t)SMO_T * SMO_E * SMO_MAXB && p >= 1 && p <= 64, "n or p out of range");
     MHS_REQUIRE(sigma > 0 && C > 0 && epsilon >= 0 && tol > 0, "sigma, C and tol must be positive, epsilon non-negative");
-    // scaled = TRUE: columns and response to zero mean, unit standard deviation (n - 1)
     std::vector<double> Z((size_t)n * p), t((size_t)n);
-    for (int j = 0; j < p; ++j) {
-        const double *col = X + (size_t)j * n;
-        double m = 0.0;
-        for (int64_t k = 0; k < n; ++k) { MHS_REQUIRE(std::isfinite(col[k]), "non-finite predictor"); m += col[k]; }
-        m /= (double)n;
-        double ss = 0.0;
-        for (int64_t k = 0; k < n; ++k) ss += (col[k] - m) * (col[k] - m);
-        const double sd = sqrt(ss / (double)(n - 1));
-        MHS_REQUIRE(sd > 0, "a predictor is constant");
-        x_center[j] = m; x_scale[j] = sd;
-        for (int64_t k = 0; k < n; ++k) Z[(size_t)k * p + j] = (col[k] - m) / sd;
-    }
-    {
-        double m = 0.0;
-        for (int64_t k = 0; k < n; ++k) { MHS_REQUIRE(std::isfinite(y[k]), "non-finite response"); m += y[k]; }
-        m /= (double)n;
-        double ss = 0.0;
-        for (int64_t k = 0; k < n; ++k) ss += (y[k] - m) * (y[k] - m);
-        const double sd = sqrt(ss / (double)(n - 1));
-        MHS_REQUIRE(sd > 0, "the response is constant");
-        *y_center = m; *y_scale = sd;
-        for (int64_t k = 0; k < n; ++k) t[(size_t)k] = (y[k] - m) / sd;
-    }
-    hipStream_t s = ctx().stream;
-    DevBuf<double> dZ, dt, dK, dbeta, dkb, dal, das;
-    DevBuf<unsigned long long> dslots;
-    DevBuf<unsigned long long> dcount;
-    DevBuf<SmoOut> dout;
-    MHS_HIP(dZ.alloc((size_t)n * p)); MHS_HIP(dt.alloc((size_t)n)); MHS_HIP(dK.alloc((size_t)n * n));
-    MHS_HIP(dbeta.alloc((size_t)n)); MHS_HIP(dkb.alloc((size_t)n)); MHS_HIP(dal.alloc((size_t)n)); MHS_HIP(das.alloc((size_t)n));
-    MHS_HIP(dslots.alloc((size_t)4 * SMO_MAXB * SLOT_W)); MHS_HIP(dcount.alloc(1)); MHS_HIP(dout.alloc(1));
-    MHS_HIP(hipMemcpyAsync(dZ.p, Z.data(), sizeof(double) * Z.size(), hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dt.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemsetAsync(dslots.p, 0, sizeof(unsigned long long) * 4 * SMO_MAXB * SLOT_W, s));
-    MHS_HIP(hipMemsetAsync(dcount.p, 0, sizeof(unsigned long long), s));
-    MHS_HIP(hipMemsetAsync(dout.p, 0, sizeof(SmoOut), s));
-    hipLaunchKernelGGL(rbf_gram_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, s, dZ.p, (int)n, p, sigma, dK.p);
-    MHS_HIP(hipGetLastError());
-    const unsigned nb = (unsigned)((n + (int64_t)SMO_T * SMO_E - 1) / ((int64_t)SMO_T * SMO_E));
-    {
-        const double *Kp = dK.p, *yp = dt.p;
-        int nn = (int)n;
-        long long mi = max_iter > 0 ? (long long)max_iter : std::max<long long>(10000000LL, 100LL * n);
-        unsigned long long *sl = dslots.p;
-        unsigned long long *cn = dcount.p;
-        double *ao = dal.p, *so = das.p, *ko = dkb.p;
-        SmoOut *oo = dout.p;
-        void *args[] = {&Kp, &yp, &nn, &C, &epsilon, &tol, &mi, &sl, &cn, &ao, &so, &ko, &oo};
-        if (nb > 1) MHS_HIP(hipLaunchCooperativeKernel((const void *)svr_smo_kernel, dim3(nb), dim3(SMO_T), args, 0, s));
-        else MHS_HIP(hipLaunchKernel((const void *)svr_smo_kernel, dim3(1), dim3(SMO_T), args, 0, s));
-    }
-    hipLaunchKernelGGL(svr_rho_kernel, dim3(1), dim3(256), 0, s, dal.p, das.p, dkb.p, dt.p, (int)n, C, epsilon, dbeta.p, dout.p);
-    MHS_HIP(hipGetLastError());
+    if (int rc = svr_scale(__func__, X, y, n, p, Z.data(), t.data(), x_center, x_scale, y_center, y_scale)) return rc;
     SmoOut h;
-    MHS_HIP(hipMemcpyAsync(beta, dbeta.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipMemcpyAsync(&h, dout.p, sizeof(SmoOut), hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipStreamSynchronize(s));
+    if (int rc = svr_fit_one(Z.data(), t.data(), n, p, sigma, C, epsilon, tol, max_iter, beta, &h)) return rc;
     *b = h.rho;
     if (n_iter) *n_iter = h.iters;
     if (h.status != 0) { set_error("mhs_svr_fit: no convergence within %lld iterations (violation %.3g)", h.iters, h.violation); return MHS_ERR_NUMERIC; }
+    return MHS_OK;
+}
+
+int mhs_svr_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p, const double *sigma,
+                     double C, double epsilon, double tol, int64_t max_iter, int64_t gram_budget_bytes, double *const *beta,
+                     double *b, double *const *x_center, double *const *x_scale, double *y_center, double *y_scale,
+                     int64_t *n_iter, int *status) {
+    const char *fn = __func__;
+    if (int rc = require_ready()) return rc;
+    if (int rc = fit_check_batch(fn, count, p, 64, 1)) return rc;
+    FIT_REQUIRE(X && y && n && sigma && beta && b && x_center && x_scale && y_center && y_scale, "NULL argument");
+    FIT_REQUIRE(C > 0 && epsilon >= 0 && tol > 0 && gram_budget_bytes >= 0, "C and tol must be positive, epsilon and the Gram budget non-negative");
+    for (int k = 0; k < count; ++k) {
+        FIT_REQUIRE(X[k] && y[k] && beta[k] && x_center[k] && x_scale[k], "NULL array of a model");
+        FIT_REQUIRE(n[k] >= 2 && n[k] <= (int64_t)SMO_T * SMO_E * SMO_MAXB, "n out of range");
+        FIT_REQUIRE(sigma[k] > 0, "sigma must be positive");
+    }
+    size_t budget = (size_t)gram_budget_bytes;
+    if (budget == 0) {
+        size_t free_b = 0, total_b = 0;
+        MHS_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget = free_b / 2;
+    }
+    std::vector<SmoOut> h((size_t)count);
+    // the models one block holds, in batch order, into as few launches as keep the Gram arena within the budget
+    std::vector<int> pack;
+    size_t bytes = 0;
+    for (int k = 0; k <= count; ++k) {
+        const bool small = k < count && n[k] <= (int64_t)SMO_T * SMO_E;
+        const size_t need = small ? sizeof(double) * (size_t)n[k] * (size_t)n[k] : 0;
+        if (!pack.empty() && (k == count || (small && bytes + need > budget))) {
+            if (int rc = svr_fit_pack(fn, pack.data(), (int)pack.size(), X, y, n, p, sigma, C, epsilon, tol, max_iter, beta, x_center, x_scale,
+                                      y_center, y_scale, h.data())) return rc;
+            pack.clear(); bytes = 0;
+        }
+        if (small) { pack.push_back(k); bytes += need; }
+    }
+    // the others one after another through the cooperative grid
+    for (int k = 0; k < count; ++k)
+        if (n[k] > (int64_t)SMO_T * SMO_E) {
+            std::vector<double> Z((size_t)n[k] * p), t((size_t)n[k]);
+            if (int rc = svr_scale(fn, X[k], y[k], n[k], p, Z.data(), t.data(), x_center[k], x_scale[k], y_center + k, y_scale + k)) return rc;
+            if (int rc = svr_fit_one(Z.data(), t.data(), n[k], p, sigma[k], C, epsilon, tol, max_iter, beta[k], &h[(size_t)k])) return rc;
+        }
+    int bad = -1;
+    for (int k = 0; k < count; ++k) {
+        b[k] = h[(size_t)k].rho;
+        if (n_iter) n_iter[k] = h[(size_t)k].iters;
+        if (status) status[k] = h[(size_t)k].status;
+        if (h[(size_t)k].status != 0 && bad < 0) bad = k;
+    }
+    if (bad >= 0) {
+        set_error("%s: model %d: no convergence within %lld iterations (violation %.3g)", fn, bad, h[(size_t)bad].iters, h[(size_t)bad].violation);
+        return MHS_ERR_NUMERIC;
+    }
     return MHS_OK;
 }
 
@@ -549,39 +827,21 @@ int mhs_nnet_fit(const double *X, const double *y, int64_t n, int p, int size, d
     MHS_REQUIRE(X && y && wts && n >= 1 && n < (1LL << 31), "bad arguments");
     MHS_REQUIRE(size == NN_H, "this build fits nnet(size = 10) only (V73:249, V73:463)");
     MHS_REQUIRE(p >= 1 && p <= 12, "p must be between 1 and 12");
-    const int NW = (p + 1) * NN_H + NN_H + 1;
-    // rows in the kernel's order (row-major) from R's column-major matrix
-    std::vector<double> Xr((size_t)n * p);
-    for (int j = 0; j < p; ++j)
-        for (int64_t k = 0; k < n; ++k) {
-            const double v = X[(size_t)j * n + k];
-            MHS_REQUIRE(std::isfinite(v), "non-finite predictor");
-            Xr[(size_t)k * p + j] = v;
-        }
-    for (int64_t k = 0; k < n; ++k) MHS_REQUIRE(std::isfinite(y[k]), "non-finite response");
-    hipStream_t s = ctx().stream;
-    DevBuf<double> dX, dy, dw;
-    DevBuf<NnOut> dout;
-    MHS_HIP(dX.alloc(Xr.size())); MHS_HIP(dy.alloc((size_t)n)); MHS_HIP(dw.alloc((size_t)NW)); MHS_HIP(dout.alloc(1));
-    MHS_HIP(hipMemcpyAsync(dX.p, Xr.data(), sizeof(double) * Xr.size(), hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dw.p, wts, sizeof(double) * (size_t)NW, hipMemcpyHostToDevice, s));
-    int rc = MHS_OK;
-    switch (p) {
-#define MHS_NNF(P_) case P_: rc = launch_nnet_fit<P_>(dX.p, dy.p, (int)n, dw.p, maxit, abstol, reltol, dout.p, s); break;
-        MHS_NNF(1) MHS_NNF(2) MHS_NNF(3) MHS_NNF(4) MHS_NNF(5) MHS_NNF(6) MHS_NNF(7) MHS_NNF(8) MHS_NNF(9) MHS_NNF(10) MHS_NNF(11) MHS_NNF(12)
-#undef MHS_NNF
-    }
+    // the launch of one; as before, a non-finite initial value leaves value / counts / fail untouched
+    double v = 0.0;
+    int c[2] = {0, 0}, f = 0;
+    const int rc = nnet_fit_batch(__func__, 1, &X, &y, &n, p, size, &wts, maxit, abstol, reltol, &v, c, &f);
+    if (rc == MHS_ERR_NUMERIC && f == 2) { set_error("mhs_nnet_fit: the initial value is not finite"); return rc; }
     if (rc) return rc;
-    NnOut h;
-    MHS_HIP(hipMemcpyAsync(wts, dw.p, sizeof(double) * (size_t)NW, hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipMemcpyAsync(&h, dout.p, sizeof(NnOut), hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipStreamSynchronize(s));
-    if (h.fail == 2) { set_error("mhs_nnet_fit: the initial value is not finite"); return MHS_ERR_NUMERIC; }
-    if (value) *value = h.value;
-    if (counts) { counts[0] = h.fncount; counts[1] = h.grcount; }
-    if (fail) *fail = h.fail;
+    if (value) *value = v;
+    if (counts) { counts[0] = c[0]; counts[1] = c[1]; }
+    if (fail) *fail = f;
     return MHS_OK;
+}
+
+int mhs_nnet_fit_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p, int size, double *const *wts,
+                      int maxit, double abstol, double reltol, double *value, int *counts, int *fail) {
+    return nnet_fit_batch(__func__, count, X, y, n, p, size, wts, maxit, abstol, reltol, value, counts, fail);
 }
 
 }  // extern "C"

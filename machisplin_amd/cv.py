@@ -2,9 +2,10 @@
 k-fold cross-validation (V73:225-319) on the GPU, and the ensemble weight search that consumes them
 (V73:326-393); rank 4: the tree-count search of machisplin.gbm.step over grown fold models (gbm_step_search).
 
-All six members have device fits (models.py; :func:`fit_forest_folds` grows all fold forests and
-:func:`fit_earth_folds` fits all fold earth models, with their nfold sub-models, in one call each), and
-:func:`gbm_step` runs machisplin.gbm.step whole.  What else runs here is what R does with
+All six members have device fits (models.py; :func:`fit_forest_folds`, :func:`fit_earth_folds`, :func:`fit_nnet_folds`
+and :func:`fit_ksvm_folds` fit all fold models of their member in one device call each), :func:`gbm_step` runs
+machisplin.gbm.step whole, :func:`kfold` draws the fold labels and :func:`fit_layer` performs Step 1 and the final
+fits of one layer (V73:220-620): its result is a ``fitted[i]`` of :func:`mltps.mltps`.  What else runs here is what R does with
 ``terra::predict(model, test)`` inside the fold loop: every fold's models evaluated at that fold's hold-out
 rows through ``mhs_predict_points``, the residual vectors concatenated in fold order, and
 ``optimx(par = 0.5, lower = 0, upper = 1, method = "L-BFGS-B")`` on
@@ -80,6 +81,157 @@ def fit_earth_folds(X, resp, kfolds, nfold=10, seed=0, nk=None, thresh=0.001, pe
     rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
     gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
     return earth_fit_many([X[r] for r in rows], [resp[r] for r in rows], nk, thresh, penalty, minspan, endspan, nfold, None, gen)
+
+
+def _fold_batch(X, resp, kfolds, seed):
+    """the training rows of every fold (:func:`train_rows`) and what seeds fold v's generator: ``[seed, v - 1]``"""
+    X = np.asarray(X, dtype=np.float64)
+    resp = np.asarray(resp, dtype=np.float64)
+    nfolds = int(np.max(kfolds))
+    rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
+    gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
+    return [X[r] for r in rows], [resp[r] for r in rows], gen
+
+
+def fit_nnet_folds(X, resp, kfolds, wts0=None, seed=0, maxit=10000):
+    """``mod.nn.tps.elev <- nnet::nnet(mod.form, data = trainNN, size = 10, linout = TRUE, maxit = 10000)`` for every fold
+    (V73:249) with the fold's own response scaling (V73:235-241), ALL fold models in ONE launch
+    (:func:`models.nnet_fit_many`: a workgroup per model).  Fold v is trained on :func:`train_rows`, so the > 4000-row
+    rule of V73:228-232 holds.  ``wts0``: one vector of initial weights per fold; ``None`` draws fold v's from
+    ``default_rng([seed, v - 1]).uniform(-0.7, 0.7)``.  Returns the fold models in fold order, ready for the ``n`` slot
+    of ``fold_models`` in :func:`cv_residuals`."""
+    from .models import nnet_fit_many
+    Xs, ys, gen = _fold_batch(X, resp, kfolds, seed)
+    return nnet_fit_many(Xs, ys, wts0, gen, maxit=maxit)
+
+
+def fit_ksvm_folds(X, resp, kfolds, sigma=None, seed=0):
+    """``mod.svm.tps.elev <- kernlab::ksvm(mod.form, data = train)`` for every fold (V73:251), ALL fold models in ONE
+    device call (:func:`models.ksvm_fit_many`: the SMO a workgroup per model).  Fold v is trained on :func:`train_rows`,
+    so the > 4000-row rule of V73:228-232 holds.  ``sigma``: a scalar, one value per fold, or ``None`` -- kernlab's
+    automatic width, fold v's from ``sigest(train, seed = [seed, v - 1])``.  Returns the fold models in fold order, ready
+    for the ``v`` slot of ``fold_models`` in :func:`cv_residuals`."""
+    from .models import ksvm_fit_many
+    Xs, ys, gen = _fold_batch(X, resp, kfolds, seed)
+    return ksvm_fit_many(Xs, ys, sigma, gen)
+
+
+def kfold(n, k=10, seed=0):
+    """``machisplin.kfold(x, k)`` (V73:1553-1573): 1-based fold labels for n rows.  The group sizes are the differences
+    of ``round(c(0, n / k * 1:(k - 1), n))`` (R rounds half to even, as numpy does); the labels ``rep(j, times[j])`` are
+    then put in a random order -- here a permutation from ``default_rng(seed)``, NOT R's ``order(runif(n))``."""
+    n, k = int(n), int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    if k == 1:
+        return np.ones(n, dtype=np.int64)
+    if n / k < 1:
+        raise ValueError("insufficient records: %d, with k = %d" % (n, k))
+    edges = np.round(np.concatenate([[0.0], n / k * np.arange(1, k), [float(n)]])).astype(np.int64)
+    group = np.repeat(np.arange(1, k + 1), np.diff(edges))
+    return group[np.random.default_rng(seed).permutation(n)]
+
+
+_MEMBER = {lab: i for i, lab in enumerate(ORDER_ALL)}
+
+
+def _member_seeds(seed, lab, count):
+    """``[seed, member, j]`` for j = 0 .. count - 1; member = the label's place in "bgnmrv" """
+    return [[int(seed), _MEMBER[lab], j] for j in range(count)]
+
+
+def _member_int_seed(seed, lab, j):
+    """an int from the stream ``[seed, member, j]`` for :func:`gbm_step`, which takes an int and derives its own streams"""
+    return int(np.random.SeedSequence([int(seed), _MEMBER[lab], j]).generate_state(1)[0])
+
+
+def fit_layer(X, resp, kfolds=None, seed=0, smooth_only=False, nfolds=10, gbm_fold=None, gbm_final=None, rf=None, earth=None,
+              nnet=None, ksvm=None):
+    """Step 1 and the final fits of ONE response layer (V73:220-620), every fit on the device:
+
+    1. the fold labels: ``kfolds`` as given (1-based, one per row) or :func:`kfold` ``(n, nfolds, seed)`` (V73:220);
+    2. the fold models of every member in play -- ``bgnmrv``, or ``gnmv`` with ``smooth_only`` (no tree is fitted then):
+       ``b`` by :func:`gbm_step` fold by fold (``tree_complexity = 25, learning_rate = 0.01, bag_fraction = 0.5``,
+       V73:247; ``gbm_fold`` overrides; an abort of machisplin.gbm.step raises ``RuntimeError`` naming the fold, as R
+       stops there), the other five through :func:`fit_linear_folds`, :func:`fit_nnet_folds`, :func:`fit_earth_folds`,
+       :func:`fit_forest_folds` and :func:`fit_ksvm_folds`, one device call per member; the dicts ``rf``, ``earth``,
+       ``nnet`` and ``ksvm`` are forwarded to them as keywords;
+    3. :func:`cv_residuals`, :func:`optx_weights`: the kept labels, their rounded weights, the unrounded total (V73:322-392);
+    4. the final fits on ALL rows of the kept members only, in ``mods.run`` order (V73:447-619): ``b`` by
+       :func:`gbm_step` with ``tree_complexity = 5, learning_rate = 0.001`` (V73:493; ``gbm_final`` overrides), ``n`` with
+       the all-rows response scaling of V73:454-459, ``n`` and ``v`` through :func:`models.nnet_fit_many` /
+       :func:`models.ksvm_fit_many`; the scalar arguments of the member's dict apply (a per-fold ``wts0``, ``inbag``,
+       ``seeds`` or ``sigma`` sequence does not).
+
+    Every draw comes from a ``default_rng`` stream derived from ``seed``, the member and the fold, none from R's: member
+    ``bgnmrv`` is number 0 .. 5; fold v (1-based) of a member draws from ``default_rng([seed, member, v - 1])``, its final
+    fit from ``default_rng([seed, member, nfolds])``; :func:`gbm_step` takes an int seed, which is the first word of
+    ``SeedSequence([seed, 0, j])``; the fold labels come from ``default_rng(seed)``.  A ``seed`` in a member's dict
+    replaces that member's derivation for the folds.  The same arguments give bit-identical results.
+
+    Returns a dict: ``kfolds``, ``fold_models`` (per fold, label -> model), ``residuals`` (hold-out rows x members in
+    play), ``p`` (the optimiser's end point), ``labels`` (the kept ones), and ``models`` / ``weights`` / ``wt_total`` --
+    exactly a ``fitted[i]`` of :func:`mltps.mltps`."""
+    from . import models as _models
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    resp = np.asarray(resp, dtype=np.float64)
+    n = X.shape[0]
+    if X.ndim != 2 or resp.shape != (n,):
+        raise ValueError("X must be n x p with one response per row")
+    if kfolds is None:
+        kfolds = kfold(n, nfolds, seed)
+    else:
+        kfolds = np.asarray(kfolds)
+        if kfolds.shape != (n,):
+            raise ValueError("kfolds needs one label per row")
+    nf = int(np.max(kfolds))
+    labels = ORDER_SMOOTH if smooth_only else ORDER_ALL
+    nnet, ksvm, rf, earth = dict(nnet or {}), dict(ksvm or {}), dict(rf or {}), dict(earth or {})
+
+    def with_seed(lab, kw):
+        return {"seed": _member_seeds(seed, lab, nf), **kw}
+
+    def run_gbm_step(Xt, yt, j, what, defaults, over):
+        kw = {"seed": _member_int_seed(seed, "b", j), **defaults, "bag_fraction": 0.5, **(over or {})}
+        res = gbm_step(Xt, yt, **kw)
+        if res is None:
+            raise RuntimeError("machisplin.gbm.step aborted for %s: restart with a smaller learning rate" % what)
+        return res[0]
+
+    by_label = {"g": fit_linear_folds(X, resp, kfolds),
+                "n": fit_nnet_folds(X, resp, kfolds, **with_seed("n", nnet)),
+                "m": fit_earth_folds(X, resp, kfolds, **with_seed("m", earth)),
+                "v": fit_ksvm_folds(X, resp, kfolds, **with_seed("v", ksvm))}
+    if not smooth_only:
+        by_label["r"] = fit_forest_folds(X, resp, kfolds, **with_seed("r", rf))
+        by_label["b"] = []
+        for v in range(1, nf + 1):
+            tr = train_rows(kfolds, v, n)
+            by_label["b"].append(run_gbm_step(X[tr], resp[tr], v - 1, "fold %d" % v, {"tree_complexity": 25, "learning_rate": 0.01},
+                                              gbm_fold))
+    fold_models = [{lab: by_label[lab][v] for lab in labels} for v in range(nf)]
+    residuals = cv_residuals(fold_models, X, resp, kfolds, labels)
+    p_opt, kept, wts, tot = optx_weights(residuals, smooth_only)
+    scalars = lambda kw, drop: {k: v for k, v in kw.items() if k not in drop}
+    final = []
+    for lab in kept:
+        gen = [int(seed), _MEMBER[lab], nf]
+        if lab == "b":
+            m = run_gbm_step(X, resp, nf, "the final model", {"tree_complexity": 5, "learning_rate": 0.001}, gbm_final)
+        elif lab == "g":
+            m = _models.Gam.fit(X, resp)
+        elif lab == "n":
+            m = _models.nnet_fit_many([X], [resp], None, [gen], **scalars(nnet, ("wts0", "seed")))[0]
+        elif lab == "m":       # (the *_fit_many take one seed PER MODEL: [gen] names the stream, a bare gen would be read as a list of them)
+            m = _models.earth_fit_many([X], [resp], **{"nfold": 10, **scalars(earth, ("seed",)), "seed": [gen]})[0]
+        elif lab == "r":
+            m = _models.rf_fit_many([X], [resp], **{**scalars(rf, ("inbag", "seeds", "seed")), "seed": [gen]})[0]
+        else:
+            sig = ksvm.get("sigma")
+            m = _models.ksvm_fit_many([X], [resp], sig if sig is None or np.ndim(sig) == 0 else None, [gen])[0]
+        final.append(m)
+    return {"kfolds": kfolds, "fold_models": fold_models, "residuals": residuals, "p": p_opt, "labels": kept, "models": final,
+            "weights": wts, "wt_total": tot}
 
 
 def cv_residuals(fold_models, X, resp, kfolds, labels: str = ORDER_ALL):

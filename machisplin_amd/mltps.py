@@ -1,8 +1,8 @@
 """Steps 2-5 of ``machisplin.mltps`` (V73:442-930) with every raster-sized operation on the
 GPU: ensemble prediction over the covariate stack, thin-plate spline of the station
 residuals (tiled exactly as the reference tiles it, or globally), seam feathering, the
-final sum and the R^2 selection.  Model FITTING (Step 1 and the final fits) is out of scope:
-callers pass the fitted members' parameters, as a `.Call()` shim would from R.
+final sum and the R^2 selection.  Model FITTING (Step 1 and the final fits) is not done here:
+callers pass the fitted members, as a `.Call()` shim would from R or as :func:`cv.fit_layer` returns them.
 """
 from __future__ import annotations
 
@@ -218,7 +218,8 @@ def mltps(stack: RasterStack, int_values, fitted, tps: bool = True, tile_edge: i
     table as an array (columns long, lat, then one response column per layer, V73:120-154); ``fitted[i]`` holds
     layer i's ``models`` (device models in ``mods.run`` order), ``weights`` (rounded kept weights) and ``wt_total``
     (V73:337-392).  Returns the list ``omega``: one :func:`mltps_predict` result per layer plus ``n_layers``
-    (V73:955) -- Step 1 (fitting, CV, weight search) happens before this call, in R or through :mod:`cv`."""
+    (V73:955) -- Step 1 (fitting, CV, weight search) happens before this call: in R, or by :func:`cv.fit_layer`, whose
+    result for layer i IS a ``fitted[i]``."""
     int_values = np.asarray(int_values, dtype=np.float64)
     n_layers = int_values.shape[1] - 2
     if n_layers != len(fitted):

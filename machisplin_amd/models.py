@@ -147,6 +147,40 @@ class Nnet(Model):
         return m
 
 
+def nnet_fit_many(Xs, ys, wts0=None, seed=0, size=10, maxit=10000, abstol=1e-4, reltol=1e-8):
+    """:meth:`Nnet.fit` for several models (each its own rows and initial weights; the same p, size, maxit and
+    tolerances) in ONE launch, a workgroup per model (mhs_nnet_fit_many): the shape of the ten fold models of V73:249 and
+    of the final model of V73:463.  Every model gets the response scaling of V73:235-241 from its OWN rows, and equals
+    :meth:`Nnet.fit` on those rows bit for bit, whatever shares the launch.  ``wts0``: one vector per model; ``None``
+    draws model k's from ``default_rng(g_k).uniform(-0.7, 0.7, nw)`` -- nnet's ``rang``, NOT R's stream -- with ``g_k``
+    as :func:`_fit_generators` derives it from ``seed`` (an int gives model k ``[seed, k]``, a single model ``seed``; or
+    one seed per model).  Every model carries ``.wts``, ``.value``, ``.counts``, ``.fail`` and ``.wts0``."""
+    Xs, ys = _fit_inputs(Xs, ys)
+    count, p, size = len(Xs), Xs[0].shape[1], int(size)
+    nw = (p + 1) * size + size + 1
+    if wts0 is None:
+        w0 = [np.random.default_rng(g).uniform(-0.7, 0.7, nw) for g in _fit_generators(seed, count)]
+    else:
+        w0 = [_f64(w).copy() for w in wts0]
+        if len(w0) != count or any(w.size != nw for w in w0):
+            raise ValueError("wts0 must hold one vector of the length for (p, size) per model")
+    ws = [w.copy() for w in w0]
+    mn = [float(y.min()) for y in ys]
+    mx = [float((y - m).max()) for y, m in zip(ys, mn)]
+    ts = [np.ascontiguousarray((y - m) / s) for y, m, s in zip(ys, mn, mx)]
+    ns = _i64([X.shape[0] for X in Xs])
+    val, counts, fail = np.empty(count), np.zeros(2 * count, dtype=np.int32), np.zeros(count, dtype=np.int32)
+    _lib.init()
+    _lib.check(_lib.lib().mhs_nnet_fit_many(count, _ptrs(Xs), _ptrs(ts), ns.ctypes.data, p, size, _ptrs(ws), int(maxit), float(abstol),
+                                            float(reltol), val.ctypes.data, counts.ctypes.data, fail.ctypes.data))
+    out = []
+    for k in range(count):
+        m = Nnet(ws[k], p, size, mx[k], mn[k])
+        m.wts, m.value, m.counts, m.fail, m.wts0 = ws[k], float(val[k]), (int(counts[2 * k]), int(counts[2 * k + 1])), int(fail[k]), w0[k]
+        out.append(m)
+    return out
+
+
 class Earth(Model):
     """earth::earth (V73:539): coefficients, dirs and cuts of the SELECTED terms."""
     label = "m"
@@ -297,6 +331,76 @@ class Ksvm(Model):
         m.params = {"kind": "svr", "alpha": beta[sv], "sv": Z, "b": b.value, "sigma": float(sigma), "x_center": xc, "x_scale": xs,
                     "y_center": yc.value, "y_scale": ys.value}
         return m
+
+
+def sigest(X, index=None, index2=None, seed=0, frac=0.5):
+    """kernlab::sigest as ``ksvm(kpar = "automatic")`` applies it to the predictor matrix (host numpy, O(n)): the columns
+    standardised (mean, sd with n - 1), ``m = floor(frac n)`` pairs of rows ``index`` / ``index2`` drawn with replacement,
+    ``d`` their squared distances with the zeros dropped, and ``1 / quantile(d, [0.9, 0.5, 0.1])`` (linear interpolation,
+    R's type 7) returned.  ksvm's automatic sigma is the mean of the first and the third value.  ``index`` / ``index2``
+    ``None``: two draws of ``default_rng(seed).integers(0, n, m)`` -- NOT R's RNG stream, so the value is kernlab's rule
+    on other pairs; parity with kernlab is not pinned."""
+    X = np.ascontiguousarray(X, dtype=np.float64)          # one memory order: numpy's sums depend on it in the last bit
+    if X.ndim != 2 or X.shape[0] < 2:
+        raise ValueError("X must be n x p with at least two rows")
+    n = X.shape[0]
+    m = int(np.floor(frac * n))
+    z = (X - X.mean(0)) / X.std(0, ddof=1)
+    if index is None or index2 is None:
+        rng = np.random.default_rng(seed)
+        drawn = rng.integers(0, n, m), rng.integers(0, n, m)
+        index = drawn[0] if index is None else index
+        index2 = drawn[1] if index2 is None else index2
+    index, index2 = np.asarray(index), np.asarray(index2)
+    if index.shape != index2.shape or index.ndim != 1:
+        raise ValueError("index and index2 must hold as many rows each")
+    diff = z[index] - z[index2]
+    d = np.sum(diff * diff, axis=1)
+    d = d[d != 0.0]
+    if d.size == 0:
+        raise ValueError("every drawn pair of rows coincides")
+    return 1.0 / np.quantile(d, [0.9, 0.5, 0.1])
+
+
+def ksvm_fit_many(Xs, ys, sigma=None, seed=0, C_=1.0, epsilon=0.1, tol=1e-3, max_iter=0, gram_budget=0):
+    """:meth:`Ksvm.fit` for several models (each its own rows and kernel width; the same C, epsilon, tol and max_iter) in
+    ONE device call (mhs_svr_fit_many): the shape of the ten fold models of V73:251 and of the final model of V73:560.
+    Models of up to 8 192 rows share three launches (Gram matrices in one arena, the SMO a workgroup per model, rho);
+    ``gram_budget`` bounds that arena in bytes (0: half of the free device memory) and splits the batch into more
+    launches where it must; larger models follow one by one.  Every model equals :meth:`Ksvm.fit` on its rows bit for
+    bit, whatever the packing.  ``sigma``: a scalar (shared), one per model, or ``None`` -- kernlab's automatic value,
+    ``mean(sigest(X_k, seed = g_k)[[0, 2]])`` with ``g_k`` as :func:`_fit_generators` derives it from ``seed`` (an int
+    gives model k ``[seed, k]``, a single model ``seed``; or one seed per model), stored as ``.sigma``.  The models
+    carry what :meth:`Ksvm.fit` sets, and ``.sigma``."""
+    Xs, ys = _fit_inputs(Xs, ys)
+    count, p = len(Xs), Xs[0].shape[1]
+    if sigma is None:
+        sig = np.array([float(np.mean(sigest(X, seed=g)[[0, 2]])) for X, g in zip(Xs, _fit_generators(seed, count))])
+    elif np.ndim(sigma) == 0:
+        sig = np.full(count, float(sigma))
+    else:
+        sig = _f64(sigma)
+        if sig.shape != (count,):
+            raise ValueError("sigma must be a scalar or hold one value per model")
+    ns = _i64([X.shape[0] for X in Xs])
+    beta = [np.empty(X.shape[0]) for X in Xs]
+    xc, xs = [np.empty(p) for _ in Xs], [np.empty(p) for _ in Xs]
+    b, yc, ysc = np.empty(count), np.empty(count), np.empty(count)
+    it, status = np.zeros(count, dtype=np.int64), np.zeros(count, dtype=np.int32)
+    _lib.init()
+    _lib.check(_lib.lib().mhs_svr_fit_many(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, sig.ctypes.data, float(C_), float(epsilon),
+                                           float(tol), int(max_iter), int(gram_budget), _ptrs(beta), b.ctypes.data, _ptrs(xc), _ptrs(xs),
+                                           yc.ctypes.data, ysc.ctypes.data, it.ctypes.data, status.ctypes.data))
+    out = []
+    for k in range(count):
+        sv = np.flatnonzero(beta[k] != 0.0)
+        Z = (np.ascontiguousarray(Xs[k])[sv] - xc[k]) / xs[k]
+        m = Ksvm(beta[k][sv], Z, float(b[k]), float(sig[k]), xc[k], xs[k], float(yc[k]), float(ysc[k]))
+        m.beta, m.n_iter, m.sv_index, m.sigma = beta[k], int(it[k]), sv, float(sig[k])
+        m.params = {"kind": "svr", "alpha": beta[k][sv], "sv": Z, "b": float(b[k]), "sigma": float(sig[k]), "x_center": xc[k],
+                    "x_scale": xs[k], "y_center": float(yc[k]), "y_scale": float(ysc[k])}
+        out.append(m)
+    return out
 
 
 class Gbm(Model):
