@@ -456,78 +456,59 @@ int mhs_earth_fit_many(int count, const double *const *X, const double *const *y
     MHS_REQUIRE(nk <= MHS_EARTH_MAX_NK, "nk exceeds MHS_EARTH_MAX_NK (p > 32 must pass an nk)");
     MHS_REQUIRE(thresh >= 0.0 && penalty >= 0.0, "thresh and penalty must not be negative");       // (false for NaN)
     for (int k = 0; k < count; ++k) models_out[k] = nullptr;
-    // ---- checks, the sorted orders, and the layout of the uploaded block and of the work / result slabs
-    struct Lay { size_t X, y, ord, Q, XO, rg, bg, R, z, od, oi; };
+    // ---- checks, and the layout of the three blocks: [uploaded: inputs, records] [work] [out: every model's records, zeroed, all home]
+    struct Lay { FitPiece<double> X, y, Q, XO, rg, bg, R, z; FitPiece<int> ord; };
     std::vector<Lay> lay((size_t)count);
-    std::vector<EarthModelDev> hm((size_t)count);
-    FitCarve in, work;
-    size_t dpos = 0, ipos = 0;
+    FitBlock in, work, out;
     int64_t n_max = 0;
     const size_t od_len = 4 * (size_t)nk + (size_t)nk * nk + 4, oi_len = 2 * (size_t)nk + (size_t)nk * nk + 4;
     for (int k = 0; k < count; ++k) {
         MHS_REQUIRE(n[k] >= 2 && n[k] * (int64_t)std::max(p, nk) < (1LL << 31), "n out of range");
         if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
+        const size_t nn = (size_t)n[k]; n_max = std::max(n_max, n[k]);
+        lay[k].X = in.take<double>(nn * p); lay[k].y = in.take<double>(nn); lay[k].ord = in.take<int>(nn * p);
+        lay[k].Q = work.take<double>(nn * nk); lay[k].XO = work.take<double>(nn * p);
+        lay[k].rg = work.take<double>(nn); lay[k].bg = work.take<double>(nn);
+        lay[k].R = work.take<double>((size_t)nk * nk); lay[k].z = work.take<double>((size_t)nk);
+    }
+    const FitPiece<EarthModelDev> mod = in.take<EarthModelDev>((size_t)count);
+    const FitPiece<double> od = out.take<double>(od_len * count);       // the models' records back to back, as the kernel's rows are
+    const FitPiece<int> oi = out.take<int>(oi_len * count);
+    in.mirror(0, in.mark()); out.mirror(0, out.mark());
+    MHS_HIP(in.alloc()); MHS_HIP(work.alloc()); MHS_HIP(out.alloc());
+    for (int k = 0; k < count; ++k) {
+        const Lay &L = lay[k];
         const int64_t nn = n[k];
-        n_max = std::max(n_max, nn);
-        lay[k].X = in(sizeof(double) * (size_t)nn * p);
-        lay[k].y = in(sizeof(double) * (size_t)nn);
-        lay[k].ord = in(sizeof(int) * (size_t)nn * p);
-        lay[k].Q = work(sizeof(double) * (size_t)nn * nk);
-        lay[k].XO = work(sizeof(double) * (size_t)nn * p);
-        lay[k].rg = work(sizeof(double) * (size_t)nn);
-        lay[k].bg = work(sizeof(double) * (size_t)nn);
-        lay[k].R = work(sizeof(double) * (size_t)nk * nk);
-        lay[k].z = work(sizeof(double) * (size_t)nk);
-        lay[k].od = dpos; dpos += od_len;
-        lay[k].oi = ipos; ipos += oi_len;
-        hm[k].n = (int)nn; hm[k].pad = 0;
+        std::copy_n(X[k], (size_t)nn * p, in.host(L.X));
+        std::copy_n(y[k], (size_t)nn, in.host(L.y));
+        fit_sorted_orders(X[k], nn, p, in.host(L.ord));
+        EarthModelDev &m = in.host(mod)[k];
+        m.X = in.dev(L.X); m.y = in.dev(L.y); m.ord = in.dev(L.ord);
+        m.Q = work.dev(L.Q); m.XO = work.dev(L.XO); m.rg = work.dev(L.rg); m.bg = work.dev(L.bg); m.R = work.dev(L.R); m.z = work.dev(L.z);
+        m.out_d = out.dev(od) + od_len * k; m.out_i = out.dev(oi) + oi_len * k;
+        m.n = (int)nn; m.pad = 0;
         const int ms = (int)(-std::log2(-(1.0 / ((double)p * (double)nn)) * std::log(1.0 - 0.05)) / 2.5);
         const int es = (int)(3.0 - std::log2(0.05 / (double)p));
-        hm[k].minspan = minspan > 0 ? minspan : std::max(1, ms);
-        hm[k].endspan = endspan > 0 ? endspan : std::max(1, es);
-    }
-    std::vector<char> host(in.at);
-    for (int k = 0; k < count; ++k) {
-        const int64_t nn = n[k];
-        std::copy_n(X[k], (size_t)nn * p, (double *)(host.data() + lay[k].X));
-        std::copy_n(y[k], (size_t)nn, (double *)(host.data() + lay[k].y));
-        fit_sorted_orders(X[k], nn, p, (int *)(host.data() + lay[k].ord));
+        m.minspan = minspan > 0 ? minspan : std::max(1, ms);
+        m.endspan = endspan > 0 ? endspan : std::max(1, es);
     }
     hipStream_t s = ctx().stream;
-    DevBuf<char> din, dwork;
-    DevBuf<double> dod;
-    DevBuf<int> doi;
-    DevBuf<EarthModelDev> dmod;
-    MHS_HIP(din.alloc(in.at)); MHS_HIP(dwork.alloc(work.at)); MHS_HIP(dod.alloc(dpos)); MHS_HIP(doi.alloc(ipos)); MHS_HIP(dmod.alloc((size_t)count));
-    for (int k = 0; k < count; ++k) {
-        EarthModelDev &m = hm[k];
-        m.X = (const double *)(din.p + lay[k].X); m.y = (const double *)(din.p + lay[k].y); m.ord = (const int *)(din.p + lay[k].ord);
-        m.Q = (double *)(dwork.p + lay[k].Q); m.XO = (double *)(dwork.p + lay[k].XO);
-        m.rg = (double *)(dwork.p + lay[k].rg); m.bg = (double *)(dwork.p + lay[k].bg);
-        m.R = (double *)(dwork.p + lay[k].R); m.z = (double *)(dwork.p + lay[k].z);
-        m.out_d = dod.p + lay[k].od; m.out_i = doi.p + lay[k].oi;
-    }
-    MHS_HIP(hipMemcpyAsync(din.p, host.data(), in.at, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dmod.p, hm.data(), sizeof(EarthModelDev) * (size_t)count, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemsetAsync(dod.p, 0, sizeof(double) * dpos, s));
-    MHS_HIP(hipMemsetAsync(doi.p, 0, sizeof(int) * ipos, s));
+    MHS_HIP(in.upload(0, in.mark(), s));
+    MHS_HIP(out.zero(0, out.mark(), s));
     // the LDS of a block: the fixed part, then the larger of (r, the column) for the call's largest model and (R, rows of R^-1)
     const int lds_rows = (int)std::min<int64_t>(n_max, EARTH_LDS_ROWS);
     const size_t fixed = sizeof(double) * (8 + 2 * EARTH_MAXP + 3 * (MHS_EARTH_MAX_NK + 1)) + sizeof(int) * (2 * EARTH_MAXP + MHS_EARTH_MAX_NK + 3 + 8);
     const size_t lds_bytes = fit_align(fixed) + sizeof(double) * std::max<size_t>(2 * (size_t)lds_rows, 2 * (size_t)nk * nk) + 16;
     MHS_HIP(hipFuncSetAttribute((const void *)earth_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(earth_fit_kernel, dim3((unsigned)count), dim3(EARTH_T), lds_bytes, s, (const EarthModelDev *)dmod.p, p, nk, thresh, penalty,
-                       lds_rows);
+    hipLaunchKernelGGL(earth_fit_kernel, dim3((unsigned)count), dim3(EARTH_T), lds_bytes, s, (const EarthModelDev *)in.dev(mod), p, nk, thresh,
+                       penalty, lds_rows);
     MHS_HIP(hipGetLastError());
-    std::vector<double> rd(dpos);
-    std::vector<int> ri(ipos);
-    MHS_HIP(hipMemcpyAsync(rd.data(), dod.p, sizeof(double) * dpos, hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipMemcpyAsync(ri.data(), doi.p, sizeof(int) * ipos, hipMemcpyDeviceToHost, s));
+    MHS_HIP(out.download(0, out.mark(), s));
     MHS_HIP(hipStreamSynchronize(s));
     // ---- the records, then the ordinary loader
     for (int k = 0; k < count; ++k) {
-        const double *d = rd.data() + lay[k].od;
-        const int *iv = ri.data() + lay[k].oi;
+        const double *d = out.host(od) + od_len * k;
+        const int *iv = out.host(oi) + oi_len * k;
         const int *head = iv + 2 * (size_t)nk + (size_t)nk * nk;
         const int M = head[0], ksel = head[2];
         int rc = MHS_OK;

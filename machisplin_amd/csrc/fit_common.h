@@ -1,12 +1,12 @@
-// What the device fits (gbm_fit.hip, rf_fit.hip, earth_fit.hip) share: the wave primitives whose lane order fixes the
-// last bits of every sum -- the fits promise models that are bit-identical from call to call and independent of what
-// shares the launch, and that promise is the order written HERE -- and the host's staging of a batch (argument checks,
-// the rows sorted per variable, the 16-byte layout of the device blocks).
+// What the five device fits (gbm_fit.hip, rf_fit.hip, earth_fit.hip, and learn_fit.hip's nnet and ksvm) share: the wave
+// primitives whose lane order fixes the last bits of every sum -- the fits promise models that are bit-identical from
+// call to call and independent of what shares the launch, and that promise is the order written HERE -- and the host's
+// staging of a batch (argument checks, the rows sorted per variable, the typed staging block of fit_stage.h on the device).
 #pragma once
-#include <algorithm>
 #include <cmath>
 #include <numeric>
 #include "common.h"
+#include "fit_stage.h"
 
 namespace mhs {
 
@@ -86,12 +86,24 @@ __device__ __forceinline__ void fit_partition(const int *src, int *dst, int m, i
 
 // ---------------------------------------------------------------- host: staging a batch of models
 
-static __host__ __device__ inline size_t fit_align(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// Offsets into one block, every piece 16-byte aligned: carve(bytes) is where the piece starts, carve.at the bytes so far.
-struct FitCarve {
-    size_t at = 0;
-    size_t operator()(size_t bytes) { const size_t o = at; at += fit_align(bytes); return o; }
+// A FitPlan with its device memory: ONE allocation of the planned bytes, and ONE hipMemcpyAsync per upload / download of
+// a byte range [a, b) that the mirror holds.
+struct FitBlock : FitPlan {
+    DevBuf<char> d;
+    hipError_t alloc() { return d.alloc(at); }
+    template <typename T>
+    T *dev(FitPiece<T> q) const { assert(d.p && q.off + q.bytes() <= d.n); return reinterpret_cast<T *>(d.p + q.off); }
+    hipError_t upload(size_t a, size_t b, hipStream_t s) {
+        assert(from <= a && a <= b && b <= to && b <= d.n);
+        return hipMemcpyAsync(d.p + a, buf.data() + (a - from), b - a, hipMemcpyHostToDevice, s);
+    }
+    hipError_t download(size_t a, size_t b, hipStream_t s) {
+        assert(from <= a && a <= b && b <= to && b <= d.n);
+        return hipMemcpyAsync(buf.data() + (a - from), d.p + a, b - a, hipMemcpyDeviceToHost, s);
+    }
+    hipError_t zero(size_t a, size_t b, hipStream_t s) { assert(a <= b && b <= d.n); return hipMemsetAsync(d.p + a, 0, b - a, s); }
+    template <typename T>
+    hipError_t zero(FitPiece<T> q, hipStream_t s) { return zero(q.off, q.off + q.bytes(), s); }
 };
 
 // out (p x n) <- the rows in ascending order of every column of X (n x p column-major), ties in row order

@@ -248,48 +248,43 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
     MHS_REQUIRE(std::isfinite(shrinkage), "shrinkage is not finite");
     MHS_REQUIRE(!first_call || init_f, "init_f is NULL on the first call");
     const size_t cap = (size_t)n_new * (3 * (size_t)interaction_depth + 1);
-    // ---- checks, and the layout of the one device block: [uploaded | F | outputs | work]
-    struct Lay { size_t X, y, bags, ord, F, toff, sval, svar, left, right, miss, idx, scr, zg, fg; };
+    // ---- checks, and the layout of the one device block: [uploaded: inputs, records | F | outputs | work]
+    struct Lay { FitPiece<double> X, y, F, sval, zg; FitPiece<int> bags, ord, svar, left, right, miss, idx, scr;
+                 FitPiece<long long> toff; FitPiece<unsigned char> fg; };
     std::vector<Lay> lay((size_t)count);
-    FitCarve carve;
+    FitBlock blk;
+    int64_t n_max = 0;
     for (int k = 0; k < count; ++k) {
         MHS_REQUIRE(bags[k] && F[k] && tree_offsets[k] && split_var[k] && split_val[k] && left[k] && right[k] && missing[k],
                     "NULL array of a model");
         if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
         MHS_REQUIRE(bag_size[k] >= 1 && bag_size[k] <= n[k], "bag_size must be between 1 and n");
-        lay[k].X = carve(sizeof(double) * (size_t)n[k] * p);
-        lay[k].y = carve(sizeof(double) * (size_t)n[k]);
-        lay[k].bags = carve(sizeof(int) * (size_t)n_new * (size_t)bag_size[k]);
-        lay[k].ord = carve(sizeof(int) * (size_t)n[k] * p);
+        n_max = std::max(n_max, n[k]);
+        lay[k].X = blk.take<double>((size_t)n[k] * p); lay[k].y = blk.take<double>((size_t)n[k]);
+        lay[k].bags = blk.take<int>((size_t)n_new * (size_t)bag_size[k]); lay[k].ord = blk.take<int>((size_t)n[k] * p);
     }
-    const size_t in_bytes = carve.at;
-    for (int k = 0; k < count; ++k) lay[k].F = carve(sizeof(double) * (size_t)n[k]);
-    const size_t up_bytes = carve.at;
+    const FitPiece<GfModel> mod = blk.take<GfModel>((size_t)count);
+    const size_t in_end = blk.mark();
+    for (int k = 0; k < count; ++k) lay[k].F = blk.take<double>((size_t)n[k]);
+    const size_t up_end = blk.mark();
     for (int k = 0; k < count; ++k) {
-        lay[k].toff = carve(sizeof(long long) * ((size_t)n_new + 1));
-        lay[k].sval = carve(sizeof(double) * cap);
-        lay[k].svar = carve(sizeof(int) * cap);
-        lay[k].left = carve(sizeof(int) * cap);
-        lay[k].right = carve(sizeof(int) * cap);
-        lay[k].miss = carve(sizeof(int) * cap);
+        lay[k].toff = blk.take<long long>((size_t)n_new + 1);
+        lay[k].sval = blk.take<double>(cap); lay[k].svar = blk.take<int>(cap);
+        lay[k].left = blk.take<int>(cap); lay[k].right = blk.take<int>(cap); lay[k].miss = blk.take<int>(cap);
     }
-    const size_t down_end = carve.at;
+    const size_t down_end = blk.mark();
     for (int k = 0; k < count; ++k) {
-        lay[k].idx = carve(sizeof(int) * (size_t)bag_size[k] * p);
-        lay[k].scr = carve(sizeof(int) * (size_t)bag_size[k] * p);
-        lay[k].zg = carve(sizeof(double) * (size_t)n[k]);
-        lay[k].fg = carve(2 * (size_t)n[k]);
+        lay[k].idx = blk.take<int>((size_t)bag_size[k] * p); lay[k].scr = blk.take<int>((size_t)bag_size[k] * p);
+        lay[k].zg = blk.take<double>((size_t)n[k]); lay[k].fg = blk.take<unsigned char>(2 * (size_t)n[k]);
     }
-    const size_t total = carve.at;
-    std::vector<char> host(std::max(up_bytes, down_end - in_bytes));
-    int64_t n_max = 0;
+    blk.mirror(0, up_end, down_end - in_end);       // the same bytes take [F | outputs] home
+    MHS_HIP(blk.alloc());
     for (int k = 0; k < count; ++k) {
+        const Lay &L = lay[k];
         const int64_t nk = n[k], bk = bag_size[k];
-        n_max = std::max(n_max, nk);
-        double *hX = (double *)(host.data() + lay[k].X), *hy = (double *)(host.data() + lay[k].y), *hF = (double *)(host.data() + lay[k].F);
-        int *hb = (int *)(host.data() + lay[k].bags), *ho = (int *)(host.data() + lay[k].ord);
-        std::copy_n(X[k], (size_t)nk * p, hX);
-        std::copy_n(y[k], (size_t)nk, hy);
+        double *hF = blk.host(L.F); int *hb = blk.host(L.bags);
+        std::copy_n(X[k], (size_t)nk * p, blk.host(L.X));
+        std::copy_n(y[k], (size_t)nk, blk.host(L.y));
         double sum = 0.0;
         for (int64_t i = 0; i < nk; ++i) sum += y[k][i];
         if (first_call) {
@@ -307,46 +302,37 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
                 stamp[(size_t)r] = t;
                 hb[(size_t)t * bk + b] = r;
             }
-        fit_sorted_orders(X[k], nk, p, ho);
+        fit_sorted_orders(X[k], nk, p, blk.host(L.ord));
+        GfModel &m = blk.host(mod)[k];
+        m.X = blk.dev(L.X); m.y = blk.dev(L.y); m.F = blk.dev(L.F); m.bags = blk.dev(L.bags); m.ord = blk.dev(L.ord);
+        m.idx = blk.dev(L.idx); m.scr = blk.dev(L.scr); m.zg = blk.dev(L.zg); m.fg = blk.dev(L.fg);
+        m.toff = blk.dev(L.toff); m.sval = blk.dev(L.sval); m.svar = blk.dev(L.svar);
+        m.left = blk.dev(L.left); m.right = blk.dev(L.right); m.miss = blk.dev(L.miss);
+        m.n = (int)nk; m.bag = (int)bk;
     }
     hipStream_t s = ctx().stream;
-    DevBuf<char> dev;
-    DevBuf<GfModel> dmod;
-    MHS_HIP(dev.alloc(total)); MHS_HIP(dmod.alloc((size_t)count));
-    std::vector<GfModel> hm((size_t)count);
-    for (int k = 0; k < count; ++k) {
-        GfModel &m = hm[k];
-        char *b = dev.p;
-        m.X = (const double *)(b + lay[k].X); m.y = (const double *)(b + lay[k].y); m.F = (double *)(b + lay[k].F);
-        m.bags = (const int *)(b + lay[k].bags); m.ord = (const int *)(b + lay[k].ord);
-        m.idx = (int *)(b + lay[k].idx); m.scr = (int *)(b + lay[k].scr); m.zg = (double *)(b + lay[k].zg);
-        m.fg = (unsigned char *)(b + lay[k].fg);
-        m.toff = (long long *)(b + lay[k].toff); m.sval = (double *)(b + lay[k].sval); m.svar = (int *)(b + lay[k].svar);
-        m.left = (int *)(b + lay[k].left); m.right = (int *)(b + lay[k].right); m.miss = (int *)(b + lay[k].miss);
-        m.n = (int)n[k]; m.bag = (int)bag_size[k];
-    }
-    MHS_HIP(hipMemcpyAsync(dev.p, host.data(), up_bytes, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dmod.p, hm.data(), sizeof(GfModel) * (size_t)count, hipMemcpyHostToDevice, s));
+    MHS_HIP(blk.upload(0, up_end, s));
     const int lds_rows = (int)std::min<int64_t>(n_max, GF_LDS_ROWS);
     const size_t lds_bytes = fit_align((size_t)lds_rows * 10);
     MHS_HIP(hipFuncSetAttribute((const void *)gbm_grow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(gbm_grow_kernel, dim3((unsigned)count), dim3(GF_T), lds_bytes, s, (const GfModel *)dmod.p, p, n_new,
+    hipLaunchKernelGGL(gbm_grow_kernel, dim3((unsigned)count), dim3(GF_T), lds_bytes, s, (const GfModel *)blk.dev(mod), p, n_new,
                        interaction_depth, n_minobsinnode, shrinkage, lds_rows);
     MHS_HIP(hipGetLastError());
-    MHS_HIP(hipMemcpyAsync(host.data(), dev.p + in_bytes, down_end - in_bytes, hipMemcpyDeviceToHost, s));
+    blk.mirror(in_end, down_end);
+    MHS_HIP(blk.download(in_end, down_end, s));
     MHS_HIP(hipStreamSynchronize(s));
     for (int k = 0; k < count; ++k) {
-        const char *b = host.data() - in_bytes;
-        std::copy_n((const double *)(b + lay[k].F), (size_t)n[k], F[k]);
-        const long long *to = (const long long *)(b + lay[k].toff);
+        const Lay &L = lay[k];
+        std::copy_n(blk.host(L.F), (size_t)n[k], F[k]);
+        const long long *to = blk.host(L.toff);
         for (int t = 0; t <= n_new; ++t) tree_offsets[k][t] = (int64_t)to[t];
         const size_t nn = (size_t)to[n_new];
         if (nn > cap) { set_error("mhs_gbm_grow_many: node count exceeds its bound"); return MHS_ERR_NUMERIC; }
-        std::copy_n((const double *)(b + lay[k].sval), nn, split_val[k]);
-        std::copy_n((const int *)(b + lay[k].svar), nn, split_var[k]);
-        std::copy_n((const int *)(b + lay[k].left), nn, left[k]);
-        std::copy_n((const int *)(b + lay[k].right), nn, right[k]);
-        std::copy_n((const int *)(b + lay[k].miss), nn, missing[k]);
+        std::copy_n(blk.host(L.sval), nn, split_val[k]);
+        std::copy_n(blk.host(L.svar), nn, split_var[k]);
+        std::copy_n(blk.host(L.left), nn, left[k]);
+        std::copy_n(blk.host(L.right), nn, right[k]);
+        std::copy_n(blk.host(L.miss), nn, missing[k]);
     }
     return MHS_OK;
 }

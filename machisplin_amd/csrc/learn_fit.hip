@@ -613,49 +613,47 @@ static int svr_fit_pack(const char *fn, const int *pack, int m, const double *co
                         const double *sigma, double C, double epsilon, double tol, int64_t max_iter, double *const *beta,
                         double *const *x_center, double *const *x_scale, double *y_center, double *y_scale, SmoOut *h) {
     hipStream_t s = ctx().stream;
-    FitCarve carve;
-    std::vector<size_t> oZ(m), ot(m), oal(m), oas(m), okb(m);
+    struct Lay { FitPiece<double> Z, t, al, as, kb; };
+    std::vector<Lay> lay((size_t)m);
+    FitBlock blk;
     size_t rows = 0, gram = 0;
     int64_t nmax = 0;
     for (int e = 0; e < m; ++e) {
         const size_t nk = (size_t)n[pack[e]];
-        oZ[e] = carve(sizeof(double) * nk * p); ot[e] = carve(sizeof(double) * nk);
+        lay[e].Z = blk.take<double>(nk * p); lay[e].t = blk.take<double>(nk);
         rows += nk; gram += nk * nk; nmax = std::max<int64_t>(nmax, (int64_t)nk);
     }
-    const size_t ojobs = carve(sizeof(SvrJob) * (size_t)m);
-    const size_t upload = carve.at;                                     // what the host fills: Z, t, the job records
+    const FitPiece<SvrJob> jobs = blk.take<SvrJob>((size_t)m);
+    const size_t up_end = blk.mark();                                   // what the host fills: Z, t, the job records
     for (int e = 0; e < m; ++e) {
         const size_t nk = (size_t)n[pack[e]];
-        oal[e] = carve(sizeof(double) * nk); oas[e] = carve(sizeof(double) * nk); okb[e] = carve(sizeof(double) * nk);
+        lay[e].al = blk.take<double>(nk); lay[e].as = blk.take<double>(nk); lay[e].kb = blk.take<double>(nk);
     }
-    const size_t obeta = carve(sizeof(double) * rows);                  // the betas back to back, then the records: one copy home
-    const size_t oout = carve(sizeof(SmoOut) * (size_t)m);
-    std::vector<char> host(upload, 0);
+    const size_t down_from = blk.mark();
+    const FitPiece<double> betas = blk.take<double>(rows);              // the betas back to back, then the records: one copy home
+    const FitPiece<SmoOut> outs = blk.take<SmoOut>((size_t)m);
+    blk.mirror(0, up_end, blk.mark() - down_from);
     for (int e = 0; e < m; ++e) {
         const int k = pack[e];
-        if (int rc = svr_scale(fn, X[k], y[k], n[k], p, reinterpret_cast<double *>(host.data() + oZ[e]),
-                               reinterpret_cast<double *>(host.data() + ot[e]), x_center[k], x_scale[k], y_center + k, y_scale + k)) return rc;
+        if (int rc = svr_scale(fn, X[k], y[k], n[k], p, blk.host(lay[e].Z), blk.host(lay[e].t), x_center[k], x_scale[k], y_center + k,
+                               y_scale + k)) return rc;
     }
-    DevBuf<char> blk;
     DevBuf<double> dK;
-    MHS_HIP(blk.alloc(carve.at)); MHS_HIP(dK.alloc(gram));
-    SvrJob *jobs = reinterpret_cast<SvrJob *>(host.data() + ojobs);
+    MHS_HIP(blk.alloc()); MHS_HIP(dK.alloc(gram));
     size_t kat = 0, bat = 0;
     for (int e = 0; e < m; ++e) {
         const int k = pack[e];
         const size_t nk = (size_t)n[k];
-        SvrJob &j = jobs[e];
-        j.Z = reinterpret_cast<const double *>(blk.p + oZ[e]); j.t = reinterpret_cast<const double *>(blk.p + ot[e]);
+        SvrJob &j = blk.host(jobs)[e];
+        j.Z = blk.dev(lay[e].Z); j.t = blk.dev(lay[e].t);
         j.K = dK.p + kat;
-        j.al = reinterpret_cast<double *>(blk.p + oal[e]); j.as = reinterpret_cast<double *>(blk.p + oas[e]);
-        j.kb = reinterpret_cast<double *>(blk.p + okb[e]); j.beta = reinterpret_cast<double *>(blk.p + obeta) + bat;
+        j.al = blk.dev(lay[e].al); j.as = blk.dev(lay[e].as); j.kb = blk.dev(lay[e].kb); j.beta = blk.dev(betas) + bat;
         j.sigma = sigma[k]; j.max_iter = svr_iter_limit(max_iter, (int64_t)nk); j.n = (int)nk; j.pad = 0;
         kat += nk * nk; bat += nk;
     }
-    MHS_HIP(hipMemcpyAsync(blk.p, host.data(), upload, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemsetAsync(blk.p + oout, 0, sizeof(SmoOut) * (size_t)m, s));
-    const SvrJob *dj = reinterpret_cast<const SvrJob *>(blk.p + ojobs);
-    SmoOut *dout = reinterpret_cast<SmoOut *>(blk.p + oout);
+    MHS_HIP(blk.upload(0, up_end, s));
+    MHS_HIP(blk.zero(outs, s));
+    const SvrJob *dj = blk.dev(jobs); SmoOut *dout = blk.dev(outs);
     const unsigned gx = (unsigned)std::min<int64_t>((nmax * nmax + 255) / 256, 2048);
     hipLaunchKernelGGL(rbf_gram_many_kernel, dim3(gx, (unsigned)m), dim3(256), 0, s, dj, p);
     MHS_HIP(hipGetLastError());
@@ -666,16 +664,15 @@ static int svr_fit_pack(const char *fn, const int *pack, int m, const double *co
     MHS_HIP(hipGetLastError());
     hipLaunchKernelGGL(svr_rho_many_kernel, dim3((unsigned)m), dim3(256), 0, s, dj, C, epsilon, dout);
     MHS_HIP(hipGetLastError());
-    std::vector<char> back(carve.at - obeta);
-    MHS_HIP(hipMemcpyAsync(back.data(), blk.p + obeta, back.size(), hipMemcpyDeviceToHost, s));
+    blk.mirror(down_from, blk.mark());
+    MHS_HIP(blk.download(down_from, blk.mark(), s));
     MHS_HIP(hipStreamSynchronize(s));
-    const double *hb = reinterpret_cast<const double *>(back.data());
-    const SmoOut *ho = reinterpret_cast<const SmoOut *>(back.data() + (oout - obeta));
+    const double *hb = blk.host(betas);
     bat = 0;
     for (int e = 0; e < m; ++e) {
         const size_t nk = (size_t)n[pack[e]];
         std::copy(hb + bat, hb + bat + nk, beta[pack[e]]);
-        h[pack[e]] = ho[e];
+        h[pack[e]] = blk.host(outs)[e];
         bat += nk;
     }
     return MHS_OK;
@@ -689,36 +686,34 @@ static int nnet_fit_batch(const char *fn, int count, const double *const *X, con
     FIT_REQUIRE(X && y && n && wts, "NULL argument");
     FIT_REQUIRE(size == NN_H, "this build fits nnet(size = 10) only (V73:249, V73:463)");
     const int NW = (p + 1) * NN_H + NN_H + 1;
-    FitCarve carve;
-    std::vector<size_t> oX(count), oy(count);
+    struct Lay { FitPiece<double> X, y; };
+    std::vector<Lay> lay((size_t)count);
+    FitBlock blk;
     for (int k = 0; k < count; ++k) {
         FIT_REQUIRE(wts[k], "NULL weights of a model");
         if (int rc = fit_check_model(fn, X[k], y[k], n[k], p)) return rc;
-        oX[k] = carve(sizeof(double) * (size_t)n[k] * p); oy[k] = carve(sizeof(double) * (size_t)n[k]);
+        lay[k].X = blk.take<double>((size_t)n[k] * p); lay[k].y = blk.take<double>((size_t)n[k]);
     }
-    const size_t ojobs = carve(sizeof(NnJob) * (size_t)count);
-    const size_t ow = carve(sizeof(double) * (size_t)NW * count);      // the weights back to back, then the records: one copy home
-    const size_t upload = carve.at;
-    const size_t oout = carve(sizeof(NnOut) * (size_t)count);
-    DevBuf<char> blk;
-    MHS_HIP(blk.alloc(carve.at));
-    std::vector<char> host(upload, 0);
-    NnJob *jobs = reinterpret_cast<NnJob *>(host.data() + ojobs);
+    const FitPiece<NnJob> jobs = blk.take<NnJob>((size_t)count);
+    const FitPiece<double> w = blk.take<double>((size_t)NW * count);    // the weights back to back, then the records: one copy home
+    const size_t up_end = blk.mark();
+    const FitPiece<NnOut> outs = blk.take<NnOut>((size_t)count);
+    blk.mirror(0, blk.mark());
+    MHS_HIP(blk.alloc());
     for (int k = 0; k < count; ++k) {
         // rows in the kernel's order (row-major) from R's column-major matrix
-        double *Xr = reinterpret_cast<double *>(host.data() + oX[k]);
+        double *Xr = blk.host(lay[k].X);
         for (int j = 0; j < p; ++j)
             for (int64_t r = 0; r < n[k]; ++r) Xr[(size_t)r * p + j] = X[k][(size_t)j * n[k] + r];
-        std::copy(y[k], y[k] + n[k], reinterpret_cast<double *>(host.data() + oy[k]));
-        std::copy(wts[k], wts[k] + NW, reinterpret_cast<double *>(host.data() + ow) + (size_t)k * NW);
-        jobs[k].X = reinterpret_cast<const double *>(blk.p + oX[k]); jobs[k].y = reinterpret_cast<const double *>(blk.p + oy[k]);
-        jobs[k].wts = reinterpret_cast<double *>(blk.p + ow) + (size_t)k * NW; jobs[k].n = (int)n[k]; jobs[k].pad = 0;
+        std::copy(y[k], y[k] + n[k], blk.host(lay[k].y));
+        std::copy(wts[k], wts[k] + NW, blk.host(w) + (size_t)k * NW);
+        NnJob &j = blk.host(jobs)[k];
+        j.X = blk.dev(lay[k].X); j.y = blk.dev(lay[k].y); j.wts = blk.dev(w) + (size_t)k * NW; j.n = (int)n[k]; j.pad = 0;
     }
     hipStream_t s = ctx().stream;
-    MHS_HIP(hipMemcpyAsync(blk.p, host.data(), upload, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemsetAsync(blk.p + oout, 0, sizeof(NnOut) * (size_t)count, s));
-    const NnJob *dj = reinterpret_cast<const NnJob *>(blk.p + ojobs);
-    NnOut *dout = reinterpret_cast<NnOut *>(blk.p + oout);
+    MHS_HIP(blk.upload(0, up_end, s));
+    MHS_HIP(blk.zero(outs, s));
+    const NnJob *dj = blk.dev(jobs); NnOut *dout = blk.dev(outs);
     int rc = MHS_OK;
     switch (p) {
 #define MHS_NNF(P_) case P_: rc = launch_nnet_fit<P_>(dj, count, maxit, abstol, reltol, dout, s); break;
@@ -726,11 +721,9 @@ static int nnet_fit_batch(const char *fn, int count, const double *const *X, con
 #undef MHS_NNF
     }
     if (rc) return rc;
-    std::vector<char> back(carve.at - ow);
-    MHS_HIP(hipMemcpyAsync(back.data(), blk.p + ow, back.size(), hipMemcpyDeviceToHost, s));
+    MHS_HIP(blk.download(w.off, blk.mark(), s));
     MHS_HIP(hipStreamSynchronize(s));
-    const double *hw = reinterpret_cast<const double *>(back.data());
-    const NnOut *ho = reinterpret_cast<const NnOut *>(back.data() + (oout - ow));
+    const double *hw = blk.host(w); const NnOut *ho = blk.host(outs);
     int bad = -1;
     for (int k = 0; k < count; ++k) {
         std::copy(hw + (size_t)k * NW, hw + (size_t)(k + 1) * NW, wts[k]);

@@ -365,14 +365,13 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
     MHS_REQUIRE(nodesize >= 1, "nodesize must be positive");
     MHS_REQUIRE((int64_t)count * n_trees < (1LL << 30), "too many trees in one call");
     for (int k = 0; k < count; ++k) models_out[k] = nullptr;
-    // ---- checks, and the layout of the uploaded block
-    struct Lay { size_t X, y, ord, inbag, seeds; };
+    // ---- checks, and the layout of the uploaded block: every model's inputs, then the model and tree records
+    struct Lay { FitPiece<double> X, y; FitPiece<int> ord, inbag; FitPiece<unsigned long long> seeds; };
     std::vector<Lay> lay((size_t)count);
-    const size_t total_trees = (size_t)count * (size_t)n_trees;
-    std::vector<RfTree> ht(total_trees);
-    std::vector<RfModelDev> hm((size_t)count);
+    const size_t NT = (size_t)count * (size_t)n_trees;
+    std::vector<RfTree> ht(NT);
     std::vector<long long> out_base((size_t)count + 1, 0), res_off((size_t)count + 1, 0);
-    FitCarve in;
+    FitBlock in, work, res;
     long long idx_total = 0, node_total = 0, row_total = 0;
     int64_t n_max = 0;
     for (int k = 0; k < count; ++k) {
@@ -380,12 +379,8 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
         const int64_t nk = n[k];
         n_max = std::max(n_max, nk);
-        lay[k].X = in(sizeof(double) * (size_t)nk * p);
-        lay[k].y = in(sizeof(double) * (size_t)nk);
-        lay[k].ord = in(sizeof(int) * (size_t)nk * p);
-        lay[k].inbag = in(sizeof(int) * (size_t)nk * n_trees);
-        lay[k].seeds = in(sizeof(unsigned long long) * (size_t)n_trees);
-        hm[k].n = (int)nk; hm[k].first_tree = k * n_trees; hm[k].row_base = row_total;
+        lay[k].X = in.take<double>((size_t)nk * p); lay[k].y = in.take<double>((size_t)nk); lay[k].ord = in.take<int>((size_t)nk * p);
+        lay[k].inbag = in.take<int>((size_t)nk * n_trees); lay[k].seeds = in.take<unsigned long long>((size_t)n_trees);
         long long out_nodes = 0;
         for (int t = 0; t < n_trees; ++t) {
             const int32_t *cb = inbag[k] + (size_t)t * nk;
@@ -407,88 +402,80 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         out_base[k + 1] = out_base[k] + out_nodes;
         res_off[k + 1] = res_off[k] + nk;
     }
-    const size_t in_bytes = in.at;
-    std::vector<char> host(in_bytes);
+    const size_t NN = (size_t)node_total, NR = (size_t)row_total, NO = (size_t)out_base[count], NS = (size_t)res_off[count];
+    const FitPiece<RfModelDev> mod = in.take<RfModelDev>((size_t)count);
+    const FitPiece<RfTree> tree = in.take<RfTree>(NT);
+    // ---- the other two blocks: [work: index buffers, node slabs, per-tree rows] and [results: what comes home at once | compacted arrays]
+    const FitPiece<int> w_idx = work.take<int>((size_t)idx_total), w_scr = work.take<int>((size_t)idx_total);
+    FitPiece<int> w_int[6], r_int[4];
+    FitPiece<double> w_dbl[4], r_dbl[2];
+    for (auto &a : w_int) a = work.take<int>(NN);
+    for (auto &a : w_dbl) a = work.take<double>(NN);
+    const FitPiece<double> w_oob = work.take<double>(NR);
+    const FitPiece<unsigned char> w_mark = work.take<unsigned char>(NR);
+    const FitPiece<double> w_pur = work.take<double>(NT * p);
+    const FitPiece<int> w_nn = work.take<int>(NT), w_flag = work.take<int>(NT);
+    const FitPiece<long long> r_toff = res.take<long long>((size_t)count * ((size_t)n_trees + 1));
+    const FitPiece<int> r_flag = res.take<int>(NT);
+    const FitPiece<double> r_oobp = res.take<double>(NS);
+    const FitPiece<int> r_oobc = res.take<int>(NS);
+    const FitPiece<double> r_pur = res.take<double>((size_t)count * p);
+    const size_t small_end = res.mark();
+    for (auto &a : r_int) a = res.take<int>(NO);
+    for (auto &a : r_dbl) a = res.take<double>(NO);
+    in.mirror(0, in.mark()); res.mirror(0, small_end);
+    MHS_HIP(in.alloc()); MHS_HIP(work.alloc()); MHS_HIP(res.alloc());
+    std::copy(ht.begin(), ht.end(), in.host(tree));
     for (int k = 0; k < count; ++k) {
+        const Lay &L = lay[k];
         const int64_t nk = n[k];
-        std::copy_n(X[k], (size_t)nk * p, (double *)(host.data() + lay[k].X));
-        std::copy_n(y[k], (size_t)nk, (double *)(host.data() + lay[k].y));
-        std::copy_n(inbag[k], (size_t)nk * n_trees, (int *)(host.data() + lay[k].inbag));
-        std::copy_n(seeds[k], (size_t)n_trees, (unsigned long long *)(host.data() + lay[k].seeds));
-        fit_sorted_orders(X[k], nk, p, (int *)(host.data() + lay[k].ord));
-    }
-    // ---- device memory: [uploaded] [work: index buffers, node slabs, per-tree rows] [results]
-    const size_t NT = total_trees, NN = (size_t)node_total, NR = (size_t)row_total, NO = (size_t)out_base[count], NS = (size_t)res_off[count];
-    FitCarve work;
-    const size_t w_idx = work(sizeof(int) * (size_t)idx_total), w_scr = work(sizeof(int) * (size_t)idx_total);
-    size_t w_int[6], w_dbl[4];
-    for (size_t &a : w_int) a = work(sizeof(int) * NN);
-    for (size_t &a : w_dbl) a = work(sizeof(double) * NN);
-    const size_t w_oob = work(sizeof(double) * NR), w_mark = work(NR), w_pur = work(sizeof(double) * NT * p);
-    const size_t w_nn = work(sizeof(int) * NT), w_flag = work(sizeof(int) * NT);
-    const size_t work_bytes = work.at;
-    FitCarve res;
-    const size_t r_toff = res(sizeof(long long) * (size_t)count * ((size_t)n_trees + 1)), r_flag = res(sizeof(int) * NT);
-    const size_t r_oobp = res(sizeof(double) * NS), r_oobc = res(sizeof(int) * NS), r_pur = res(sizeof(double) * (size_t)count * p);
-    const size_t small_bytes = res.at;
-    size_t r_int[4], r_dbl[2];
-    for (size_t &a : r_int) a = res(sizeof(int) * NO);
-    for (size_t &a : r_dbl) a = res(sizeof(double) * NO);
-    const size_t res_bytes = res.at;
-    hipStream_t s = ctx().stream;
-    DevBuf<char> din, dwork, dres;
-    DevBuf<RfModelDev> dmod;
-    DevBuf<RfTree> dtree;
-    MHS_HIP(din.alloc(in_bytes)); MHS_HIP(dwork.alloc(work_bytes)); MHS_HIP(dres.alloc(res_bytes));
-    MHS_HIP(dmod.alloc((size_t)count)); MHS_HIP(dtree.alloc(NT));
-    for (int k = 0; k < count; ++k) {
-        RfModelDev &m = hm[k];
-        m.X = (const double *)(din.p + lay[k].X); m.y = (const double *)(din.p + lay[k].y); m.ord = (const int *)(din.p + lay[k].ord);
-        m.inbag = (const int *)(din.p + lay[k].inbag); m.seeds = (const unsigned long long *)(din.p + lay[k].seeds);
-        m.oob_pred = (double *)(dres.p + r_oobp) + res_off[k]; m.oob_count = (int *)(dres.p + r_oobc) + res_off[k];
-        m.purity = (double *)(dres.p + r_pur) + (size_t)k * p;
+        std::copy_n(X[k], (size_t)nk * p, in.host(L.X));
+        std::copy_n(y[k], (size_t)nk, in.host(L.y));
+        std::copy_n(inbag[k], (size_t)nk * n_trees, in.host(L.inbag));
+        std::copy_n(seeds[k], (size_t)n_trees, in.host(L.seeds));
+        fit_sorted_orders(X[k], nk, p, in.host(L.ord));
+        RfModelDev &m = in.host(mod)[k];
+        m.X = in.dev(L.X); m.y = in.dev(L.y); m.ord = in.dev(L.ord); m.inbag = in.dev(L.inbag); m.seeds = in.dev(L.seeds);
+        m.oob_pred = res.dev(r_oobp) + res_off[k]; m.oob_count = res.dev(r_oobc) + res_off[k];
+        m.purity = res.dev(r_pur) + (size_t)k * p;
+        m.row_base = ht[(size_t)k * n_trees].row_off; m.n = (int)nk; m.first_tree = k * n_trees;
     }
     RfWork S;
-    S.idx = (int *)(dwork.p + w_idx); S.scr = (int *)(dwork.p + w_scr);
-    S.left = (int *)(dwork.p + w_int[0]); S.right = (int *)(dwork.p + w_int[1]); S.var = (int *)(dwork.p + w_int[2]);
-    S.start = (int *)(dwork.p + w_int[3]); S.cnt = (int *)(dwork.p + w_int[4]); S.pop = (int *)(dwork.p + w_int[5]);
-    S.split = (double *)(dwork.p + w_dbl[0]); S.pred = (double *)(dwork.p + w_dbl[1]); S.tot = (double *)(dwork.p + w_dbl[2]);
-    S.crit = (double *)(dwork.p + w_dbl[3]);
-    S.oob = (double *)(dwork.p + w_oob); S.mark = (unsigned char *)(dwork.p + w_mark); S.purity = (double *)(dwork.p + w_pur);
-    S.n_nodes = (int *)(dwork.p + w_nn); S.flag = (int *)(dwork.p + w_flag);
-    MHS_HIP(hipMemcpyAsync(din.p, host.data(), in_bytes, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dmod.p, hm.data(), sizeof(RfModelDev) * (size_t)count, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemcpyAsync(dtree.p, ht.data(), sizeof(RfTree) * NT, hipMemcpyHostToDevice, s));
-    MHS_HIP(hipMemsetAsync(S.flag, 0, sizeof(int) * NT, s));
+    S.idx = work.dev(w_idx); S.scr = work.dev(w_scr);
+    S.left = work.dev(w_int[0]); S.right = work.dev(w_int[1]); S.var = work.dev(w_int[2]);
+    S.start = work.dev(w_int[3]); S.cnt = work.dev(w_int[4]); S.pop = work.dev(w_int[5]);
+    S.split = work.dev(w_dbl[0]); S.pred = work.dev(w_dbl[1]); S.tot = work.dev(w_dbl[2]); S.crit = work.dev(w_dbl[3]);
+    S.oob = work.dev(w_oob); S.mark = work.dev(w_mark); S.purity = work.dev(w_pur);
+    S.n_nodes = work.dev(w_nn); S.flag = work.dev(w_flag);
+    const RfModelDev *dmod = in.dev(mod); const RfTree *dtree = in.dev(tree);
+    hipStream_t s = ctx().stream;
+    MHS_HIP(in.upload(0, in.mark(), s));
+    MHS_HIP(work.zero(w_flag, s));
     // the LDS of a block is sized by the rows of the call's largest model (up to RF_LDS_ROWS), so small trees share a compute unit
     const int lds_rows = (int)std::min<int64_t>(n_max, RF_LDS_ROWS);
     const size_t lds_bytes = fit_align(sizeof(double) * (size_t)lds_rows) + fit_align(sizeof(int) * (size_t)lds_rows) + fit_align((size_t)lds_rows) +
                              (2 * sizeof(double) + 2 * sizeof(int)) * RF_PAIRS + 16;
     MHS_HIP(hipFuncSetAttribute((const void *)rf_grow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(rf_grow_kernel, dim3((unsigned)NT), dim3(RF_T), lds_bytes, s, (const RfModelDev *)dmod.p, (const RfTree *)dtree.p, S, p,
-                       mtry, nodesize, lds_rows);
+    hipLaunchKernelGGL(rf_grow_kernel, dim3((unsigned)NT), dim3(RF_T), lds_bytes, s, dmod, dtree, S, p, mtry, nodesize, lds_rows);
     MHS_HIP(hipGetLastError());
-    long long *d_toff = (long long *)(dres.p + r_toff);
-    hipLaunchKernelGGL(rf_offsets_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, (const int *)S.n_nodes, d_toff, count, n_trees);
+    long long *d_toff = res.dev(r_toff);
+    hipLaunchKernelGGL(rf_offsets_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, S.n_nodes, d_toff, count, n_trees);
     MHS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf_compact_kernel, dim3((unsigned)NT), dim3(256), 0, s, (const RfTree *)dtree.p, S, (const long long *)d_toff, n_trees,
-                       (int *)(dres.p + r_int[0]), (int *)(dres.p + r_int[1]), (int *)(dres.p + r_int[2]), (int *)(dres.p + r_int[3]),
-                       (double *)(dres.p + r_dbl[0]), (double *)(dres.p + r_dbl[1]));
+    hipLaunchKernelGGL(rf_compact_kernel, dim3((unsigned)NT), dim3(256), 0, s, dtree, S, d_toff, n_trees, res.dev(r_int[0]), res.dev(r_int[1]),
+                       res.dev(r_int[2]), res.dev(r_int[3]), res.dev(r_dbl[0]), res.dev(r_dbl[1]));
     MHS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf_reduce_kernel, dim3((unsigned)((n_max + 255) / 256), (unsigned)count), dim3(256), 0, s, (const RfModelDev *)dmod.p, S, p,
-                       n_trees);
+    hipLaunchKernelGGL(rf_reduce_kernel, dim3((unsigned)((n_max + 255) / 256), (unsigned)count), dim3(256), 0, s, dmod, S, p, n_trees);
     MHS_HIP(hipGetLastError());
-    MHS_HIP(hipMemcpyAsync(dres.p + r_flag, S.flag, sizeof(int) * NT, hipMemcpyDeviceToDevice, s));
-    std::vector<char> small(small_bytes);
-    MHS_HIP(hipMemcpyAsync(small.data(), dres.p, small_bytes, hipMemcpyDeviceToHost, s));
+    MHS_HIP(hipMemcpyAsync(res.dev(r_flag), S.flag, r_flag.bytes(), hipMemcpyDeviceToDevice, s));
+    MHS_HIP(res.download(0, small_end, s));
     MHS_HIP(hipStreamSynchronize(s));
-    const int *flags = (const int *)(small.data() + r_flag);
+    const int *flags = res.host(r_flag);
     for (size_t t = 0; t < NT; ++t)
         if (flags[t]) { set_error("mhs_rf_fit_many: a tree's node count exceeds its bound"); return MHS_ERR_NUMERIC; }
     // ---- the compacted arrays of every model, then the ordinary loader
     std::vector<std::shared_ptr<RfFitted>> fitted((size_t)count);
     for (int k = 0; k < count; ++k) {
-        const long long *to = (const long long *)(small.data() + r_toff) + (size_t)k * ((size_t)n_trees + 1);
+        const long long *to = res.host(r_toff) + (size_t)k * ((size_t)n_trees + 1);
         const size_t nn = (size_t)to[n_trees];
         if ((long long)nn > out_base[k + 1] - out_base[k]) { set_error("mhs_rf_fit_many: node count exceeds its bound"); return MHS_ERR_NUMERIC; }
         auto f = std::make_shared<RfFitted>();
@@ -497,9 +484,9 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         int32_t *const ia[4] = {f->left.data(), f->right.data(), f->status.data(), f->best_var.data()};
         double *const da[2] = {f->split.data(), f->node_pred.data()};
         for (int a = 0; a < 4; ++a)
-            MHS_HIP(hipMemcpyAsync(ia[a], (const int *)(dres.p + r_int[a]) + out_base[k], sizeof(int) * nn, hipMemcpyDeviceToHost, s));
+            MHS_HIP(hipMemcpyAsync(ia[a], res.dev(r_int[a]) + out_base[k], sizeof(int) * nn, hipMemcpyDeviceToHost, s));
         for (int a = 0; a < 2; ++a)
-            MHS_HIP(hipMemcpyAsync(da[a], (const double *)(dres.p + r_dbl[a]) + out_base[k], sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+            MHS_HIP(hipMemcpyAsync(da[a], res.dev(r_dbl[a]) + out_base[k], sizeof(double) * nn, hipMemcpyDeviceToHost, s));
         fitted[k] = f;
     }
     MHS_HIP(hipStreamSynchronize(s));
@@ -514,9 +501,9 @@ int mhs_rf_fit_many(int count, const double *const *X, const double *const *y, c
         }
         m->rf_fitted = fitted[k];
         models_out[k] = m;
-        if (oob_pred && oob_pred[k]) std::copy_n((const double *)(small.data() + r_oobp) + res_off[k], (size_t)n[k], oob_pred[k]);
-        if (oob_count && oob_count[k]) std::copy_n((const int *)(small.data() + r_oobc) + res_off[k], (size_t)n[k], oob_count[k]);
-        if (inc_node_purity && inc_node_purity[k]) std::copy_n((const double *)(small.data() + r_pur) + (size_t)k * p, (size_t)p, inc_node_purity[k]);
+        if (oob_pred && oob_pred[k]) std::copy_n(res.host(r_oobp) + res_off[k], (size_t)n[k], oob_pred[k]);
+        if (oob_count && oob_count[k]) std::copy_n(res.host(r_oobc) + res_off[k], (size_t)n[k], oob_count[k]);
+        if (inc_node_purity && inc_node_purity[k]) std::copy_n(res.host(r_pur) + (size_t)k * p, (size_t)p, inc_node_purity[k]);
     }
     return MHS_OK;
 }

@@ -59,12 +59,8 @@ def fit_forest_folds(X, resp, kfolds, n_trees=500, mtry=None, nodesize=5, inbag=
     array per fold (over that fold's training rows); ``None`` draws fold v's from ``default_rng([seed, v - 1])``.
     Returns the fold models in fold order, ready for the ``r`` slot of ``fold_models`` in :func:`cv_residuals`."""
     from .models import rf_fit_many
-    X = np.asarray(X, dtype=np.float64)
-    resp = np.asarray(resp, dtype=np.float64)
-    nfolds = int(np.max(kfolds))
-    rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
-    gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
-    return rf_fit_many([X[r] for r in rows], [resp[r] for r in rows], n_trees, mtry, nodesize, inbag, seeds, gen)
+    Xs, ys, gen = _fold_batch(X, resp, kfolds, seed)
+    return rf_fit_many(Xs, ys, n_trees, mtry, nodesize, inbag, seeds, gen)
 
 
 def fit_earth_folds(X, resp, kfolds, nfold=10, seed=0, nk=None, thresh=0.001, penalty=2.0, minspan=0, endspan=0):
@@ -75,12 +71,8 @@ def fit_earth_folds(X, resp, kfolds, nfold=10, seed=0, nk=None, thresh=0.001, pe
     ``default_rng([seed, v - 1])``.  Returns the fold models in fold order, ready for the ``m`` slot of ``fold_models`` in
     :func:`cv_residuals`."""
     from .models import earth_fit_many
-    X = np.asarray(X, dtype=np.float64)
-    resp = np.asarray(resp, dtype=np.float64)
-    nfolds = int(np.max(kfolds))
-    rows = [train_rows(kfolds, v, X.shape[0]) for v in range(1, nfolds + 1)]
-    gen = [[int(seed), v] for v in range(nfolds)] if np.ndim(seed) == 0 else list(seed)
-    return earth_fit_many([X[r] for r in rows], [resp[r] for r in rows], nk, thresh, penalty, minspan, endspan, nfold, None, gen)
+    Xs, ys, gen = _fold_batch(X, resp, kfolds, seed)
+    return earth_fit_many(Xs, ys, nk, thresh, penalty, minspan, endspan, nfold, None, gen)
 
 
 def _fold_batch(X, resp, kfolds, seed):

@@ -52,16 +52,22 @@ class Model:
             self._h = None
 
 
+def _fit_xy(X, y):
+    """The rows of one fit: X as float64 in column-major order, y as float64, one response per row."""
+    X, y = np.asfortranarray(np.asarray(X, dtype=np.float64)), _f64(y)
+    if X.ndim != 2 or X.shape[0] != y.size:
+        raise ValueError("X must be n x p with one response per row")
+    return X, y
+
+
 def _fit_inputs(Xs, ys):
-    """The batch of a ``*_fit_many``: every X as float64 in column-major order, every y as float64; one response vector
-    per matrix, one response per row, the same p throughout."""
-    Xs = [np.asfortranarray(np.asarray(X, dtype=np.float64)) for X in Xs]
-    ys = [_f64(y) for y in ys]
+    """The batch of a ``*_fit_many``: :func:`_fit_xy` of every model; one response vector per matrix, the same p throughout."""
+    Xs, ys = list(Xs), list(ys)
     if not Xs or len(Xs) != len(ys):
         raise ValueError("need one response vector per predictor matrix")
-    for X, y in zip(Xs, ys):
-        if X.ndim != 2 or X.shape[0] != y.size or X.shape[1] != Xs[0].shape[1]:
-            raise ValueError("every X must be n x p with one response per row and the same p")
+    Xs, ys = map(list, zip(*[_fit_xy(X, y) for X, y in zip(Xs, ys)]))
+    if any(X.shape[1] != Xs[0].shape[1] for X in Xs):
+        raise ValueError("every X must have the same p")
     return Xs, ys
 
 
@@ -100,10 +106,7 @@ class Gam(Model):
     def fit(cls, X, y) -> "Gam":
         """mgcv::gam(resp ~ a + b + ..., data) (V73:252, V73:600): least squares on the device (Householder QR of
         [1 X]).  X is n x p in rast_stack order, rows with NA already dropped (V73:154)."""
-        X = np.asfortranarray(np.asarray(X, dtype=np.float64))
-        y = _f64(y)
-        if X.ndim != 2 or X.shape[0] != y.size:
-            raise ValueError("X must be n x p with one response per row")
+        X, y = _fit_xy(X, y)
         coef = np.empty(X.shape[1] + 1)
         _lib.check(_lib.lib().mhs_lm_fit(X.ctypes.data, y.ctypes.data, X.shape[0], X.shape[1], coef.ctypes.data))
         return cls(coef)
@@ -127,24 +130,30 @@ class Nnet(Model):
         """nnet::nnet(mod.form, data = trainNN, size = 10, linout = TRUE, maxit = 10000) with the response scaling of
         V73:455-459 (resp - min, / max) around it, on the device (R's vmmin in one resident kernel).  wts0: the
         initial weights, nnet order (nnet draws runif(-0.7, 0.7)).  The object carries .wts, .value, .counts, .fail."""
-        X = np.asfortranarray(np.asarray(X, dtype=np.float64))
-        y = _f64(y)
-        if X.ndim != 2 or X.shape[0] != y.size:
-            raise ValueError("X must be n x p with one response per row")
+        X, y = _fit_xy(X, y)
         n, p = X.shape
         w = _f64(wts0).copy()
         if w.size != (p + 1) * size + size + 1:
             raise ValueError("wts0 has the wrong length for (p, size)")
-        mn = float(y.min())
-        mx = float((y - mn).max())
-        ys = np.ascontiguousarray((y - mn) / mx)
+        mn, mx, ys = _nnet_scaled(y)
         val, counts, fail = C.c_double(), (C.c_int * 2)(), C.c_int()
         _lib.init()
         _lib.check(_lib.lib().mhs_nnet_fit(X.ctypes.data, ys.ctypes.data, n, p, int(size), w.ctypes.data, int(maxit), float(abstol),
                                            float(reltol), C.byref(val), counts, C.byref(fail)))
-        m = cls(w, p, size, mx, mn)
-        m.wts, m.value, m.counts, m.fail = w, val.value, (counts[0], counts[1]), fail.value
-        return m
+        return _nnet_object(w, p, size, mx, mn, val.value, counts, fail.value)
+
+
+def _nnet_scaled(y):
+    """V73:455-459: (min, max of resp - min, (resp - min) / max), the response nnet is trained on"""
+    mn = float(y.min())
+    mx = float((y - mn).max())
+    return mn, mx, np.ascontiguousarray((y - mn) / mx)
+
+
+def _nnet_object(w, p, size, mx, mn, value, counts, fail):
+    m = Nnet(w, p, size, mx, mn)
+    m.wts, m.value, m.counts, m.fail = w, float(value), (int(counts[0]), int(counts[1])), int(fail)
+    return m
 
 
 def nnet_fit_many(Xs, ys, wts0=None, seed=0, size=10, maxit=10000, abstol=1e-4, reltol=1e-8):
@@ -165,9 +174,7 @@ def nnet_fit_many(Xs, ys, wts0=None, seed=0, size=10, maxit=10000, abstol=1e-4, 
         if len(w0) != count or any(w.size != nw for w in w0):
             raise ValueError("wts0 must hold one vector of the length for (p, size) per model")
     ws = [w.copy() for w in w0]
-    mn = [float(y.min()) for y in ys]
-    mx = [float((y - m).max()) for y, m in zip(ys, mn)]
-    ts = [np.ascontiguousarray((y - m) / s) for y, m, s in zip(ys, mn, mx)]
+    mn, mx, ts = zip(*[_nnet_scaled(y) for y in ys])
     ns = _i64([X.shape[0] for X in Xs])
     val, counts, fail = np.empty(count), np.zeros(2 * count, dtype=np.int32), np.zeros(count, dtype=np.int32)
     _lib.init()
@@ -175,8 +182,8 @@ def nnet_fit_many(Xs, ys, wts0=None, seed=0, size=10, maxit=10000, abstol=1e-4, 
                                             float(reltol), val.ctypes.data, counts.ctypes.data, fail.ctypes.data))
     out = []
     for k in range(count):
-        m = Nnet(ws[k], p, size, mx[k], mn[k])
-        m.wts, m.value, m.counts, m.fail, m.wts0 = ws[k], float(val[k]), (int(counts[2 * k]), int(counts[2 * k + 1])), int(fail[k]), w0[k]
+        m = _nnet_object(ws[k], p, size, mx[k], mn[k], val[k], counts[2 * k:2 * k + 2], fail[k])
+        m.wts0 = w0[k]
         out.append(m)
     return out
 
@@ -313,10 +320,7 @@ class Ksvm(Model):
         """kernlab::ksvm(mod.form, data) (V73:251, V73:560) on the device: eps-svr, rbfdot, scaled = TRUE, kernlab's
         defaults for C / epsilon / tol.  sigma is kpar$sigma (kernlab's automatic value is drawn by sigest() from a
         random half of the rows).  The fitted object carries .beta (n), .n_iter and the support-vector bundle."""
-        X = np.asfortranarray(np.asarray(X, dtype=np.float64))
-        y = _f64(y)
-        if X.ndim != 2 or X.shape[0] != y.size:
-            raise ValueError("X must be n x p with one response per row")
+        X, y = _fit_xy(X, y)
         n, p = X.shape
         beta, xc, xs = np.empty(n), np.empty(p), np.empty(p)
         b, yc, ys, it = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
@@ -324,13 +328,18 @@ class Ksvm(Model):
         _lib.check(_lib.lib().mhs_svr_fit(X.ctypes.data, y.ctypes.data, n, p, float(sigma), float(C_), float(epsilon), float(tol),
                                           int(max_iter), beta.ctypes.data, C.byref(b), xc.ctypes.data, xs.ctypes.data,
                                           C.byref(yc), C.byref(ys), C.byref(it)))
-        sv = np.flatnonzero(beta != 0.0)
-        Z = (np.ascontiguousarray(X)[sv] - xc) / xs
-        m = cls(beta[sv], Z, b.value, sigma, xc, xs, yc.value, ys.value)
-        m.beta, m.n_iter, m.sv_index = beta, int(it.value), sv
-        m.params = {"kind": "svr", "alpha": beta[sv], "sv": Z, "b": b.value, "sigma": float(sigma), "x_center": xc, "x_scale": xs,
-                    "y_center": yc.value, "y_scale": ys.value}
-        return m
+        return _ksvm_object(X, beta, b.value, sigma, xc, xs, yc.value, ys.value, it.value)
+
+
+def _ksvm_object(X, beta, b, sigma, xc, xs, yc, ys, n_iter):
+    """the Ksvm of a fit's result: the support vectors are the rows with beta != 0, scaled as the fit scaled them"""
+    sv = np.flatnonzero(beta != 0.0)
+    Z = (np.ascontiguousarray(X)[sv] - xc) / xs
+    m = Ksvm(beta[sv], Z, float(b), float(sigma), xc, xs, float(yc), float(ys))
+    m.beta, m.n_iter, m.sv_index, m.sigma = beta, int(n_iter), sv, float(sigma)
+    m.params = {"kind": "svr", "alpha": beta[sv], "sv": Z, "b": float(b), "sigma": float(sigma), "x_center": xc, "x_scale": xs,
+                "y_center": float(yc), "y_scale": float(ys)}
+    return m
 
 
 def sigest(X, index=None, index2=None, seed=0, frac=0.5):
@@ -391,16 +400,7 @@ def ksvm_fit_many(Xs, ys, sigma=None, seed=0, C_=1.0, epsilon=0.1, tol=1e-3, max
     _lib.check(_lib.lib().mhs_svr_fit_many(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, sig.ctypes.data, float(C_), float(epsilon),
                                            float(tol), int(max_iter), int(gram_budget), _ptrs(beta), b.ctypes.data, _ptrs(xc), _ptrs(xs),
                                            yc.ctypes.data, ysc.ctypes.data, it.ctypes.data, status.ctypes.data))
-    out = []
-    for k in range(count):
-        sv = np.flatnonzero(beta[k] != 0.0)
-        Z = (np.ascontiguousarray(Xs[k])[sv] - xc[k]) / xs[k]
-        m = Ksvm(beta[k][sv], Z, float(b[k]), float(sig[k]), xc[k], xs[k], float(yc[k]), float(ysc[k]))
-        m.beta, m.n_iter, m.sv_index, m.sigma = beta[k], int(it[k]), sv, float(sig[k])
-        m.params = {"kind": "svr", "alpha": beta[k][sv], "sv": Z, "b": float(b[k]), "sigma": float(sig[k]), "x_center": xc[k],
-                    "x_scale": xs[k], "y_center": float(yc[k]), "y_scale": float(ysc[k])}
-        out.append(m)
-    return out
+    return [_ksvm_object(Xs[k], beta[k], b[k], sig[k], xc[k], xs[k], yc[k], ysc[k], it[k]) for k in range(count)]
 
 
 class Gbm(Model):
