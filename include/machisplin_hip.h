@@ -324,6 +324,18 @@ MHS_API int mhs_gbm_grow_many(int count, const double *const *X, const double *c
                               int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
                               int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
                               int32_t *const *left, int32_t *const *right, int32_t *const *missing);
+/* mhs_gbm_grow_many -- the same code, the same trees bit for bit -- that also returns what gbm keeps as ErrorReduction:
+ * error_reduction[k] (room for n_new * (3 interaction_depth + 1) doubles, node-aligned with the five node arrays) holds
+ * the improvement of every split node, 0 at terminals.  Summed per variable it is gbm's relative.influence, what
+ * summary.gbm's contributions are made of (V73:495, V73:2115, V73:2210).  error_reduction, or any error_reduction[k], may
+ * be NULL.
+ * replaces gbm's $trees[[t]][[7]] (ErrorReduction) behind summary.gbm V73:495                                          */
+MHS_API int mhs_gbm_grow_many_reduction(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                                        const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth,
+                                        int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
+                                        int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
+                                        int32_t *const *left, int32_t *const *right, int32_t *const *missing,
+                                        double *const *error_reduction);
 /* randomForest regression $forest (V73:517): per-tree columns concatenated
  * (leftDaughter/rightDaughter 1-based tree-local, nodestatus -1 terminal, bestvar
  * 1-based, xbestsplit, nodepred).
@@ -356,8 +368,8 @@ MHS_API int mhs_rf_load(int64_t n_trees, const int64_t *tree_offsets, const int3
  * Outputs per forest: models_out[k], an ordinary mhs_model (mhs_rf_load's path; mhs_rf_get returns its arrays);
  * oob_pred[k] (n[k]): the mean, in tree order, of the predictions of the trees with inbag == 0 for the row, NaN where
  * there is none; oob_count[k] (n[k]): how many there are; inc_node_purity[k] (p): the winning criteria summed per
- * variable over all trees / n_trees (IncNodePurity).  Permutation importance (importance = TRUE's %IncMSE) is out of
- * scope: it needs a second source of randomness.  Any of the three output arrays (not models_out) may be NULL.
+ * variable over all trees / n_trees (IncNodePurity).  Permutation importance (importance = TRUE's %IncMSE) is
+ * mhs_rf_importance_many's, on the handle this call returns.  Any of the three output arrays (not models_out) may be NULL.
  * MHS_ERR_INVALID: NaN / infinite X or y, a negative count, a tree whose counts are all zero, mtry outside 1 .. p, p
  * outside mhs_rf_load's range, nodesize < 1, NULL arguments.
  * replaces randomForest::randomForest(mod.form, data = train) V73:248, V73:517                                       */
@@ -372,6 +384,30 @@ MHS_API int mhs_rf_fit_many(int count, const double *const *X, const double *con
  * (n_trees + 1, from 0)                                                                                                */
 MHS_API int mhs_rf_get(const mhs_model *m, int64_t *n_nodes, int32_t *left, int32_t *right, int32_t *status,
                        int32_t *best_var, double *split, double *node_pred, int64_t *tree_offsets);
+/* randomForest(importance = TRUE)$importance's %IncMSE and $importanceSD -- V73:517-519 -- for `count` forests in ONE
+ * launch, a workgroup per tree: regRF's permutation importance with the randomness made an input, as seeds drive the
+ * variable draw of mhs_rf_fit_many.  models[k] is ANY randomForest handle (mhs_rf_load's or mhs_rf_fit_many's) of p
+ * predictors; the forests of one call have the SAME number of trees, n_trees, and live on the current device; X[k] (n[k] x p column-major), y[k] and inbag[k] (n_trees x n[k], as in the fit) are its training rows and
+ * bags, perm_seeds[k] n_trees uint64.  Walk rule: mhs_rf_load's, x <= split goes left.  THE RULE, for tree t with seed
+ * s_t: O = the rows with inbag[t][i] == 0 in ascending order, m = |O|; e0 = sum over O of (pred_t(x_i) - y_i)^2; a
+ * variable is USED if some split node of the tree tests it.  For a used variable v and k = 0 .. n_perm - 1:
+ * h = mix(s_t + k p + v) (mod 2^64, mix as in mhs_rf_fit_many), key_j = mix(h + j) for j = 0 .. m - 1, sigma = the stable
+ * ascending argsort of the keys (ties to the lower j); row O_j is walked with its x_v replaced by x_v of row O_sigma(j);
+ * e_k = the same sum of squares.  delta[t][v] = (sum_k e_k / n_perm - e0) / m; 0 for an unused variable; 0 for every
+ * variable of a tree with m = 0 (a stated DEPARTURE: regRF would divide by zero).  IncMSE_v = sum_t delta[t][v] /
+ * n_trees, summed in tree order; SD_v = sqrt(max(0, (sum_t delta[t][v]^2 / n_trees - IncMSE_v^2) / n_trees))
+ * ($importanceSD).  R's Mersenne-Twister stream is NOT reproduced (the caveat of the fit).  The sums of squares are added
+ * 64 rows at a time in a fixed order (rf_importance.hip): bit-reproducible and independent of what shares the launch.
+ * Outputs per forest, each may be NULL: inc_mse[k] (p, the RAW importance as $importance holds it), inc_mse_sd[k] (p),
+ * tree_delta[k] (n_trees x p row-major).
+ * MHS_ERR_INVALID: a handle that is not a forest or whose p differs, forests of different tree counts or on another
+ * device, n_perm outside 1 .. 16, NaN / infinite X or y, a
+ * negative in-bag count, NULL required arguments.
+ * replaces randomForest(importance = TRUE)$importance[, "%IncMSE"] / $importanceSD V73:517-519                        */
+MHS_API int mhs_rf_importance_many(int count, const mhs_model *const *models, const double *const *X,
+                                   const double *const *y, const int64_t *n, int p, const int32_t *const *inbag,
+                                   const uint64_t *const *perm_seeds, int n_perm, double *const *inc_mse,
+                                   double *const *inc_mse_sd, double *const *tree_delta);
 /* earth::earth(mod.form, data, nfold = 10) -- V73:250 (once per CV fold), V73:539 (the final model) -- as that call
  * drives it: degree = 1, pmethod = "backward", penalty = 2, thresh = 0.001, nk = min(200, max(20, 2 p)) + 1, minspan =
  * endspan = 0 (automatic), numeric predictors, no weights, no NA rows (V73:154); for `count` independent models in ONE

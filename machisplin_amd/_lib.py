@@ -122,9 +122,12 @@ SIGNATURES = {
     "mhs_gbm_load": (C.c_int, [C.c_double, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "mhs_gbm_grow_many": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mhs_gbm_grow_many_reduction": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mhs_rf_load": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "mhs_rf_fit_many": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mhs_rf_get": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mhs_rf_importance_many": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "mhs_model_free": (C.c_int, [_vp]),
     "mhs_predict_dev": (C.c_int, [_vp, C.POINTER(Grid), C.POINTER(Stack), _i64, _i64, _i64, _i64,
                                   C.c_double, C.c_int, _vp, _i64, _vp]),

@@ -10,6 +10,15 @@
 
 namespace mhs {
 
+// The counter-based generator behind every draw the caller seeds (the header's mix(z)): randomForest's per-node variable draw
+// (rf_fit.hip) and the keys of its permutation importance (rf_importance.hip).
+__host__ __device__ inline unsigned long long fit_mix(unsigned long long z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---------------------------------------------------------------- device: one wave of 64 lanes
 
 // The wave's sum by an xor butterfly: every lane adds the same pairs, so all lanes hold one value.  NOT devmath.h's

@@ -28,6 +28,10 @@
 // to call and do not depend on which other models share the launch -- but the left sums differ from gbm's sequential
 // ones in the last bits, and two candidate splits whose improvements agree to ~1e-13 relative may be ordered
 // differently.  Split VALUES are 0.5 * (x_prev + x) of the data and are bit-equal whenever the same candidate wins.
+//
+// mhs_gbm_grow_many_reduction is the same kernel with one more output: the improvement every split node won with (gbm's
+// ErrorReduction, what relative.influence sums per variable), kept in a sixth per-node LDS array and written in the
+// stored preorder beside the five node arrays, 0 at terminals.
 #include <vector>
 #include "fit_common.h"
 
@@ -52,6 +56,7 @@ struct GfModel {
     long long *toff;                    // n_new + 1
     int *svar, *left, *right, *miss;    // n_new * (3 depth + 1)
     double *sval;
+    double *red;                        // n_new * (3 depth + 1): the improvement of every split node (NULL: not asked for)
     int n, bag;
 };
 
@@ -97,6 +102,7 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
     __shared__ double t_sum[GF_SLOTS], b_imp[GF_SLOTS], b_ls[GF_SLOTS], b_sv[GF_SLOTS];
     __shared__ int n_var[GF_NODES], n_left[GF_NODES], n_right[GF_NODES], n_miss[GF_NODES], n_pre[GF_NODES];
     __shared__ double n_val[GF_NODES];          // split value of an internal node, mean of z (then x shrinkage) of a terminal one
+    __shared__ double n_imp[GF_NODES];          // the improvement an internal node was split for (gbm's ErrorReduction), 0 at a terminal one
     __shared__ double r_imp[2 * GF_MAXP], r_ls[2 * GF_MAXP], r_sv[2 * GF_MAXP];
     __shared__ int r_pos[2 * GF_MAXP], s_nterm, s_nnodes;
 
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
             }
             if (lane == 0) {
                 t_node[0] = 0; t_start[0] = 0; t_cnt[0] = B; t_sum[0] = carry;
-                n_var[0] = -1; n_val[0] = carry / (double)B; n_left[0] = n_right[0] = n_miss[0] = 0;
+                n_var[0] = -1; n_val[0] = carry / (double)B; n_left[0] = n_right[0] = n_miss[0] = 0; n_imp[0] = 0.0;
                 s_nterm = 1; s_nnodes = 1;
             }
         }
@@ -177,9 +183,10 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
             if (tid == 0) {
                 const int pn = t_node[k], nn = s_nnodes;
                 const double pm = n_val[pn];
-                n_var[pn] = v; n_val[pn] = sv; n_left[pn] = nn; n_right[pn] = nn + 1; n_miss[pn] = nn + 2;
+                n_var[pn] = v; n_val[pn] = sv; n_left[pn] = nn; n_right[pn] = nn + 1; n_miss[pn] = nn + 2; n_imp[pn] = best;
                 n_var[nn] = -1; n_val[nn] = ls / (double)nL;
                 n_var[nn + 1] = -1; n_val[nn + 1] = (tot - ls) / (double)(m - nL);
+                n_imp[nn] = n_imp[nn + 1] = n_imp[nn + 2] = 0.0;
                 n_var[nn + 2] = -1; n_val[nn + 2] = pm;                     // no NA in the training rows (V73:154): the parent's mean
                 // the left child takes the parent's place in the terminal list, right and missing are appended
                 t_node[k] = nn; t_cnt[k] = nL; t_sum[k] = ls;
@@ -220,6 +227,7 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
             M.left[o] = split ? n_pre[n_left[e]] : -1;
             M.right[o] = split ? n_pre[n_right[e]] : -1;
             M.miss[o] = split ? n_pre[n_miss[e]] : -1;
+            if (M.red) M.red[o] = split ? n_imp[e] : 0.0;
         }
         node_off += nnodes;
         if (tid == 0) M.toff[t + 1] = node_off;
@@ -231,34 +239,33 @@ __global__ __launch_bounds__(GF_T) void gbm_grow_kernel(const GfModel *__restric
 
 using namespace mhs;
 
-extern "C" {
-
-int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
-                      const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth,
-                      int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
-                      int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
-                      int32_t *const *left, int32_t *const *right, int32_t *const *missing) {
+// Both entry points: `fn` is the name the argument errors carry; error_reduction NULL = mhs_gbm_grow_many.
+static int gbm_grow_many(const char *fn, int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                         const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth, int n_minobsinnode,
+                         double shrinkage, int first_call, double *const *F, double *init_f, int64_t *const *tree_offsets,
+                         int32_t *const *split_var, double *const *split_val, int32_t *const *left, int32_t *const *right,
+                         int32_t *const *missing, double *const *error_reduction) {
     if (int rc = require_ready()) return rc;
-    MHS_REQUIRE(X && y && n && bags && bag_size && F && tree_offsets && split_var && split_val && left && right && missing,
+    FIT_REQUIRE(X && y && n && bags && bag_size && F && tree_offsets && split_var && split_val && left && right && missing,
                 "NULL argument");
-    if (int rc = fit_check_batch(__func__, count, p, GF_MAXP)) return rc;
-    MHS_REQUIRE(n_new >= 1 && n_new < (1 << 24), "n_new out of range");
-    MHS_REQUIRE(interaction_depth >= 1 && interaction_depth <= GF_MAXDEPTH, "interaction_depth must be 1..64");
-    MHS_REQUIRE(n_minobsinnode >= 1, "n_minobsinnode must be positive");
-    MHS_REQUIRE(std::isfinite(shrinkage), "shrinkage is not finite");
-    MHS_REQUIRE(!first_call || init_f, "init_f is NULL on the first call");
+    if (int rc = fit_check_batch(fn, count, p, GF_MAXP)) return rc;
+    FIT_REQUIRE(n_new >= 1 && n_new < (1 << 24), "n_new out of range");
+    FIT_REQUIRE(interaction_depth >= 1 && interaction_depth <= GF_MAXDEPTH, "interaction_depth must be 1..64");
+    FIT_REQUIRE(n_minobsinnode >= 1, "n_minobsinnode must be positive");
+    FIT_REQUIRE(std::isfinite(shrinkage), "shrinkage is not finite");
+    FIT_REQUIRE(!first_call || init_f, "init_f is NULL on the first call");
     const size_t cap = (size_t)n_new * (3 * (size_t)interaction_depth + 1);
     // ---- checks, and the layout of the one device block: [uploaded: inputs, records | F | outputs | work]
-    struct Lay { FitPiece<double> X, y, F, sval, zg; FitPiece<int> bags, ord, svar, left, right, miss, idx, scr;
+    struct Lay { FitPiece<double> X, y, F, sval, zg, red; FitPiece<int> bags, ord, svar, left, right, miss, idx, scr;
                  FitPiece<long long> toff; FitPiece<unsigned char> fg; };
     std::vector<Lay> lay((size_t)count);
     FitBlock blk;
     int64_t n_max = 0;
     for (int k = 0; k < count; ++k) {
-        MHS_REQUIRE(bags[k] && F[k] && tree_offsets[k] && split_var[k] && split_val[k] && left[k] && right[k] && missing[k],
+        FIT_REQUIRE(bags[k] && F[k] && tree_offsets[k] && split_var[k] && split_val[k] && left[k] && right[k] && missing[k],
                     "NULL array of a model");
-        if (int rc = fit_check_model(__func__, X[k], y[k], n[k], p)) return rc;
-        MHS_REQUIRE(bag_size[k] >= 1 && bag_size[k] <= n[k], "bag_size must be between 1 and n");
+        if (int rc = fit_check_model(fn, X[k], y[k], n[k], p)) return rc;
+        FIT_REQUIRE(bag_size[k] >= 1 && bag_size[k] <= n[k], "bag_size must be between 1 and n");
         n_max = std::max(n_max, n[k]);
         lay[k].X = blk.take<double>((size_t)n[k] * p); lay[k].y = blk.take<double>((size_t)n[k]);
         lay[k].bags = blk.take<int>((size_t)n_new * (size_t)bag_size[k]); lay[k].ord = blk.take<int>((size_t)n[k] * p);
@@ -272,6 +279,9 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
         lay[k].sval = blk.take<double>(cap); lay[k].svar = blk.take<int>(cap);
         lay[k].left = blk.take<int>(cap); lay[k].right = blk.take<int>(cap); lay[k].miss = blk.take<int>(cap);
     }
+    const auto wants_red = [&](int k) { return error_reduction && error_reduction[k]; };
+    for (int k = 0; k < count; ++k)
+        if (wants_red(k)) lay[k].red = blk.take<double>(cap);
     const size_t down_end = blk.mark();
     for (int k = 0; k < count; ++k) {
         lay[k].idx = blk.take<int>((size_t)bag_size[k] * p); lay[k].scr = blk.take<int>((size_t)bag_size[k] * p);
@@ -291,14 +301,14 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
             init_f[k] = sum / (double)nk;
             for (int64_t i = 0; i < nk; ++i) hF[i] = init_f[k];
         } else {
-            for (int64_t i = 0; i < nk; ++i) { MHS_REQUIRE(std::isfinite(F[k][i]), "non-finite F"); hF[i] = F[k][i]; }
+            for (int64_t i = 0; i < nk; ++i) { FIT_REQUIRE(std::isfinite(F[k][i]), "non-finite F"); hF[i] = F[k][i]; }
         }
         std::vector<int> stamp((size_t)nk, -1);
         for (int t = 0; t < n_new; ++t)
             for (int64_t b = 0; b < bk; ++b) {
                 const int32_t r = bags[k][(size_t)t * bk + b];
-                MHS_REQUIRE(r >= 0 && r < nk, "bag index out of range");
-                MHS_REQUIRE(stamp[(size_t)r] != t, "a row appears twice in one bag (gbm samples without replacement)");
+                FIT_REQUIRE(r >= 0 && r < nk, "bag index out of range");
+                FIT_REQUIRE(stamp[(size_t)r] != t, "a row appears twice in one bag (gbm samples without replacement)");
                 stamp[(size_t)r] = t;
                 hb[(size_t)t * bk + b] = r;
             }
@@ -308,6 +318,7 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
         m.idx = blk.dev(L.idx); m.scr = blk.dev(L.scr); m.zg = blk.dev(L.zg); m.fg = blk.dev(L.fg);
         m.toff = blk.dev(L.toff); m.sval = blk.dev(L.sval); m.svar = blk.dev(L.svar);
         m.left = blk.dev(L.left); m.right = blk.dev(L.right); m.miss = blk.dev(L.miss);
+        m.red = wants_red(k) ? blk.dev(L.red) : nullptr;
         m.n = (int)nk; m.bag = (int)bk;
     }
     hipStream_t s = ctx().stream;
@@ -327,14 +338,36 @@ int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y,
         const long long *to = blk.host(L.toff);
         for (int t = 0; t <= n_new; ++t) tree_offsets[k][t] = (int64_t)to[t];
         const size_t nn = (size_t)to[n_new];
-        if (nn > cap) { set_error("mhs_gbm_grow_many: node count exceeds its bound"); return MHS_ERR_NUMERIC; }
+        if (nn > cap) { set_error("%s: node count exceeds its bound", fn); return MHS_ERR_NUMERIC; }
         std::copy_n(blk.host(L.sval), nn, split_val[k]);
         std::copy_n(blk.host(L.svar), nn, split_var[k]);
         std::copy_n(blk.host(L.left), nn, left[k]);
         std::copy_n(blk.host(L.right), nn, right[k]);
         std::copy_n(blk.host(L.miss), nn, missing[k]);
+        if (wants_red(k)) std::copy_n(blk.host(L.red), nn, error_reduction[k]);
     }
     return MHS_OK;
+}
+
+extern "C" {
+
+int mhs_gbm_grow_many(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                      const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth,
+                      int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
+                      int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
+                      int32_t *const *left, int32_t *const *right, int32_t *const *missing) {
+    return gbm_grow_many(__func__, count, X, y, n, p, bags, bag_size, n_new, interaction_depth, n_minobsinnode, shrinkage, first_call, F,
+                         init_f, tree_offsets, split_var, split_val, left, right, missing, nullptr);
+}
+
+int mhs_gbm_grow_many_reduction(int count, const double *const *X, const double *const *y, const int64_t *n, int p,
+                                const int32_t *const *bags, const int64_t *bag_size, int n_new, int interaction_depth,
+                                int n_minobsinnode, double shrinkage, int first_call, double *const *F, double *init_f,
+                                int64_t *const *tree_offsets, int32_t *const *split_var, double *const *split_val,
+                                int32_t *const *left, int32_t *const *right, int32_t *const *missing,
+                                double *const *error_reduction) {
+    return gbm_grow_many(__func__, count, X, y, n, p, bags, bag_size, n_new, interaction_depth, n_minobsinnode, shrinkage, first_call, F,
+                         init_f, tree_offsets, split_var, split_val, left, right, missing, error_reduction);
 }
 
 }  // extern "C"

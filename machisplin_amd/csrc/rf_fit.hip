@@ -4,12 +4,12 @@
 // predictors, no NA in the training rows (V73:154).  The randomness is an INPUT, as gbm's bags are in gbm_fit.hip:
 // inbag[t][i] says how many times row i is in tree t's bootstrap (a row with count c weighs c in every sum and every
 // population count: the same tree as duplicating the row, because no candidate lies between equal values), and one
-// uint64 seed per tree drives the per-node variable draw through a counter-based generator (rf_mix / rf_draw below), so
+// uint64 seed per tree drives the per-node variable draw through a counter-based generator (fit_mix / rf_draw below), so
 // the growth carries no sequential RNG state.  R's Mersenne-Twister stream is NOT reproduced: the forest is
 // randomForest's for these bags and draws, not for R's set.seed (the caveat of Gbm.fit).  The modulo bias of the draw
 // is accepted (p <= 64).  The RANDOM tie-break between equal criteria of recent randomForest releases is not
 // reproduced either: ties go to the lowest position within a variable and to the first drawn variable.  Permutation
-// importance (importance = TRUE's %IncMSE) is out of scope: it needs a second source of randomness.
+// importance (importance = TRUE's %IncMSE) takes its randomness from the caller in the same way: rf_importance.hip.
 //
 // The parallelism is across trees: a forest is n_trees INDEPENDENT CARTs, and the ten fold forests of a layer are
 // 5 000 of them.  One launch grows all count x n_trees trees, ONE WORKGROUP (4 waves) PER TREE; the dynamic LDS is sized
@@ -84,21 +84,14 @@ struct RfWork {
     int *n_nodes, *flag;                                // per tree
 };
 
-__host__ __device__ inline unsigned long long rf_mix(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // The j-th drawn variable of node k of a tree with seed `seed`: ind[] lives one entry per lane (p <= 64).  Every lane
 // returns the same value.
 __device__ __forceinline__ int rf_draw(unsigned long long seed, int k, int j, int p) {
     const int lane = threadIdx.x & 63;
-    const unsigned long long h = rf_mix(seed + (unsigned long long)k);
+    const unsigned long long h = fit_mix(seed + (unsigned long long)k);
     int ind = lane, last = p - 1, take = 0;
     for (int s = 0; s <= j; ++s) {
-        const int i = (int)(rf_mix(h + (unsigned long long)s) % (unsigned long long)(last + 1));
+        const int i = (int)(fit_mix(h + (unsigned long long)s) % (unsigned long long)(last + 1));
         take = __shfl(ind, i);
         const int moved = __shfl(ind, last);
         if (lane == i) ind = moved;

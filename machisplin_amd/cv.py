@@ -138,7 +138,7 @@ def _member_int_seed(seed, lab, j):
 
 
 def fit_layer(X, resp, kfolds=None, seed=0, smooth_only=False, nfolds=10, gbm_fold=None, gbm_final=None, rf=None, earth=None,
-              nnet=None, ksvm=None):
+              nnet=None, ksvm=None, var_imp=False):
     """Step 1 and the final fits of ONE response layer (V73:220-620), every fit on the device:
 
     1. the fold labels: ``kfolds`` as given (1-based, one per row) or :func:`kfold` ``(n, nfolds, seed)`` (V73:220);
@@ -161,9 +161,17 @@ def fit_layer(X, resp, kfolds=None, seed=0, smooth_only=False, nfolds=10, gbm_fo
     ``SeedSequence([seed, 0, j])``; the fold labels come from ``default_rng(seed)``.  A ``seed`` in a member's dict
     replaces that member's derivation for the folds.  The same arguments give bit-identical results.
 
+    ``var_imp = True`` adds the layer's ``$var.imp`` (V73:465 ... 602), a dict by kept label of one entry per predictor,
+    in predictor order: ``b`` :meth:`models.Gbm.contributions` (percent), ``g`` the p slope coefficients (the intercept
+    stays in the model's ``coefficients[0]``), ``n`` :func:`varimp.garson`, ``m`` :func:`varimp.evimp` as p x 3 (nsubsets,
+    gcv, rss), ``r`` the forest's ``.importance`` (p x 2: raw %IncMSE, IncNodePurity; :func:`models.rf_importance_many`)
+    and ``v`` :func:`varimp.ksvm_contributions`.  The forest's permutation seeds come from
+    ``default_rng([seed, 4, nfolds, 1])`` and the ksvm sample from ``default_rng([seed, 5, nfolds, 1])``: streams of
+    their own, so every other draw -- and every other entry of the result -- is the same bit for bit with and without it.
+
     Returns a dict: ``kfolds``, ``fold_models`` (per fold, label -> model), ``residuals`` (hold-out rows x members in
-    play), ``p`` (the optimiser's end point), ``labels`` (the kept ones), and ``models`` / ``weights`` / ``wt_total`` --
-    exactly a ``fitted[i]`` of :func:`mltps.mltps`."""
+    play), ``p`` (the optimiser's end point), ``labels`` (the kept ones), ``models`` / ``weights`` / ``wt_total`` --
+    exactly a ``fitted[i]`` of :func:`mltps.mltps` -- and, when asked for, ``var_imp``."""
     from . import models as _models
     X = np.ascontiguousarray(X, dtype=np.float64)
     resp = np.asarray(resp, dtype=np.float64)
@@ -222,8 +230,28 @@ def fit_layer(X, resp, kfolds=None, seed=0, smooth_only=False, nfolds=10, gbm_fo
             sig = ksvm.get("sigma")
             m = _models.ksvm_fit_many([X], [resp], sig if sig is None or np.ndim(sig) == 0 else None, [gen])[0]
         final.append(m)
-    return {"kfolds": kfolds, "fold_models": fold_models, "residuals": residuals, "p": p_opt, "labels": kept, "models": final,
-            "weights": wts, "wt_total": tot}
+    out = {"kfolds": kfolds, "fold_models": fold_models, "residuals": residuals, "p": p_opt, "labels": kept, "models": final,
+           "weights": wts, "wt_total": tot}
+    if var_imp:
+        out["var_imp"] = {lab: _member_var_imp(lab, m, X, resp, [int(seed), _MEMBER[lab], nf, 1]) for lab, m in zip(kept, final)}
+    return out
+
+
+def _member_var_imp(lab, m, X, resp, gen):
+    """the $var.imp entry of one final model (V73:465 ... 602); ``gen`` seeds what the entry draws"""
+    from . import models as _models, varimp
+    if lab == "b":
+        return m.contributions()[0]
+    if lab == "g":
+        return m.coefficients[1:].copy()
+    if lab == "n":
+        return varimp.garson(m.wts, m.p, (m.wts.size - 1) // (m.p + 2))
+    if lab == "m":
+        return np.column_stack(varimp.evimp(m, m.p)[:3]).astype(np.float64)
+    if lab == "r":
+        seeds = np.random.default_rng(gen).integers(0, 2 ** 64, size=m.n_trees, dtype=np.uint64)
+        return _models.rf_importance_many([m], [X], [resp], perm_seeds=[seeds])[0].importance
+    return varimp.ksvm_contributions(m, X, seed=gen)
 
 
 def cv_residuals(fold_models, X, resp, kfolds, labels: str = ORDER_ALL):

@@ -218,7 +218,7 @@ def mltps(stack: RasterStack, int_values, fitted, tps: bool = True, tile_edge: i
     table as an array (columns long, lat, then one response column per layer, V73:120-154); ``fitted[i]`` holds
     layer i's ``models`` (device models in ``mods.run`` order), ``weights`` (rounded kept weights) and ``wt_total``
     (V73:337-392).  Returns the list ``omega``: one :func:`mltps_predict` result per layer plus ``n_layers``
-    (V73:955) -- Step 1 (fitting, CV, weight search) happens before this call: in R, or by :func:`cv.fit_layer`, whose
+    (V73:955) and, where ``fitted[i]`` carries one, its ``var_imp`` -- Step 1 (fitting, CV, weight search) happens before this call: in R, or by :func:`cv.fit_layer`, whose
     result for layer i IS a ``fitted[i]``."""
     int_values = np.asarray(int_values, dtype=np.float64)
     n_layers = int_values.shape[1] - 2
@@ -232,5 +232,7 @@ def mltps(stack: RasterStack, int_values, fitted, tps: bool = True, tile_edge: i
             out = mltps_predict(stack, int_values[:, :2], int_values[:, 2 + i], f["models"], f["weights"], f["wt_total"],
                                 tps=tps, tile_edge=tile_edge, lambda_=lambda_, gcv_mode=gcv_mode, keep=keep)
             out["n_layers"] = n_layers
+            if "var_imp" in f:       # cv.fit_layer(var_imp = True): the layer's $var.imp (V73:465 ... 602)
+                out["var_imp"] = f["var_imp"]
             omega.append(out)
     return omega

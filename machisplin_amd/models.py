@@ -7,6 +7,7 @@ arithmetic runs in libmachisplin_hip.so; there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -439,7 +440,8 @@ class Gbm(Model):
         tree t is grown on; ``None`` draws ``floor(bag_fraction * n)`` rows per tree without replacement from
         ``numpy.random.default_rng(seed)`` -- NOT R's RNG stream, so the trees are gbm's for these bags, not for
         R's ``set.seed``.  The object carries ``.params`` (the ``kind = "gbm"`` dict of :func:`from_param_dict`),
-        ``.fit`` (the model's value on the training rows) and ``.init_f``."""
+        ``.fit`` (the model's value on the training rows), ``.init_f`` and ``.error_reduction`` (node-aligned with
+        ``params["split_var"]``: the improvement every split node won with, gbm's ErrorReduction; 0 at terminals)."""
         return gbm_fit_many([X], [y], n_trees, None if bags is None else [bags], seed, interaction_depth, shrinkage,
                             bag_fraction, n_minobsinnode)[0]
 
@@ -447,6 +449,30 @@ class Gbm(Model):
         """gbm::gbm.more(model, n_trees) (V73:1908): a NEW model with n_trees further trees grown from this one's
         ``.fit``; bags as in :meth:`fit` (``None`` continues this model's generator)."""
         return gbm_more_many([self], n_trees, None if bags is None else [bags])[0]
+
+    def relative_influence(self, n_trees=None) -> np.ndarray:
+        """gbm's ``relative.influence(model, n.trees)``: per variable, the sum of ``.error_reduction`` over the split nodes
+        of the first ``n_trees`` trees (all of them by default) that test it, added in tree order and then node order."""
+        red = getattr(self, "error_reduction", None)
+        if red is None:
+            raise ValueError("relative influence needs a model grown by Gbm.fit / gbm_fit_many")
+        n_trees = self.n_trees if n_trees is None else int(n_trees)
+        if not 0 <= n_trees <= self.n_trees:
+            raise ValueError("n_trees must lie in 0 .. %d" % self.n_trees)
+        end = int(self.params["tree_offsets"][n_trees])
+        var = np.asarray(self.params["split_var"][:end])
+        out = np.zeros(self.p)
+        np.add.at(out, var[var >= 0], red[:end][var >= 0])          # unbuffered: one addition per node, in node order
+        return out
+
+    def contributions(self):
+        """``summary.gbm``'s rel.inf, what the reference stores as the member's $var.imp (V73:495; V73:2115, V73:2210):
+        ``(100 * relative_influence() / its sum, the variables in descending order of it)`` -- the first array in
+        VARIABLE order, ties of the order to the lower index.  All zeros when no tree has a split."""
+        ri = self.relative_influence()
+        tot = float(ri.sum())
+        rel = 100.0 * ri / tot if tot > 0.0 else np.zeros(self.p)
+        return rel, np.argsort(-rel, kind="stable")
 
 
 def _gbm_bags(bags, rngs, ns, n_trees, bag_fraction):
@@ -464,7 +490,8 @@ def _gbm_bags(bags, rngs, ns, n_trees, bag_fraction):
 
 
 def _gbm_grow(Xs, ys, Fs, bags, n_trees, depth, minobs, shrinkage):
-    """mhs_gbm_grow_many; Fs None = the first call.  Returns per model (F, init_f, offsets, var, val, left, right, missing)."""
+    """mhs_gbm_grow_many_reduction; Fs None = the first call.  Returns per model (F, init_f, offsets, var, val, left, right,
+    missing, error_reduction)."""
     count = len(Xs)
     p = Xs[0].shape[1]
     cap = n_trees * (3 * depth + 1)
@@ -474,22 +501,24 @@ def _gbm_grow(Xs, ys, Fs, bags, n_trees, depth, minobs, shrinkage):
     off = [np.zeros(n_trees + 1, dtype=np.int64) for _ in range(count)]
     var, left, right, miss = ([np.zeros(cap, dtype=np.int32) for _ in range(count)] for _ in range(4))
     val = [np.zeros(cap) for _ in range(count)]
+    red = [np.zeros(cap) for _ in range(count)]
     ns = _i64([X.shape[0] for X in Xs])
     bs = _i64([b.shape[1] for b in bags])
     _lib.init()
-    _lib.check(_lib.lib().mhs_gbm_grow_many(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, _ptrs(bags), bs.ctypes.data, int(n_trees),
-                                            int(depth), int(minobs), float(shrinkage), int(first), _ptrs(Fs), init.ctypes.data,
-                                            _ptrs(off), _ptrs(var), _ptrs(val), _ptrs(left), _ptrs(right), _ptrs(miss)))
+    _lib.check(_lib.lib().mhs_gbm_grow_many_reduction(count, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, _ptrs(bags), bs.ctypes.data,
+                                                      int(n_trees), int(depth), int(minobs), float(shrinkage), int(first), _ptrs(Fs),
+                                                      init.ctypes.data, _ptrs(off), _ptrs(var), _ptrs(val), _ptrs(left), _ptrs(right),
+                                                      _ptrs(miss), _ptrs(red)))
     out = []
     for k in range(count):
         nn = int(off[k][-1])
-        out.append((Fs[k], float(init[k]), off[k], var[k][:nn], val[k][:nn], left[k][:nn], right[k][:nn], miss[k][:nn]))
+        out.append((Fs[k], float(init[k]), off[k], var[k][:nn], val[k][:nn], left[k][:nn], right[k][:nn], miss[k][:nn], red[k][:nn]))
     return out
 
 
-def _gbm_object(params, F, state):
+def _gbm_object(params, F, state, red):
     m = from_param_dict(params)
-    m.params, m.fit, m.init_f, m._grow = params, F, params["init_f"], state
+    m.params, m.fit, m.init_f, m._grow, m.error_reduction = params, F, params["init_f"], state, red
     return m
 
 
@@ -503,12 +532,12 @@ def gbm_fit_many(Xs, ys, n_trees, bags=None, seed=0, interaction_depth=25, shrin
     bags = _gbm_bags(bags, rngs, [X.shape[0] for X in Xs], int(n_trees), bag_fraction)
     res = _gbm_grow(Xs, ys, None, bags, int(n_trees), interaction_depth, n_minobsinnode, shrinkage)
     out = []
-    for k, (F, init_f, off, var, val, left, right, miss) in enumerate(res):
+    for k, (F, init_f, off, var, val, left, right, miss, red) in enumerate(res):
         params = {"kind": "gbm", "init_f": init_f, "tree_offsets": off, "split_var": var, "split_val": val, "left": left,
                   "right": right, "missing": miss, "p": Xs[k].shape[1]}
         state = {"X": Xs[k], "y": ys[k], "rng": rngs[k], "depth": interaction_depth, "minobs": n_minobsinnode,
                  "shrinkage": shrinkage, "bag_fraction": bag_fraction}
-        out.append(_gbm_object(params, F, state))
+        out.append(_gbm_object(params, F, state, red))
     return out
 
 
@@ -526,14 +555,29 @@ def gbm_more_many(models, n_trees, bags=None):
     res = _gbm_grow([s["X"] for s in st], [s["y"] for s in st], [m.fit for m in models], bags, int(n_trees), st[0]["depth"],
                     st[0]["minobs"], st[0]["shrinkage"])
     out = []
-    for m, s, (F, _, off, var, val, left, right, miss) in zip(models, st, res):
+    for m, s, (F, _, off, var, val, left, right, miss, red) in zip(models, st, res):
         q = m.params
         params = {"kind": "gbm", "init_f": q["init_f"], "tree_offsets": np.concatenate([q["tree_offsets"], q["tree_offsets"][-1] + off[1:]]),
                   "split_var": np.concatenate([q["split_var"], var]), "split_val": np.concatenate([q["split_val"], val]),
                   "left": np.concatenate([q["left"], left]), "right": np.concatenate([q["right"], right]),
                   "missing": np.concatenate([q["missing"], miss]), "p": q["p"]}
-        out.append(_gbm_object(params, F, s))
+        out.append(_gbm_object(params, F, s, np.concatenate([m.error_reduction, red])))
     return out
+
+
+class _ImportanceTable(np.ndarray):
+    """What :func:`rf_importance_many` stores as ``model.importance``: the p x 2 array.  The attribute takes the place of
+    the method :meth:`RandomForest.importance` on that model, so the array can still be called like it."""
+    _model = None
+
+    def __array_finalize__(self, obj):
+        self._model = getattr(obj, "_model", None)
+
+    def __call__(self, X, y, inbag=None, perm_seeds=None, n_perm=1, seed=0):
+        m = self._model() if self._model is not None else None
+        if m is None:
+            raise ReferenceError("this importance table has outlived its forest: call RandomForest.importance on a live model")
+        return RandomForest.importance(m, X, y, inbag, perm_seeds, n_perm, seed)
 
 
 class RandomForest(Model):
@@ -552,28 +596,39 @@ class RandomForest(Model):
         super().__init__(h, p)
 
     @classmethod
-    def fit(cls, X, y, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0) -> "RandomForest":
+    def fit(cls, X, y, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0, importance=False, n_perm=1,
+            perm_seeds=None) -> "RandomForest":
         """randomForest::randomForest(mod.form, data = train) (V73:248 per CV fold, V73:517 the final model) with the
         package's regression defaults (ntree = 500, mtry = max(floor(p / 3), 1), nodesize = 5, bootstrap of n rows with
         replacement), grown on the device (mhs_rf_fit_many, a workgroup per tree).  ``inbag``: (n_trees, n) int32, how
         many times row i is in tree t's bootstrap; ``None`` draws n rows with replacement per tree from
         ``numpy.random.default_rng(seed)``.  ``seeds``: one uint64 per tree, driving the per-node variable draw;
         ``None`` draws them from the same generator (after the bags).  NOT R's RNG stream: the forest is randomForest's
-        for these bags and draws, not for R's ``set.seed``; the random tie-break of recent randomForest releases and
-        permutation importance are not reproduced (include/machisplin_hip.h).  The object carries ``.params`` (the
+        for these bags and draws, not for R's ``set.seed``; the random tie-break of recent randomForest releases is not
+        reproduced (include/machisplin_hip.h).  ``importance = True`` (randomForest's ``importance = TRUE``, V73:517-519)
+        runs :func:`rf_importance_many` on the fitted forest with ``n_perm`` permutations per tree and variable and the
+        permutation seeds ``perm_seeds`` (``None``: a stream of their own, see there).  The object carries ``.params`` (the
         ``kind = "rf"`` dict of :func:`from_param_dict`), ``.oob_pred`` / ``.oob_count`` (the out-of-bag mean of every
         row, NaN where no tree left it out), ``.mse`` and ``.rsq`` (mean squared OOB error and
         ``1 - mse / mean((y - mean(y))^2)`` over the rows with ``oob_count > 0``), ``.inc_node_purity`` (IncNodePurity),
         ``.inbag`` and ``.seeds``."""
         return rf_fit_many([X], [y], n_trees, mtry, nodesize, None if inbag is None else [inbag],
-                           None if seeds is None else [seeds], seed)[0]
+                           None if seeds is None else [seeds], seed, importance, n_perm, None if perm_seeds is None else [perm_seeds])[0]
+
+    def importance(self, X, y, inbag=None, perm_seeds=None, n_perm=1, seed=0) -> np.ndarray:
+        """:func:`rf_importance_many` for this forest on its training rows: sets and returns ``.importance`` (which, an
+        instance attribute from then on, stays callable with these arguments)."""
+        rf_importance_many([self], [X], [y], None if inbag is None else [inbag], None if perm_seeds is None else [perm_seeds], n_perm, seed)
+        return self.importance
 
 
-def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0):
+def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=None, seed=0, importance=False, n_perm=1,
+                perm_seeds=None):
     """:meth:`RandomForest.fit` for several forests (each its own rows, bags and seeds; the same p, n_trees, mtry and
     nodesize) in ONE device call: the shape of the ten fold forests of V73:248.  ``inbag`` / ``seeds``: one array per
     model; ``seed``: an int (model k draws from ``default_rng([seed, k])``; a single model from ``default_rng(seed)``) or
-    one per model."""
+    one per model.  ``importance``: one more device call, :func:`rf_importance_many` ``(models, Xs, ys, n_perm = n_perm,
+    perm_seeds = perm_seeds, seed = seed)``, after the fit; the bags and the draw seeds are the same with and without it."""
     Xs, ys = _fit_inputs(Xs, ys)
     count, p, n_trees = len(Xs), Xs[0].shape[1], int(n_trees)
     mtry = max(p // 3, 1) if mtry is None else int(mtry)
@@ -624,7 +679,63 @@ def rf_fit_many(Xs, ys, n_trees=500, mtry=None, nodesize=5, inbag=None, seeds=No
         var = float(np.mean(dy * dy)) if seen.any() else 0.0
         m.rsq = 1.0 - m.mse / var if var > 0.0 else float("nan")
         out.append(m)
+    if importance:
+        rf_importance_many(out, Xs, ys, None, perm_seeds, n_perm, gen)
     return out
+
+
+_IMPORTANCE_STREAM = 1 << 20       # the last word of the permutation seeds' stream: no fit stream [seed, k] ends in it (k < 65536)
+
+
+def rf_importance_many(models, Xs, ys, inbag=None, perm_seeds=None, n_perm=1, seed=0):
+    """randomForest's permutation importance (``importance = TRUE``: ``$importance[, "%IncMSE"]`` and ``$importanceSD``,
+    what the reference stores as the forest's $var.imp, V73:517-519) of several forests -- any :class:`RandomForest`,
+    loaded or fitted here; the same p and number of trees -- on their training rows, in ONE device call, a workgroup per
+    tree (mhs_rf_importance_many; the rule is stated in include/machisplin_hip.h).  ``inbag``: one (n_trees, n) array of
+    in-bag counts per model, as in the fit; ``None`` takes each model's ``.inbag`` (set when it was fitted here).
+    ``perm_seeds``: one array of n_trees uint64 per model; ``None`` draws model k's from
+    ``default_rng([*g_k, 2 ** 20])`` with ``g_k`` as :func:`_fit_generators` derives it from ``seed`` -- a stream of its
+    own, NOT R's: the fit's bags and draw seeds are what they are without this call.  ``n_perm``: permutations per tree
+    and variable (randomForest's ``nPerm``), 1 .. 16.
+
+    Every model gains ``.importance`` (p x 2: the RAW ``%IncMSE`` as ``$importance`` holds it -- not divided by its SD --
+    and ``IncNodePurity``, NaN for a forest that was not fitted here), ``.importance_sd`` (``$importanceSD``),
+    ``.tree_delta`` (n_trees x p, every tree's increase) and ``.perm_seeds``.  Returns the models."""
+    models = list(models)
+    Xs, ys = _fit_inputs(Xs, ys)
+    count, p = len(Xs), Xs[0].shape[1]
+    if len(models) != count or any(not isinstance(m, RandomForest) for m in models):
+        raise ValueError("need one RandomForest per predictor matrix")
+    lib = _lib.lib()
+    nt = C.c_int64()
+    _lib.check(lib.mhs_model_info(models[0]._h, None, None, C.byref(nt)))
+    n_trees = int(nt.value)
+    if inbag is None:
+        if any(getattr(m, "inbag", None) is None for m in models):
+            raise ValueError("a forest that was not fitted here needs its inbag counts")
+        inbag = [m.inbag for m in models]
+    bags = [_i32(b) for b in inbag]
+    if len(bags) != count or any(b.shape != (n_trees, X.shape[0]) for b, X in zip(bags, Xs)):
+        raise ValueError("inbag must hold one n_trees x n array of in-bag counts per model")
+    if perm_seeds is None:
+        sds = [np.random.default_rng(np.atleast_1d(g).tolist() + [_IMPORTANCE_STREAM]).integers(0, 2 ** 64, size=n_trees, dtype=np.uint64)
+               for g in _fit_generators(seed, count)]
+    else:
+        sds = [np.ascontiguousarray(np.asarray(s, dtype=np.uint64)) for s in perm_seeds]
+        if len(sds) != count or any(s.shape != (n_trees,) for s in sds):
+            raise ValueError("perm_seeds must hold one uint64 per tree and model")
+    inc, sd = [np.empty(p) for _ in Xs], [np.empty(p) for _ in Xs]
+    delta = [np.empty((n_trees, p)) for _ in Xs]
+    ns = _i64([X.shape[0] for X in Xs])
+    hs = (C.c_void_p * count)(*[m._h for m in models])
+    _lib.check(lib.mhs_rf_importance_many(count, hs, _ptrs(Xs), _ptrs(ys), ns.ctypes.data, p, _ptrs(bags), _ptrs(sds), int(n_perm),
+                                          _ptrs(inc), _ptrs(sd), _ptrs(delta)))
+    for k, m in enumerate(models):
+        pur = getattr(m, "inc_node_purity", None)
+        m.importance = np.column_stack([inc[k], np.full(p, np.nan) if pur is None else pur]).view(_ImportanceTable)
+        m.importance._model = weakref.ref(m)
+        m.importance_sd, m.tree_delta, m.perm_seeds = sd[k], delta[k], sds[k]
+    return models
 
 
 def from_param_dict(m: dict) -> Model:
