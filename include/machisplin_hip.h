@@ -194,12 +194,33 @@ MHS_API int mhs_tps_predict_points(const mhs_tps *t, const double *xy, int64_t n
  *     var(x) = rho phi(0) - 2 rho k(x)'a(x) + a(x)' (rho K + sigma^2 W^-1) a(x),   f^(x) = a(x)' yM ,
  * which for rho = sigma^2 / lambda (fields' own MLE pair satisfies shat.MLE^2 = lambda rho.MLE) is exactly
  *     var(x) = -(sigma^2 / lambda) z(x)' M^-1 z(x),  M = [[K + lambda W^-1, T], [T', 0]],  z(x) = [phi(|u - u_j|^2)_j; 1; u; v];
- * the SE is sqrt(max(var, 0)).  M^-1 is built once per spline on the host (O(n^3)) and kept in the handle, so SE needs a
- * spline of at most MHS_TPS_SE_MAX_N distinct stations (MHS_ERR_INVALID above it).  sigma2 = NaN takes the fit's own
+ * the SE is sqrt(max(var, 0)).  M^-1 is built once per spline (O(n^3)) and kept in the handle; by default SE needs a
+ * spline of at most MHS_TPS_SE_MAX_N distinct stations (MHS_ERR_INVALID above it; see mhs_tps_se_max_n below).
+ * sigma2 = NaN takes the fit's own
  *     sigma^2 hat = (RSS_w(lambda) + pure_ss) / (N - eff_df),  RSS_w = sum_i w_i (yM_i - f^(xM_i))^2
  * (fields' shat.GCV^2); to reproduce predictSE of a real fields object pass sigma2 = fit$best.model[2].  A handle of
  * mhs_tps_from_coef has no observations: its weights are taken as 1 and sigma2 must be given (NaN => MHS_ERR_INVALID). */
 #define MHS_TPS_SE_MAX_N 2048
+/* Two process-wide settings and a report.  Neither setter needs an initialised device; a setting applies to every Q built
+ * after it, a handle keeps the Q it already has.
+ *   mhs_tps_se_max_n      the largest number of distinct stations SE accepts: 1 .. MHS_TPS_SE_HARD_MAX_N (MHS_ERR_INVALID
+ *                         outside), default MHS_TPS_SE_MAX_N; *previous (may be NULL) receives the value it replaces.  The
+ *                         refusal message names the limit in force.
+ *   mhs_tps_se_build_mode where Q = -M^-1 is built: AUTO = on the host up to MHS_TPS_SE_MAX_N distinct stations (the bits
+ *                         of every earlier release; the tiles of mhs_tps_surface_se side by side on host threads) and on
+ *                         the device above; HOST; DEVICE (blocked MFMA Cholesky, triangular inverse and X = L^-T L^-1 on
+ *                         the device, nothing of order n^2 crosses the bus; builds on one device run one after the other).
+ *                         Q needs 8 (n + 3)^2 bytes and the device build three times that while it runs: 9.6 GB at
+ *                         n = 20 000, the largest fit the test suite exercises and therefore the hard limit.
+ *   mhs_tps_se_info       what a handle holds: where its Q was built (MHS_SE_BUILD_HOST / _DEVICE), the build's wall time
+ *                         and Q's bytes (any pointer may be NULL).  MHS_ERR_INVALID for a handle that has no Q yet. */
+#define MHS_TPS_SE_HARD_MAX_N 20000
+MHS_API int mhs_tps_se_max_n(int64_t max_n, int64_t *previous);
+#define MHS_SE_BUILD_AUTO 0
+#define MHS_SE_BUILD_HOST 1
+#define MHS_SE_BUILD_DEVICE 2
+MHS_API int mhs_tps_se_build_mode(int mode);
+MHS_API int mhs_tps_se_info(const mhs_tps *t, int *built_on, double *build_ms, int64_t *q_bytes);
 /* sigma^2 hat of the fit (above); MHS_ERR_INVALID for a mhs_tps_from_coef handle */
 MHS_API int mhs_tps_sigma2(const mhs_tps *t, double *sigma2);
 /* predictSE.Krig(fit, xy): xy n x 2 column-major, SE of each point into out_host[n] */
@@ -610,7 +631,8 @@ MHS_API int mhs_tps_surface_dev(const mhs_grid *g, const double *xy, const doubl
  * mhs_mosaic_feather_dev).  A linear blend of SEs with non-negative weights is the SE of the blended estimate if the
  * tiles' errors were perfectly correlated, and an upper bound on it otherwise.  A zero tile (fewer than 10 stations,
  * V73:710-721) has no spline, so its SE is NaN, and a cell that only zero tiles cover is NaN.  One tile or
- * tile_edge <= 0: the global fit's SE (at most MHS_TPS_SE_MAX_N distinct stations).  Blocks until done.
+ * tile_edge <= 0: the global fit's SE (at most MHS_TPS_SE_MAX_N distinct stations unless mhs_tps_se_max_n raises the
+ * limit).  Blocks until done.
  * mhs_tps_surface_se: the same plane into a host buffer (as mhs_tps_surface). */
 MHS_API int mhs_tps_surface_se(const mhs_grid *g, const double *xy, const double *resid, int64_t n,
                                const double *cov1_at_stations, int64_t tile_edge, double lambda, int gcv_mode,

@@ -84,10 +84,17 @@ mhs_interpolate <- function(r, object) {
 }
 # fields::predictSE(fit, x) for the GPU handle: var = (sigma2 / lambda) z' (-M^-1) z, i.e. predictSE.Krig with
 # rho = sigma2 / lambda.  sigma2 = NA takes the fit's own sigma^2 hat (fields' shat.GCV^2, mhs_tps_sigma2()); to
-# reproduce predictSE of a real fields object pass sigma2 = fit$best.model[2].  At most 2048 distinct stations.
+# reproduce predictSE of a real fields object pass sigma2 = fit$best.model[2].  At most 2048 distinct stations unless
+# mhs_tps_se_max_n() raises the limit (up to 20000): above 2048, Q = -M^-1 is built on the device.
 predictSE.machisplin_tps <- function(object, x, sigma2 = NA, ...)
   .Call("mhsr_tps_predict_se_points", object$handle, as.matrix(x), as.numeric(sigma2))
 mhs_tps_sigma2 <- function(object) .Call("mhsr_tps_sigma2", object$handle)
+# the limit on distinct stations (returns the previous one), and where Q is built: "auto" = host up to 2048, device above
+mhs_tps_se_max_n <- function(n) .Call("mhsr_tps_se_max_n", as.numeric(n))
+mhs_tps_se_build_mode <- function(mode = c("auto", "host", "device")) {
+  mode <- match.arg(mode)
+  invisible(.Call("mhsr_tps_se_build_mode", match(mode, c("auto", "host", "device")) - 1L))
+}
 # terra::interpolate(r, fit, fun = predictSE): the SE at every cell centre of r
 mhs_interpolate_se <- function(r, object, sigma2 = NA) {
   v <- .Call("mhsr_tps_predict_se_grid", object$handle, .mhs_geom(r), c(0L, nrow(r), 0L, ncol(r)), as.numeric(sigma2))

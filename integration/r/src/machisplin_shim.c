@@ -31,6 +31,14 @@ SEXP mhsr_init(SEXP device) { chk(mhs_init(Rf_asInteger(device))); return R_NilV
 /* 0 = by cost (default), 1 = direct sum (predict.Krig's own loop; bit-identical across windows), 2 = far-field-
    interpolated sum; see mhs_tps_eval_mode in machisplin_hip.h */
 SEXP mhsr_tps_eval_mode(SEXP mode) { chk(mhs_tps_eval_mode(Rf_asInteger(mode))); return R_NilValue; }
+/* the standard errors' limit on distinct stations (returns the value it replaces) and where Q = -M^-1 is built
+   (0 auto, 1 host, 2 device); see mhs_tps_se_max_n / mhs_tps_se_build_mode in machisplin_hip.h */
+SEXP mhsr_tps_se_max_n(SEXP n) {
+    int64_t prev = 0;
+    chk(mhs_tps_se_max_n((int64_t)Rf_asReal(n), &prev));
+    return Rf_ScalarReal((double)prev);
+}
+SEXP mhsr_tps_se_build_mode(SEXP mode) { chk(mhs_tps_se_build_mode(Rf_asInteger(mode))); return R_NilValue; }
 
 /* fields::Tps(x, Y)  (V73:722, V73:751).  xy: n x 2 numeric matrix, lambda NA => GCV */
 SEXP mhsr_tps_fit(SEXP xy, SEXP y, SEXP lambda, SEXP mode) {

@@ -100,6 +100,9 @@ SIGNATURES = {
     "mhs_tps_predict_rows_dev": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "mhs_tps_predict_points": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mhs_tps_sigma2": (C.c_int, [_vp, _dp]),
+    "mhs_tps_se_max_n": (C.c_int, [_i64, C.POINTER(_i64)]),
+    "mhs_tps_se_build_mode": (C.c_int, [C.c_int]),
+    "mhs_tps_se_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "mhs_tps_predict_se_points": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp]),
     "mhs_tps_predict_se_grid": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_double, _vp]),
     "mhs_tps_predict_se_grid_dev": (C.c_int, [_vp, C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp]),

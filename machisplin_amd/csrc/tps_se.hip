@@ -6,9 +6,10 @@
 //     var(x) = rho phi(0) - 2 rho k(x)'a(x) + a(x)' (rho K + sigma^2 W^-1) a(x)
 // reduces, for rho = sigma^2 / lambda (fields' MLE pair satisfies it), to
 //     var(x) = (sigma^2 / lambda) z(x)' Q z(x),   Q = -M^-1 .
-// Q does not depend on the data or on sigma^2: it is built once per spline on the host (O(n^3), block formula on the
-// fit's own weighted QR, below) and kept on the device in the handle.  Per cell the work is one quadratic form with a
-// fixed (n+3)^2 matrix: a batched GEMM  Z_block Q  (v_mfma_f64_16x16x4f64) followed by a row-wise dot with Z_block.
+// Q does not depend on the data or on sigma^2: it is built once per spline (O(n^3), block formula on the fit's own
+// weighted QR: on the host, below, or on the device, tps_se_build.hip -- mhs_tps_se_build_mode) and kept on the device
+// in the handle.  Per cell the work is one quadratic form with a fixed (n+3)^2 matrix: a batched GEMM  Z_block Q
+// (v_mfma_f64_16x16x4f64) followed by a row-wise dot with Z_block.
 //
 // Kernel layout (tps_se_kernel): a workgroup = 4 waves = 128 cells of one window (a wave owns two 16-cell tiles).
 // The columns of Q are walked in chunks of 64; for each chunk the rows of Q stream through LDS in slabs of 16 x 64
@@ -26,6 +27,7 @@
 #include "common.h"
 #include "devmath.h"
 #include "tps_host.h"
+#include "tps_se.h"
 
 namespace mhs {
 
@@ -35,7 +37,6 @@ constexpr int SE_CELLS = SE_WAVES * SE_CT * 16;    // cells per workgroup
 constexpr int SE_JB = 4;                           // 16-column tiles per chunk of Q
 constexpr int SE_KS = 16;                          // rows of Q per LDS slab
 constexpr int SE_LD = 80;                          // LDS row stride (doubles): consecutive rows 128 B apart in the banks
-constexpr double PHI_K = 0.5 / (8.0 * M_PI);       // fields' radial constant, folded into Q
 
 // one window (or one point set) of one spline
 struct SeWindow {
@@ -191,16 +192,11 @@ __global__ __launch_bounds__(64 * SE_WAVES) __attribute__((amdgpu_waves_per_eu(2
         }
 }
 
-// ------------------------------------------------------------------------------------------------ Q on the host --
-struct SeState {
-    int64_t n = 0, np = 0;
-    double lambda = 0;
-    double sigma2 = NAN;        // sigma^2 hat (NaN without observations)
-    double eff_df = NAN, rss_w = NAN;
-    double *q_dev = nullptr;
-    double build_ms = 0;
-};
+// process-wide settings (mhs_tps_se_max_n, mhs_tps_se_build_mode): they apply to every Q built after them
+static std::atomic<int64_t> g_se_max_n{MHS_TPS_SE_MAX_N};
+static std::atomic<int> g_se_build_mode{MHS_SE_BUILD_AUTO};
 
+// ------------------------------------------------------------------------------------------------ Q on the host --
 void se_state_free(SeState *s) {
     if (!s) return;
     pool_release(s->q_dev);
@@ -397,9 +393,10 @@ static int se_state(const mhs_tps *t, int threads, const SeState **out) {
     mhs_tps *tm = const_cast<mhs_tps *>(t);
     std::lock_guard<std::mutex> lk(tm->mu);
     if (!tm->se) {
-        if (t->n > MHS_TPS_SE_MAX_N) {
+        const int64_t max_n = g_se_max_n.load();
+        if (t->n > max_n) {
             set_error("mhs_tps_predict_se: %lld distinct stations; standard errors are limited to %d (Q = -M^-1 is dense, "
-                      "O(n^2) per cell)", (long long)t->n, (int)MHS_TPS_SE_MAX_N);
+                      "O(n^2) per cell)", (long long)t->n, (int)max_n);
             return MHS_ERR_INVALID;
         }
         if (!(t->lambda > 0)) {
@@ -407,11 +404,18 @@ static int se_state(const mhs_tps *t, int threads, const SeState **out) {
             return MHS_ERR_INVALID;
         }
         SeState *s = new SeState();
-        std::vector<double> Qh;
-        if (int rc = se_build(t, threads, Qh, *s)) { delete s; return rc; }
-        s->q_dev = (double *)pool_alloc(sizeof(double) * Qh.size());
-        if (!s->q_dev) { delete s; return MHS_ERR_ALLOC; }
-        if (int rc = h2d_sync(s->q_dev, Qh.data(), sizeof(double) * Qh.size())) { se_state_free(s); return rc; }
+        // AUTO: the host build -- the bits every earlier release gave -- up to the default limit, the device build above it
+        const int mode = g_se_build_mode.load();
+        if (mode == MHS_SE_BUILD_DEVICE || (mode == MHS_SE_BUILD_AUTO && t->n > MHS_TPS_SE_MAX_N)) {
+            if (int rc = se_build_device(t, *s)) { delete s; return rc; }
+        } else {
+            std::vector<double> Qh;
+            if (int rc = se_build(t, threads, Qh, *s)) { delete s; return rc; }
+            s->built_on = MHS_SE_BUILD_HOST;
+            s->q_dev = (double *)pool_alloc(sizeof(double) * Qh.size());
+            if (!s->q_dev) { delete s; return MHS_ERR_ALLOC; }
+            if (int rc = h2d_sync(s->q_dev, Qh.data(), sizeof(double) * Qh.size())) { se_state_free(s); return rc; }
+        }
         tm->se = s;
     }
     *out = tm->se;
@@ -515,7 +519,7 @@ static int surface_se_tiles(const mhs_grid *g, const double *xy, const double *r
             set_error("mhs_tps_surface_se_dev: the spline of tile %lld could not be fitted", (long long)todo[(size_t)q]);
             return status[(size_t)q] ? status[(size_t)q] : MHS_ERR_NUMERIC;
         }
-    // Q of every tile on the host threads, the tiles side by side
+    // Q of every tile from the host threads: host builds run side by side, device builds (MHS_SE_BUILD_DEVICE) one after the other
     std::vector<const SeState *> st((size_t)nf, nullptr);
     std::vector<int> rcs((size_t)nf, MHS_OK);
     std::vector<std::string> errs((size_t)nf);
@@ -571,6 +575,30 @@ static int surface_se_tiles(const mhs_grid *g, const double *xy, const double *r
 using namespace mhs;
 
 extern "C" {
+
+int mhs_tps_se_max_n(int64_t max_n, int64_t *previous) {
+    MHS_REQUIRE(max_n >= 1 && max_n <= MHS_TPS_SE_HARD_MAX_N, "max_n must lie in 1 .. MHS_TPS_SE_HARD_MAX_N");
+    const int64_t prev = g_se_max_n.exchange(max_n);
+    if (previous) *previous = prev;
+    return MHS_OK;
+}
+
+int mhs_tps_se_build_mode(int mode) {
+    MHS_REQUIRE(mode == MHS_SE_BUILD_AUTO || mode == MHS_SE_BUILD_HOST || mode == MHS_SE_BUILD_DEVICE, "mode must be 0, 1 or 2");
+    g_se_build_mode.store(mode);
+    return MHS_OK;
+}
+
+int mhs_tps_se_info(const mhs_tps *t, int *built_on, double *build_ms, int64_t *q_bytes) {
+    MHS_REQUIRE(t != nullptr, "NULL argument");
+    mhs_tps *tm = const_cast<mhs_tps *>(t);
+    std::lock_guard<std::mutex> lk(tm->mu);
+    MHS_REQUIRE(tm->se != nullptr, "this spline has no Q yet (no standard error has been asked of it)");
+    if (built_on) *built_on = tm->se->built_on;
+    if (build_ms) *build_ms = tm->se->build_ms;
+    if (q_bytes) *q_bytes = (int64_t)sizeof(double) * tm->se->np * tm->se->np;
+    return MHS_OK;
+}
 
 int mhs_tps_sigma2(const mhs_tps *t, double *sigma2) {
     if (int rc = require_ready()) return rc;

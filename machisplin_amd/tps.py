@@ -103,6 +103,13 @@ class Tps:
         _lib.check(_lib.lib().mhs_tps_predict_se_points(self._h, xy.ctypes.data, xy.shape[0], s2, out.ctypes.data))
         return out
 
+    def se_info(self) -> dict:
+        """What this handle's Q = -M^-1 is: ``built_on`` (SE_BUILD_HOST or SE_BUILD_DEVICE), ``build_ms`` (wall time of
+        the build) and ``q_bytes``.  Raises for a handle that has no Q yet (no standard error has been asked of it)."""
+        on, ms, nb = C.c_int(0), C.c_double(0.0), C.c_int64(0)
+        _lib.check(_lib.lib().mhs_tps_se_info(self._h, C.byref(on), C.byref(ms), C.byref(nb)))
+        return {"built_on": on.value, "build_ms": ms.value, "q_bytes": nb.value}
+
     def eval_plan(self):
         """(tile_cols, tile_rows, node_pairs, cell_pairs) of this handle's last grid evaluation; tile 0 x 0 means
         the direct sum ran."""
@@ -227,3 +234,21 @@ def eval_mode(mode: int) -> None:
     to FP64 rounding)."""
     _lib.init()
     _lib.check(_lib.lib().mhs_tps_eval_mode(int(mode)))
+
+
+SE_BUILD_AUTO, SE_BUILD_HOST, SE_BUILD_DEVICE = 0, 1, 2
+SE_MAX_N, SE_HARD_MAX_N = 2048, 20000
+
+
+def se_max_n(n: int) -> int:
+    """The largest number of distinct stations :meth:`Tps.predict_se` and :func:`interpolate_se` accept (default
+    SE_MAX_N, at most SE_HARD_MAX_N); returns the value it replaces.  Applies to every Q built afterwards."""
+    prev = C.c_int64(0)
+    _lib.check(_lib.load().mhs_tps_se_max_n(int(n), C.byref(prev)))
+    return prev.value
+
+
+def se_build_mode(mode: int) -> None:
+    """Where Q = -M^-1 of the standard errors is built: SE_BUILD_AUTO (host up to SE_MAX_N distinct stations, device
+    above), SE_BUILD_HOST or SE_BUILD_DEVICE.  A handle keeps the Q it already has."""
+    _lib.check(_lib.load().mhs_tps_se_build_mode(int(mode)))
