@@ -556,6 +556,49 @@ MHS_API int mhs_residual_points(const mhs_model *const *models, const double *we
 MHS_API int mhs_scale_add_dev(const double *a, double divisor, const double *b, double *out,
                               int64_t n, void *stream);
 
+/* ------------------------------------------------- MESS extrapolation map --
+ * replaces dismo::mess(covar.ras, dat_tps[[i]][, 1:n.covars], full = TRUE): the multivariate environmental similarity
+ * surface of Elith, Kearney & Phillips (2010) -- where the learners were asked to predict outside the data they were
+ * fitted on.  The reference does not call it; dismo is the package it copies kfold and gbm.step from.  THE RULE (this text is the specification; parity
+ * with dismo is not pinned):
+ *   Reference table: n_ref >= 2 rows x V variables, every value finite.  Per variable v the sorted values are
+ *   r_1 <= ... <= r_n, min = r_1, max = r_n > min.  For a cell value p (converted to double exactly from int16 / float32 /
+ *   float64):
+ *     i = #{j : r_j <= p}                              (R's findInterval, numpy's searchsorted(side = "right"))
+ *     f = (100.0 * i) / n
+ *     i == 0:   s = (100.0 * (p - min)) / (max - min)            negative
+ *     i == n:   s = (100.0 * (max - p)) / (max - min)            <= 0; a cell EQUAL to the largest station value gets 0
+ *     f <= 50 (equivalently 2 i <= n):  s = 2.0 * f
+ *     else:     s = 200.0 - 2.0 * f
+ *   MESS = min_v s_v; MoD ("most dissimilar variable") = the lowest v that attains the minimum, 0-based.  A cell with an NA
+ *   (NaN or the stack's nodata) in any of the V variables gets MESS = NaN and MoD = -1.  Negative MESS: at least one
+ *   variable is outside the stations' range.
+ * The operations are done in this order, each rounded once: the result equals a numpy restatement bit for bit.
+ * Variables: the C layers of the mhs_stack in layer order; when V == C + 2 also LONG and then LAT of the cell centre,
+ * x = xmin + (col + 0.5) * xres, y = ymax - (row + 0.5) * yres on ABSOLUTE grid indices (what every member kernel computes),
+ * so a window reproduces the whole-grid plane.
+ * mhs_mess_create sorts each column of ref (n_ref x n_vars column-major) on the host and keeps the sorted table on the
+ * device.  MHS_ERR_INVALID, with a message naming the row or the variable, for a non-finite entry (drop NA rows first,
+ * V73:154), n_ref < 2, n_vars < 1 (or > 2 048, or n_ref n_vars >= 2^31) and a constant variable; these checks come before
+ * the first device call.                                                                                              */
+typedef struct mhs_mess mhs_mess;
+MHS_API int mhs_mess_create(const double *ref /* n_ref x n_vars column-major */, int64_t n_ref, int n_vars, mhs_mess **out);
+MHS_API int mhs_mess_free(mhs_mess *m);
+/* The window [r0,r1) x [c0,c1) of grid g from DEVICE planes covering the whole grid: out_dev is (r1-r0) x ld row-major,
+ * mod_dev (may be NULL) the MoD plane, (r1-r0) x ld_mod int32.  Only enqueues on `stream`.  MHS_ERR_INVALID unless the
+ * table's n_vars is covars->n_layers or that + 2.  One pass: every plane element is read once, every output element
+ * written once (C sizeof(type) + 8 (+ 4) bytes per cell); no atomics, the same inputs give the same bits.            */
+MHS_API int mhs_mess_grid_dev(const mhs_mess *m, const mhs_grid *g, const mhs_stack *covars, int64_t r0, int64_t r1,
+                              int64_t c0, int64_t c1, double *out_dev, int64_t ld, int32_t *mod_dev, int64_t ld_mod,
+                              void *stream);
+/* same, host pointers: covars->data, out_host ((r1-r0) x (c1-c0)) and mod_host (may be NULL) on the host -- what the R
+ * shim hands over, with the layout of terra::values.  The planes go up in row bands; the call blocks until done.      */
+MHS_API int mhs_mess_grid(const mhs_mess *m, const mhs_grid *g, const mhs_stack *covars, int64_t r0, int64_t r1, int64_t c0,
+                          int64_t c1, double *out_host, int32_t *mod_host);
+/* rows of a table: X n x n_vars column-major (every variable given, LONG and LAT too when the table has them) -- the
+ * stations themselves, hold-out rows.  out_host[n]; mod_host[n] may be NULL.                                          */
+MHS_API int mhs_mess_points(const mhs_mess *m, const double *X, int64_t n, double *out_host, int32_t *mod_host);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

@@ -109,6 +109,21 @@ mhs_tps_surface_se <- function(rast_stack, dat, res.FINAL, n.covars, tile.edge =
   terra::setValues(terra::rast(rast_stack[[1]]), v)
 }
 
+# ---- where the learners extrapolate: dismo::mess(covar.ras, <the stations' covariates>, full = TRUE) ----------------------
+# The MESS extrapolation map (Elith, Kearney & Phillips 2010) of covar.ras against the stations of dat (a dat_tps[[i]]:
+# response, the covariates in columns 2 .. n.covars - 1, LONG and LAT in columns n.covars and n.covars + 1; n.covars =
+# nlyr(covar.ras) + 2 as at V73:123).  Returns a two-layer SpatRaster: "mess" (negative where at least one covariate is
+# outside the stations' range, NA where a covariate is NA) and "mod", the 1-based most dissimilar variable.  lonlat = TRUE
+# also places the cell centres' LONG and LAT among the stations' (variables n.covars - 1 and n.covars of "mod").
+mhs_mess <- function(covar.ras, dat, n.covars, lonlat = FALSE) {
+  ref <- as.matrix(dat[, 2:(if (lonlat) n.covars + 1 else n.covars - 1), drop = FALSE])
+  storage.mode(ref) <- "double"
+  v <- .Call("mhsr_mess_grid", ref, .mhs_geom(covar.ras), terra::values(covar.ras))
+  out <- c(terra::setValues(terra::rast(covar.ras[[1]]), v[[1]]),
+           terra::setValues(terra::rast(covar.ras[[1]]), ifelse(v[[2]] < 0L, NA_integer_, v[[2]] + 1L)))
+  names(out) <- c("mess", "mod")
+  out
+}
 
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half

@@ -210,6 +210,29 @@ SEXP mhsr_ensemble_predict(SEXP models, SEXP weights, SEXP wt_total, SEXP geom, 
     return out;
 }
 
+/* dismo::mess(covar.ras, ref, full = TRUE) (machisplin_hip.h "MESS extrapolation map").  ref: n_ref x V numeric matrix, the
+ * stations' covariate columns (V = C) or those plus LONG and LAT (V = C + 2); covars: terra::values(covar.ras), ncell x C.
+ * Returns list(mess, mod) in terra cell order: the MESS values (NaN at NA cells) and the integer most dissimilar
+ * variable, 0-based as the library counts it, -1 at NA cells. */
+SEXP mhsr_mess_grid(SEXP ref, SEXP geom, SEXP covars) {
+    mhs_grid g = grid_from(geom);
+    mhs_mess *m = NULL;
+    mhs_stack st = { REAL(covars), Rf_ncols(covars), MHS_F64, (int64_t)g.nrow * g.ncol, g.ncol, R_NaN };
+    if ((int64_t)Rf_nrows(covars) != g.nrow * g.ncol) Rf_error("mhsr_mess_grid: covars must have one row per cell");
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SEXP mess = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)g.nrow * g.ncol));
+    SEXP mod = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)g.nrow * g.ncol));
+    /* the handle lives only between here and mhs_mess_free: no R call in between can unwind past it */
+    int rc = mhs_mess_create(REAL(ref), (int64_t)Rf_nrows(ref), Rf_ncols(ref), &m);
+    if (rc == MHS_OK) rc = mhs_mess_grid(m, &g, &st, 0, g.nrow, 0, g.ncol, REAL(mess), INTEGER(mod));
+    mhs_mess_free(m);
+    SET_VECTOR_ELT(out, 0, mess);
+    SET_VECTOR_ELT(out, 1, mod);
+    UNPROTECT(3);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

@@ -146,7 +146,12 @@ SIGNATURES = {
     "mhs_gbm_probe_last": (C.c_int, [_vp, _vp, _vp]),
     "mhs_residual_points": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _vp, _i64, _vp]),
     "mhs_scale_add_dev": (C.c_int, [_vp, C.c_double, _vp, _vp, _i64, _vp]),
-    "mhs_crop_window": (C.c_int, [C.POINTER(Grid), _vp, _vp]),
+    "mhs_mess_create": (C.c_int, [_vp, _i64, C.c_int, C.POINTER(_vp)]),
+    "mhs_mess_free": (C.c_int, [_vp]),
+    "mhs_mess_grid_dev": (C.c_int, [_vp, C.POINTER(Grid), C.POINTER(Stack), _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "mhs_mess_grid": (C.c_int, [_vp, C.POINTER(Grid), C.POINTER(Stack), _i64, _i64, _i64, _i64, _vp, _vp]),
+    "mhs_mess_points": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),
     "mhs_tiles_create_windows": (C.c_int, [C.POINTER(Grid), _i64, _i64, C.c_double, _vp, _vp]),

@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib, tiles
+from .mess import Mess
 from .models import ensemble_predict
 from .raster import Geometry, RasterStack
 from .tps import Tps, fit_many, interpolate
@@ -167,7 +168,7 @@ def complete_cases(stack: RasterStack, int_values):
 
 def mltps_predict(stack: RasterStack, int_xy, resp, models, weights, wt_total, tps: bool = True,
                   tile_edge: int = 1500, lambda_=None, gcv_mode: str = "fields", tps_info: bool = False,
-                  keep=None):
+                  keep=None, mess=False):
     """machisplin.mltps Steps 2-5 for ONE response layer, given the fitted ensemble members.
 
     Returns a dict mirroring ``omega[[i]]`` (V73:914-930, 946-955): ``final`` (device tensor),
@@ -175,7 +176,10 @@ def mltps_predict(stack: RasterStack, int_xy, resp, models, weights, wt_total, t
     intermediate ``pred_elev`` and ``final_tps`` planes.  ``tps_info=True`` composes Step 3 tile by tile and
     reports the per-tile station counts and lambdas in ``tps_info`` (same surface, slower).  ``keep`` is the
     table-wide complete.cases mask (:func:`complete_cases`, what :func:`mltps` passes); without it the mask is
-    taken over this layer's columns only -- the caller then owns the reference's table-wide filter."""
+    taken over this layer's columns only -- the caller then owns the reference's table-wide filter.
+    ``mess=True`` adds ``mess`` and ``mess_var`` (device tensors): the MESS extrapolation map of the grid against the kept
+    stations' covariate columns and its most dissimilar variable (:class:`mess.Mess`; ``dismo::mess(covar.ras,
+    dat_tps[[i]][, 1:n.covars], full = TRUE)``); ``mess="all"`` includes LONG and LAT.  The default runs nothing extra."""
     import torch
     g = stack.geom
     X, rows, cols = station_predictors(stack, int_xy)
@@ -189,6 +193,10 @@ def mltps_predict(stack: RasterStack, int_xy, resp, models, weights, wt_total, t
     tss = float(np.sum((y - y.mean()) ** 2))
     rsq_model = 1.0 - float(np.sum(res_final ** 2)) / tss
     out = {"pred_elev": pred_elev, "rsq_model": rsq_model, "n_stations": int(y.size)}
+    if mess:
+        if mess is not True and mess != "all":
+            raise ValueError('mess must be False, True or "all"')
+        out["mess"], out["mess_var"] = Mess(X if mess == "all" else X[:, :stack.n_layers]).grid(stack, mod=True)
     knots = X[:, -2:]  # LONG, LAT columns of dat_tps (V73:688,751)
     if not tps:  # V73:934-953
         out.update({"final": pred_elev, "residuals": np.column_stack([res_final, knots]),
@@ -213,13 +221,14 @@ def mltps_predict(stack: RasterStack, int_xy, resp, models, weights, wt_total, t
 
 
 def mltps(stack: RasterStack, int_values, fitted, tps: bool = True, tile_edge: int = 1500, lambda_=None,
-          gcv_mode: str = "fields"):
+          gcv_mode: str = "fields", mess=False):
     """The layer loop of machisplin.mltps (V73:176-957) over fitted members: ``int_values`` is the reference's
     table as an array (columns long, lat, then one response column per layer, V73:120-154); ``fitted[i]`` holds
     layer i's ``models`` (device models in ``mods.run`` order), ``weights`` (rounded kept weights) and ``wt_total``
     (V73:337-392).  Returns the list ``omega``: one :func:`mltps_predict` result per layer plus ``n_layers``
     (V73:955) and, where ``fitted[i]`` carries one, its ``var_imp`` -- Step 1 (fitting, CV, weight search) happens before this call: in R, or by :func:`cv.fit_layer`, whose
-    result for layer i IS a ``fitted[i]``."""
+    result for layer i IS a ``fitted[i]``.  ``mess``: as in :func:`mltps_predict` (every layer keeps the same stations, so
+    the planes of the layers are equal)."""
     int_values = np.asarray(int_values, dtype=np.float64)
     n_layers = int_values.shape[1] - 2
     if n_layers != len(fitted):
@@ -230,7 +239,7 @@ def mltps(stack: RasterStack, int_values, fitted, tps: bool = True, tile_edge: i
     with reduction_cache():      # every layer fits the same stations: the tiles' reductions are built once (bit-identical fits)
         for i, f in enumerate(fitted):
             out = mltps_predict(stack, int_values[:, :2], int_values[:, 2 + i], f["models"], f["weights"], f["wt_total"],
-                                tps=tps, tile_edge=tile_edge, lambda_=lambda_, gcv_mode=gcv_mode, keep=keep)
+                                tps=tps, tile_edge=tile_edge, lambda_=lambda_, gcv_mode=gcv_mode, keep=keep, mess=mess)
             out["n_layers"] = n_layers
             if "var_imp" in f:       # cv.fit_layer(var_imp = True): the layer's $var.imp (V73:465 ... 602)
                 out["var_imp"] = f["var_imp"]
