@@ -599,6 +599,95 @@ MHS_API int mhs_mess_grid(const mhs_mess *m, const mhs_grid *g, const mhs_stack 
  * stations themselves, hold-out rows.  out_host[n]; mod_host[n] may be NULL.                                          */
 MHS_API int mhs_mess_points(const mhs_mess *m, const double *X, int64_t n, double *out_host, int32_t *mod_host);
 
+/* ------------------------------------------------------------------ terrain --
+ * Topographic covariates from an elevation model: what the reference package's README sends its users to SAGA, GRASS and
+ * terra for ("Need help with the high-resolution topography data?") -- slope, aspect, relative elevation, geomorphons.  The
+ * reference has no such step.  THE RULES (this text is the specification; parity with terra, SAGA and GRASS is not pinned).
+ * TWI needs flow accumulation and is not here.
+ *
+ * Input: layer `layer` of an mhs_stack on an mhs_grid (int16, float32 or float64).  A cell is NA if it is NaN or equals
+ * the stack's nodata; values are converted exactly to double.  Cells outside the raster count as NA.
+ * Ground units (mhs_terrain_units): dy > 0 is the cell height; the cell width is dx > 0 or, when dx_row != NULL,
+ * dx_row[row] -- one positive finite width per row of the WHOLE grid, indexed by absolute row, on the HOST in every entry
+ * point (it goes up once per call, on the call's stream).  z_factor > 0 multiplies every elevation difference.  The library
+ * never calls cos: for a lon/lat raster the caller makes dx_row = xres (pi / 180) 6378137 cos(latitude of the row's centre)
+ * and dy = yres (pi / 180) 6378137.
+ * Windows: every call makes the output window [r0,r1) x [c0,c1) and reads neighbours from the whole plane, so a window
+ * equals the same cells of the whole-grid call bit for bit.
+ * Arithmetic: no atomics; every floating-point operation below is done in the order written and rounded once (f64 sqrt and
+ * / are correctly rounded), so a numpy restatement gives the same bits.  Only atan and atan2 (slope_deg, aspect_deg, the
+ * geomorphons' angles) can differ from another math library's.  A float32 output is the float64 result rounded once.
+ *
+ * 1. 3 x 3 terrain.  Neighbourhood a b c / d e f / g h i, north row first; any NA among the nine (so the raster's outer
+ *    ring) gives NA in every variable.  Bit k of `vars` selects variable k; the requested planes come out of ONE pass in
+ *    ascending bit order, plane p at out + p * plane_stride:
+ *      0 dzdx       = (((c + 2 f) + i) - ((a + 2 d) + g)) * z_factor / (8 * dx_row)                 (Horn)
+ *      1 dzdy       = (((g + 2 h) + i) - ((a + 2 b) + c)) * z_factor / (8 * dy)                     south minus north
+ *      2 slope_tan  = sqrt(dzdx * dzdx + dzdy * dzdy)
+ *      3 slope_deg  = atan(slope_tan) * (180 / pi)
+ *      4 eastness   = -dzdx / slope_tan                                  0 where slope_tan == 0
+ *      5 northness  = dzdy / slope_tan                                   0 where slope_tan == 0
+ *      6 aspect_deg = atan2(-dzdx, dzdy) * (180 / pi), + 360 where negative: degrees clockwise from north, downslope;
+ *                     -1 where slope_tan == 0 (ESRI's convention)
+ *      7 tpi        = (e - (((((((a + b) + c) + d) + f) + g) + h) + i) / 8) * z_factor
+ *      8 tri        = (|a - e| + |b - e| + ... + |i - e| in the same order) / 8 * z_factor
+ *      9 roughness  = (max - min of the nine) * z_factor
+ * 2. Relief in a circular window of radius R cells, 1 <= R <= MHS_TERRAIN_MAX_RADIUS (the bundled relative_elevation500m is
+ *    R = 17 at 30 m).  Offsets (dr, dc) with dr^2 + dc^2 <= R^2 are visited row-major; NA cells and cells outside the raster
+ *    are skipped (na.rm); an NA centre gives NA.  Bit k of `stats`:
+ *      0 above_min  = (e - min) * z_factor      1 below_max = (max - e) * z_factor
+ *      2 minus_mean = (e - sum / count) * z_factor, the sum added in the visiting order
+ *    dx, dx_row and dy are not looked at.
+ * 3. Geomorphons (Jasiewicz & Stepinski 2013): search length L cells, 1 <= L <= MHS_TERRAIN_MAX_RADIUS, flatness threshold
+ *    flat_deg >= 0.  Per cell, for the eight directions N, NE, E, SE, S, SW, W, NW and the steps k = 1 .. L:
+ *      s_k = ((z_k - e) * z_factor) / (k * step),  step = dy, dx_row of the CENTRE's row, or sqrt(dy * dy + dx * dx).
+ *    A ray stops at the first NA or outside cell; a ray with no valid step, or an NA centre, makes the cell NA (-32768).
+ *    Per direction a = max s_k, b = min s_k, D = atan(a) + atan(b) (nadir minus zenith angle); the element is + if D > t,
+ *    - if D < -t, else 0, t = flat_deg * (pi / 180).  The int16 form comes from the counts by the paper's table:
+ *      1 flat FL, 2 peak PK, 3 ridge RI, 4 shoulder SH, 5 spur SP, 6 slope SL, 7 hollow HO, 8 footslope FS, 9 valley VL,
+ *      10 pit PT
+ *        minus\plus 0  1  2  3  4  5  6  7  8
+ *        0          FL FL FL FS FS VL VL VL PT
+ *        1          FL FL FS FS FS VL VL VL
+ *        2          FL SH SL SL HO HO VL
+ *        3          SH SH SL SL SL HO
+ *        4          SH SH SP SL SL
+ *        5          RI RI SP SP
+ *        6          RI RI RI
+ *        7          RI RI
+ *        8          PK
+ *
+ * Every argument is checked before the first device call; a failed check returns MHS_ERR_INVALID and the message names
+ * the argument (the window, the layer, radius / search with the limit, flat_deg, dx, dy, z_factor, the dx_row entry, the
+ * mask, out, ld, plane_stride).                                                                                       */
+#define MHS_TERRAIN_MAX_RADIUS 45   /* the largest halo whose float64 tile fits the kernels' LDS (csrc/terrain.hip) */
+typedef struct mhs_terrain_units {
+    double dx;              /* cell width in ground units; not looked at when dx_row != NULL */
+    const double *dx_row;   /* HOST: g->nrow widths by absolute row, or NULL */
+    double dy;              /* cell height in ground units */
+    double z_factor;        /* elevation units -> ground units */
+} mhs_terrain_units;
+MHS_API int mhs_terrain_max_radius(void);   /* MHS_TERRAIN_MAX_RADIUS of the loaded library */
+/* DEVICE planes: dem->data covers the whole grid; out_dev holds the requested planes, each (r1-r0) x ld row-major,
+ * plane_stride elements apart, of out_dtype MHS_F64 or MHS_F32.  Only enqueues on `stream`. */
+MHS_API int mhs_terrain_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int64_t r0,
+                            int64_t r1, int64_t c0, int64_t c1, unsigned vars, void *out_dev, int out_dtype, int64_t ld,
+                            int64_t plane_stride, void *stream);
+MHS_API int mhs_relief_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int radius,
+                           int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned stats, void *out_dev, int out_dtype,
+                           int64_t ld, int64_t plane_stride, void *stream);
+MHS_API int mhs_geomorphon_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
+                               double flat_deg, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int16_t *out_dev, int64_t ld,
+                               void *stream);
+/* same, HOST planes: dem->data and out_host (planes of (r1-r0) x (c1-c0), one behind the other) on the host -- what the R
+ * shim hands over.  Row bands of the window go up with their halo rows, through the same kernels; blocks until done. */
+MHS_API int mhs_terrain(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int64_t r0,
+                        int64_t r1, int64_t c0, int64_t c1, unsigned vars, void *out_host, int out_dtype);
+MHS_API int mhs_relief(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int radius,
+                       int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned stats, void *out_host, int out_dtype);
+MHS_API int mhs_geomorphon(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
+                           double flat_deg, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int16_t *out_host);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

@@ -125,6 +125,47 @@ mhs_mess <- function(covar.ras, dat, n.covars, lonlat = FALSE) {
   out
 }
 
+# ---- topographic covariates from the DEM: what the README's "Need help with the high-resolution topography data?" sends to
+# SAGA, GRASS and terra ------------------------------------------------------------------------------------------------
+# v: any of .mhs_terrain_vars (3 x 3 window), "above_min" / "below_max" / "minus_mean" (relief in a circular window of `radius`
+# cells; above_min is the bundled relative_elevation500m at radius = 17 on 30 m cells) and "geomorphon" (search length `search`
+# cells, flatness `flat.deg` degrees; forms 1 flat .. 10 pit).  Returns a SpatRaster with one layer per entry of v.  A lon/lat
+# raster gets its cell sizes in metres on the sphere -- the cosine is taken here, the library never calls cos.
+.mhs_terrain_vars <- c("dzdx", "dzdy", "slope_tan", "slope_deg", "eastness", "northness", "aspect_deg", "tpi", "tri", "roughness")
+.mhs_relief_stats <- c("above_min", "below_max", "minus_mean")
+mhs_terrain <- function(dem.ras, v = "slope_deg", radius = 17L, search = 10L, flat.deg = 1, z.factor = 1,
+                        lonlat = terra::is.lonlat(dem.ras)) {
+  bad <- setdiff(v, c(.mhs_terrain_vars, .mhs_relief_stats, "geomorphon"))
+  if (length(bad)) stop("mhs_terrain: unknown variable ", paste(bad, collapse = ", "))
+  geom <- .mhs_geom(dem.ras)
+  z <- as.numeric(terra::values(dem.ras[[1]]))
+  res <- terra::res(dem.ras)
+  if (isTRUE(lonlat)) {
+    lat <- terra::yFromRow(dem.ras, seq_len(terra::nrow(dem.ras)))
+    dx.row <- res[1] * (pi / 180) * 6378137 * cos(lat * (pi / 180))
+    units <- c(NA_real_, res[2] * (pi / 180) * 6378137, z.factor)
+  } else {
+    dx.row <- NULL
+    units <- c(res[1], res[2], z.factor)
+  }
+  layers <- list()
+  tv <- intersect(.mhs_terrain_vars, v)                      # ascending bit order: the order of the columns that come back
+  if (length(tv)) {
+    m <- .Call("mhsr_terrain", geom, z, units, dx.row, as.integer(sum(2^(match(tv, .mhs_terrain_vars) - 1))))
+    for (k in seq_along(tv)) layers[[tv[k]]] <- m[, k]
+  }
+  rs <- intersect(.mhs_relief_stats, v)
+  if (length(rs)) {
+    m <- .Call("mhsr_relief", geom, z, as.numeric(z.factor), as.integer(radius), as.integer(sum(2^(match(rs, .mhs_relief_stats) - 1))))
+    for (k in seq_along(rs)) layers[[rs[k]]] <- m[, k]
+  }
+  if ("geomorphon" %in% v)
+    layers[["geomorphon"]] <- .Call("mhsr_geomorphon", geom, z, units, dx.row, as.integer(search), as.numeric(flat.deg))
+  out <- do.call(c, lapply(v, function(n) terra::setValues(terra::rast(dem.ras[[1]]), layers[[n]])))
+  names(out) <- v
+  out
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

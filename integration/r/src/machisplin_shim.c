@@ -233,6 +233,66 @@ SEXP mhsr_mess_grid(SEXP ref, SEXP geom, SEXP covars) {
     return out;
 }
 
+/* Topographic covariates from a DEM (machisplin_hip.h "terrain"): what the package's README sends its users to SAGA, GRASS and
+ * terra for.  dem: terra::values(dem.ras), one double per cell (NA_real_ = NA); units: c(dx, dy, z_factor); dx_row: NULL or
+ * one cell width per row (a lon/lat raster: made in R, the library never calls cos).  All three run on the HOST entry points. */
+static mhs_terrain_units units_from(SEXP units, SEXP dx_row, const mhs_grid *g, const char *who) {
+    if (Rf_length(units) != 3) Rf_error("%s: units must be c(dx, dy, z_factor)", who);
+    if (!Rf_isNull(dx_row) && (int64_t)Rf_length(dx_row) != g->nrow) Rf_error("%s: dx_row must have one width per row", who);
+    mhs_terrain_units u = { REAL(units)[0], Rf_isNull(dx_row) ? NULL : REAL(dx_row), REAL(units)[1], REAL(units)[2] };
+    return u;
+}
+static mhs_stack dem_from(SEXP dem, const mhs_grid *g, const char *who) {
+    if ((int64_t)Rf_xlength(dem) != g->nrow * g->ncol) Rf_error("%s: dem must have one value per cell", who);
+    mhs_stack st = { REAL(dem), 1, MHS_F64, (int64_t)g->nrow * g->ncol, g->ncol, R_NaN };
+    return st;
+}
+static int mask_planes(int mask) { int n = 0; for (unsigned m = (unsigned)mask; m; m &= m - 1) ++n; return n; }
+
+/* the 3 x 3 variables of the bit mask vars (bit 0 dzdx ... bit 9 roughness): an ncell x n matrix, columns in ascending bit order */
+SEXP mhsr_terrain(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP vars) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_terrain");
+    mhs_terrain_units u = units_from(units, dx_row, &g, "mhsr_terrain");
+    int mask = Rf_asInteger(vars), n = mask_planes(mask);
+    if (mask == NA_INTEGER || mask < 0) Rf_error("mhsr_terrain: vars must be a bit mask");
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(g.nrow * g.ncol), n > 0 ? n : 1));
+    int rc = mhs_terrain(&g, &st, 0, &u, 0, g.nrow, 0, g.ncol, (unsigned)mask, REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
+/* relief in a circular window of `radius` cells, the statistics of the bit mask stats (1 above_min, 2 below_max, 4 minus_mean) */
+SEXP mhsr_relief(SEXP geom, SEXP dem, SEXP z_factor, SEXP radius, SEXP stats) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_relief");
+    mhs_terrain_units u = { 0.0, NULL, 0.0, Rf_asReal(z_factor) };
+    int mask = Rf_asInteger(stats), n = mask_planes(mask);
+    if (mask == NA_INTEGER || mask < 0) Rf_error("mhsr_relief: stats must be a bit mask");
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(g.nrow * g.ncol), n > 0 ? n : 1));
+    int rc = mhs_relief(&g, &st, 0, &u, Rf_asInteger(radius), 0, g.nrow, 0, g.ncol, (unsigned)mask, REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
+/* geomorphons: an integer vector of the forms 1 .. 10 in terra cell order, NA_integer_ at NA cells */
+SEXP mhsr_geomorphon(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP search, SEXP flat_deg) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_geomorphon");
+    mhs_terrain_units u = units_from(units, dx_row, &g, "mhsr_geomorphon");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    SEXP out = PROTECT(Rf_allocVector(INTSXP, n));
+    int16_t *forms = (int16_t *)R_alloc((size_t)(n ? n : 1), sizeof(int16_t));
+    int rc = mhs_geomorphon(&g, &st, 0, &u, Rf_asInteger(search), Rf_asReal(flat_deg), 0, g.nrow, 0, g.ncol, forms);
+    if (rc == MHS_OK)
+        for (R_xlen_t k = 0; k < n; ++k) INTEGER(out)[k] = forms[k] == -32768 ? NA_INTEGER : (int)forms[k];
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

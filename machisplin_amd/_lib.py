@@ -66,6 +66,11 @@ class UnitsInfo(C.Structure):
                 ("unit_ms_sum", C.c_double), ("unit_ms_max", C.c_double), ("slot_ms", C.c_double * 16)]
 
 
+class TerrainUnits(C.Structure):
+    """struct mhs_terrain_units"""
+    _fields_ = [("dx", C.c_double), ("dx_row", C.c_void_p), ("dy", C.c_double), ("z_factor", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -151,6 +156,19 @@ SIGNATURES = {
     "mhs_mess_grid_dev": (C.c_int, [_vp, C.POINTER(Grid), C.POINTER(Stack), _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mhs_mess_grid": (C.c_int, [_vp, C.POINTER(Grid), C.POINTER(Stack), _i64, _i64, _i64, _i64, _vp, _vp]),
     "mhs_mess_points": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "mhs_terrain_max_radius": (C.c_int, []),
+    "mhs_terrain_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), _i64, _i64, _i64, _i64, C.c_uint,
+                                  _vp, C.c_int, _i64, _i64, _vp]),
+    "mhs_relief_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, _i64, _i64, _i64, _i64,
+                                 C.c_uint, _vp, C.c_int, _i64, _i64, _vp]),
+    "mhs_geomorphon_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.c_double, _i64, _i64,
+                                     _i64, _i64, _vp, _i64, _vp]),
+    "mhs_terrain": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), _i64, _i64, _i64, _i64, C.c_uint, _vp,
+                              C.c_int]),
+    "mhs_relief": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, _i64, _i64, _i64, _i64, C.c_uint,
+                             _vp, C.c_int]),
+    "mhs_geomorphon": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.c_double, _i64, _i64, _i64,
+                                 _i64, _vp]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

@@ -1,0 +1,179 @@
+"""Topographic covariates from an elevation model: slope, aspect, relief, geomorphons.
+
+What the reference package's README sends its users to SAGA, GRASS and terra for ("Need help with the high-resolution
+topography data?"): the covariate rasters derived from the DEM -- ``slope``, ``rel_alt`` / ``relative_elevation500m`` and
+their kin (TWI needs flow accumulation and is not here).  include/machisplin_hip.h, section "terrain", states the rules.
+All arithmetic runs in libmachisplin_hip.so (csrc/terrain.hip); this module only marshals arguments -- and, for a lon/lat
+raster, makes the rows' ground widths with numpy, because the library never calls cos.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .raster import RasterStack
+
+VARS = ("dzdx", "dzdy", "slope_tan", "slope_deg", "eastness", "northness", "aspect_deg", "tpi", "tri", "roughness")
+STATS = ("above_min", "below_max", "minus_mean")
+FORMS = ("flat", "peak", "ridge", "shoulder", "spur", "slope", "hollow", "footslope", "valley", "pit")       # codes 1 .. 10
+GEOMORPHON_NA = -32768
+EARTH_RADIUS = 6378137.0
+
+
+def max_radius() -> int:
+    """MHS_TERRAIN_MAX_RADIUS of the loaded library: the largest relief radius and geomorphon search length, in cells."""
+    return int(_lib.load().mhs_terrain_max_radius())
+
+
+def ground_units(geom, lonlat=False, z_factor=1.0, dx=None, dy=None, dx_row=None):
+    """(dx, dx_row, dy, z_factor) of a raster: its resolution as it stands, or -- ``lonlat=True``, degrees -- metres on the
+    sphere: dx_row = xres (pi / 180) 6378137 cos(latitude of the row's centre), dy = yres (pi / 180) 6378137.  ``dx``,
+    ``dy`` and ``dx_row`` (one width per row of the whole grid) override."""
+    if dx_row is not None:
+        dx_row = np.ascontiguousarray(dx_row, dtype=np.float64)
+        if dx_row.shape != (geom.nrow,):
+            raise ValueError("dx_row must hold one width per row of the whole grid")
+    elif lonlat and dx is None:
+        lat = geom.y_from_row(np.arange(geom.nrow))
+        dx_row = np.ascontiguousarray(geom.xres * (np.pi / 180.0) * EARTH_RADIUS * np.cos(lat * (np.pi / 180.0)))
+    if dy is None:
+        dy = geom.yres * (np.pi / 180.0) * EARTH_RADIUS if lonlat else geom.yres
+    if dx is None:
+        dx = geom.xres
+    return float(dx), dx_row, float(dy), float(z_factor)
+
+
+def _c_units(units):
+    dx, dx_row, dy, zf = units
+    return _lib.TerrainUnits(dx, dx_row.ctypes.data if dx_row is not None else None, dy, zf)
+
+
+def _window(stack, window):
+    g = stack.geom
+    return tuple(int(x) for x in window) if window is not None else (0, g.nrow, 0, g.ncol)
+
+
+def _mask(names, table, what):
+    one = isinstance(names, str)
+    names = (names,) if one else tuple(names)
+    for n in names:
+        if n not in table:
+            raise ValueError(f"unknown {what} {n!r}: one of {', '.join(table)}")
+    if not names or len(set(names)) != len(names):
+        raise ValueError(f"give every {what} once")
+    mask = 0
+    for n in names:
+        mask |= 1 << table.index(n)
+    order = sorted(names, key=table.index)            # the library's plane order: ascending bit
+    return one, names, mask, [order.index(n) for n in names]
+
+
+def _planes(stack, shape, n, out_dtype, out):
+    import torch
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError("out_dtype must be torch.float64 or torch.float32")
+    if out is None:
+        out = torch.empty((n,) + shape, dtype=out_dtype, device=stack.planes.device)
+    if out.dtype != out_dtype or not out.is_cuda or out.dim() != 3 or out.stride(2) != 1 or tuple(out.shape) != (n,) + shape:
+        raise ValueError("out must be a device tensor (n, rows, cols) of out_dtype with unit column stride")
+    return out, (_lib.F64 if out_dtype == torch.float64 else _lib.F32)
+
+
+def _stream(stack, stream):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(stack.planes.device).cuda_stream
+
+
+def terrain(stack: RasterStack, layer=0, v=("slope_deg",), lonlat=False, z_factor=1.0, window=None, out_dtype=None, out=None,
+            stream=None, dx=None, dy=None, dx_row=None):
+    """3 x 3 terrain variables of layer ``layer``: ``v`` names some of :data:`VARS`; every one of them comes out of one pass.
+    A device tensor (len(v), rows, cols) in the order of ``v`` -- or (rows, cols) when ``v`` is a single name -- NaN where
+    any of the nine cells is NA (so on the raster's outer ring).  aspect_deg is degrees clockwise from north, downslope,
+    -1 at flat cells.  ``window`` = (r0, r1, c0, c1) gives those cells of the whole-grid result bit for bit.  ``out``: a
+    pre-allocated tensor for the planes in the LIBRARY's order (ascending position in :data:`VARS`)."""
+    import torch
+    one, names, mask, order = _mask(v, VARS, "variable")
+    r0, r1, c0, c1 = _window(stack, window)
+    units = ground_units(stack.geom, lonlat, z_factor, dx, dy, dx_row)
+    out, code = _planes(stack, (r1 - r0, c1 - c0), len(names), out_dtype or torch.float64, out)
+    g, s, u = stack.geom.c_struct(), stack.c_struct(), _c_units(units)
+    _lib.check(_lib.lib().mhs_terrain_dev(C.byref(g), C.byref(s), int(layer), C.byref(u), r0, r1, c0, c1, mask, out.data_ptr(), code,
+                                          out.stride(1), out.stride(0), _stream(stack, stream)))
+    if one:
+        return out[0]
+    return out if order == list(range(len(names))) else out[order]
+
+
+def relief(stack: RasterStack, radius, stat="above_min", layer=0, z_factor=1.0, window=None, out_dtype=None, out=None, stream=None):
+    """Relief of layer ``layer`` in a circular window of ``radius`` cells (1 .. :func:`max_radius`), NA cells and cells
+    outside the raster skipped: ``stat`` names some of :data:`STATS` -- above_min is the bundled ``relative_elevation500m``
+    (radius 17 at 30 m).  Shapes, ``window`` and ``out`` as in :func:`terrain`; NaN where the centre is NA."""
+    import torch
+    one, names, mask, order = _mask(stat, STATS, "statistic")
+    r0, r1, c0, c1 = _window(stack, window)
+    units = ground_units(stack.geom, False, z_factor)
+    out, code = _planes(stack, (r1 - r0, c1 - c0), len(names), out_dtype or torch.float64, out)
+    g, s, u = stack.geom.c_struct(), stack.c_struct(), _c_units(units)
+    _lib.check(_lib.lib().mhs_relief_dev(C.byref(g), C.byref(s), int(layer), C.byref(u), int(radius), r0, r1, c0, c1, mask, out.data_ptr(),
+                                         code, out.stride(1), out.stride(0), _stream(stack, stream)))
+    if one:
+        return out[0]
+    return out if order == list(range(len(names))) else out[order]
+
+
+def geomorphon(stack: RasterStack, search, flat_deg=1.0, layer=0, lonlat=False, z_factor=1.0, window=None, out=None, stream=None,
+               dx=None, dy=None, dx_row=None):
+    """Geomorphons (Jasiewicz & Stepinski 2013) of layer ``layer``: search length ``search`` cells (1 .. :func:`max_radius`),
+    flatness threshold ``flat_deg`` degrees.  An int16 device tensor (rows, cols) of the codes 1 .. 10 (:data:`FORMS`),
+    -32768 where the centre is NA or one of the eight rays has no valid step (so on the raster's outer ring)."""
+    import torch
+    r0, r1, c0, c1 = _window(stack, window)
+    units = ground_units(stack.geom, lonlat, z_factor, dx, dy, dx_row)
+    shape = (r1 - r0, c1 - c0)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=stack.planes.device)
+    if out.dtype != torch.int16 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != shape:
+        raise ValueError("out must be an int16 device tensor of the window's shape with unit column stride")
+    g, s, u = stack.geom.c_struct(), stack.c_struct(), _c_units(units)
+    _lib.check(_lib.lib().mhs_geomorphon_dev(C.byref(g), C.byref(s), int(layer), C.byref(u), int(search), float(flat_deg), r0, r1, c0, c1,
+                                             out.data_ptr(), out.stride(0), _stream(stack, stream)))
+    return out
+
+
+def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0):
+    """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
+    then one layer per entry of ``spec`` --
+      a name of :data:`VARS`                      that 3 x 3 variable (all of them in one pass)
+      (a name of :data:`STATS`, radius)           that relief statistic in a window of ``radius`` cells
+      ("geomorphon", search[, flat_deg])          the geomorphon code (1 .. 10)
+    NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
+    import torch
+    spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
+    nr, nc = dem_stack.geom.nrow, dem_stack.geom.ncol
+    planes = torch.empty((1 + len(spec), nr, nc), dtype=torch.float32, device=dem_stack.planes.device)
+    dem = dem_stack.planes[layer]
+    demf = dem.to(torch.float32)
+    if not np.isnan(dem_stack.nodata):
+        demf = torch.where(dem == dem_stack.nodata, torch.full_like(demf, float("nan")), demf)
+    planes[0] = demf
+    names = ["dem"]
+    tv = [e[0] for e in spec if len(e) == 1]
+    if tv:
+        got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
+        by_name = dict(zip(dict.fromkeys(tv), got))
+    for k, e in enumerate(spec):
+        if len(e) == 1:
+            planes[1 + k] = by_name[e[0]]
+            names.append(e[0])
+        elif e[0] == "geomorphon":
+            f = geomorphon(dem_stack, e[1], e[2] if len(e) > 2 else 1.0, layer, lonlat, z_factor)
+            planes[1 + k] = torch.where(f == GEOMORPHON_NA, torch.full((), float("nan"), device=f.device), f.to(torch.float32))
+            names.append(f"geomorphon{int(e[1])}")
+        else:
+            planes[1 + k] = relief(dem_stack, e[1], e[0], layer, z_factor, out_dtype=torch.float32)
+            names.append(f"{e[0]}{int(e[1])}")
+    out = RasterStack(dem_stack.geom, planes, float("nan"))
+    out.names = names
+    return out
