@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -99,6 +100,10 @@ struct SlotBind {                     // RAII: bind for a scope, restore the pre
 };
 std::mutex &pipe_mutex();             // one pipelined host-pointer call at a time (per slot)
 int host_pipe(size_t arena_bytes);    // streams / events on first use; grows the arena (grow-only) to at least arena_bytes
+// One plane of nr x nc doubles (ld = nc) for a host caller, from the persistent arena (no hipMalloc / hipFree per call): under
+// pipe_mutex `fill` writes it on pipe_comp, the copy to out_host follows on that stream, which is then synchronised.  An empty
+// plane still calls `fill` (its argument checks), then copies nothing.
+int plane_to_host(int64_t nr, int64_t nc, double *out_host, const std::function<int(double *dev, hipStream_t s)> &fill);
 std::mutex &mask_mutex();             // guards the fields above and the event pair's record / wait sequences (per slot)
 std::mutex &mosaic_mutex();           // one user of the slot's mosaic arena (of the calling thread's lane) at a time
 int cpu_budget();                     // CPUs this process may keep busy (hardware threads capped by the cgroup quota; tps_gcv_host.hip)

@@ -36,6 +36,7 @@
 #include <thread>
 #include <vector>
 #include "common.h"
+#include "step3_plan.h"
 
 using namespace mhs;
 
@@ -591,10 +592,8 @@ struct StepShared {
     std::vector<double> c, knots_uv;
     double d[3] = {0, 0, 0}, center[2] = {0, 0}, scale[2] = {1, 1}, lambda = NAN;
     // reference-tiled Step 3
-    int64_t nRx = 1, nCx = 1;
-    std::vector<int64_t> fit_win, keep_win;
+    Step3Plan plan;
     std::vector<int> owner;
-    std::vector<size_t> tile_cells;           // cells of tile h's keep window, rounded up to 32
     // what every slot holds of the tiles: the ones it owns (fits + evaluates) and the ones that reach its rows (pulled from
     // their owners) -- offsets into its own tile area, -1 for the others; bytes pulled from peers
     std::vector<int64_t> slot_off[MAX_SLOTS];
@@ -635,26 +634,19 @@ int mhs_mltps_grid_multi_dev(const mhs_model *const *models, const double *weigh
     if (int rc = mhs_cells_from_xy(&g, knots, n, rows.data(), cols.data())) return rc;
     StepShared S;
     S.f_actual.assign((size_t)n, NAN);
-    int64_t nt = 1;
-    if (tile_edge > 0) {
-        if (int rc = mhs_step3_tile_windows(&g, tile_edge, 0.2, 0.025, &S.nRx, &S.nCx, nullptr, nullptr, 0)) return rc;
-        nt = S.nRx * S.nCx;
-    }
+    if (int rc = step3_plan(&g, tile_edge, S.plan)) return rc;
+    const int64_t nt = S.plan.nt;
     const bool tiled = nt > 1;
     if (tiled) {
-        S.fit_win.resize((size_t)nt * 4); S.keep_win.resize((size_t)nt * 4);
-        if (int rc = mhs_step3_tile_windows(&g, tile_edge, 0.2, 0.025, &S.nRx, &S.nCx, S.fit_win.data(), S.keep_win.data(), nt)) return rc;
         // Ownership follows the rows (round 6): a tile is fitted and evaluated by the slot whose band holds most of its keep
         // window -- that slot needs the plane anyway -- and a slot pulls from its peers only the tiles that reach ITS rows,
         // then mosaics and feathers only those rows, straight into its band.  (Rounds 1-5 dealt the tiles by cost, pulled
         // EVERY tile to EVERY slot and mosaicked the whole grid N times: 0.8 GB per slot over the fabric at cfg3 and N x
         // redundant Step-4 work.)  Bands with no rows own nothing.
-        S.tile_cells.resize((size_t)nt);
         S.owner.assign((size_t)nt, 0);
         for (int k = 0; k < N; ++k) S.slot_off[k].assign((size_t)nt, -1);
         for (int64_t h = 0; h < nt; ++h) {
-            const int64_t *kw = &S.keep_win[(size_t)h * 4];
-            S.tile_cells[(size_t)h] = ((size_t)((kw[1] - kw[0]) * (kw[3] - kw[2])) + 31) & ~(size_t)31;
+            const int64_t *kw = &S.plan.keep[(size_t)h * 4];
             int64_t best_rows = -1;
             for (int k = 0; k < N; ++k) {
                 const int64_t ov = std::min(kw[1], ms->b[k].r1) - std::max(kw[0], ms->b[k].r0);
@@ -662,7 +654,7 @@ int mhs_mltps_grid_multi_dev(const mhs_model *const *models, const double *weigh
             }
             for (int k = 0; k < N; ++k) {
                 const bool reaches = ms->b[k].r1 > ms->b[k].r0 && kw[0] < ms->b[k].r1 && kw[1] > ms->b[k].r0;
-                if (reaches || S.owner[(size_t)h] == k) { S.slot_off[k][(size_t)h] = (int64_t)S.slot_need[k]; S.slot_need[k] += S.tile_cells[(size_t)h]; }
+                if (reaches || S.owner[(size_t)h] == k) { S.slot_off[k][(size_t)h] = (int64_t)S.slot_need[k]; S.slot_need[k] += S.plan.cells(h); }
             }
         }
     }
@@ -843,18 +835,18 @@ int mhs_mltps_grid_multi_dev(const mhs_model *const *models, const double *weigh
                 if (nb == 0) return MHS_OK;
                 std::vector<const double *> ptrs((size_t)nt, nullptr);
                 for (int64_t h = 0; h < nt; ++h) {
-                    const int64_t *kw = &S.keep_win[(size_t)h * 4];
+                    const int64_t *kw = &S.plan.keep[(size_t)h * 4];
                     if (!(kw[0] < b.r1 && kw[1] > b.r0)) continue;     // does not reach this slot's rows
                     const int o = S.owner[(size_t)h];
                     ptrs[(size_t)h] = b.tiles + S.slot_off[slot][(size_t)h];
                     if (o == slot) continue;
-                    const size_t bytes = sizeof(double) * S.tile_cells[(size_t)h];
+                    const size_t bytes = sizeof(double) * S.plan.cells(h);
                     MHS_HIP(hipMemcpyPeerAsync(b.tiles + S.slot_off[slot][(size_t)h], ctx_slot(slot).device,
                                                ms->b[o].tiles + S.slot_off[o][(size_t)h], ctx_slot(o).device, bytes, M->s));
                     S.pulled_bytes[slot] += (int64_t)bytes;
                 }
                 // Step 4 on this slot's rows only, into its band (the tiles are spline planes: no NA)
-                return mosaic_feather_impl(&g, S.nRx, S.nCx, S.keep_win.data(), ptrs.data(), 0, b.tot, g.ncol, nullptr, M->s, true, b.r0, b.r1);
+                return mosaic_feather_impl(&g, S.plan.nRx, S.plan.nCx, S.plan.keep.data(), ptrs.data(), 0, b.tot, g.ncol, nullptr, M->s, true, b.r0, b.r1);
             };
             TEAM_DO(team, bring());
             if (piped && nb > 0) {
@@ -975,7 +967,7 @@ int mhs_mltps_grid_multi_dev(const mhs_model *const *models, const double *weigh
         memset(info, 0, sizeof(*info));
         info->rsq_model = S.rsq_model; info->rsq_final = S.rsq_final; info->lambda = tiled ? NAN : S.lambda;
         info->n_knots = tiled ? 0 : S.nk; info->used_tps = S.used_tps; info->n_slots = N;
-        info->tiles_rows = S.nRx; info->tiles_cols = S.nCx;
+        info->tiles_rows = S.plan.nRx; info->tiles_cols = S.plan.nCx;
         info->collective = !gather ? 0 : use_rccl ? 1 : 2;
         info->fit_ms = S.fit_ms; info->step_ms = step_ms; info->suggested_slot0_share = suggested;
         for (int k = 0; k < N; ++k) {

@@ -146,6 +146,18 @@ int host_pipe(size_t arena_bytes) {
     return MHS_OK;
 }
 
+int plane_to_host(int64_t nr, int64_t nc, double *out_host, const std::function<int(double *dev, hipStream_t s)> &fill) {
+    const size_t bytes = sizeof(double) * (size_t)(nr * nc);
+    std::lock_guard<std::mutex> lk(pipe_mutex());
+    if (int rc = host_pipe(std::max(bytes, sizeof(double)))) return rc;
+    Context &c = ctx();
+    if (int rc = fill((double *)c.pipe_arena, c.pipe_comp)) return rc;
+    if (bytes == 0) return MHS_OK;
+    MHS_HIP(hipMemcpyAsync(out_host, c.pipe_arena, bytes, hipMemcpyDeviceToHost, c.pipe_comp));
+    MHS_HIP(hipStreamSynchronize(c.pipe_comp));
+    return MHS_OK;
+}
+
 int fit_lane(int i, FitLane **out) {
     Context &c = ctx();
     // mhs_fit_reserve_cus walks c.lanes and rebuilds their masked streams under this mutex

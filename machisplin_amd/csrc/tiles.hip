@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "step3_plan.h"
 
 namespace mhs {
 
@@ -323,6 +324,34 @@ int mhs_tiles_create_windows(const mhs_grid *g, int64_t out_ncol, int64_t out_nr
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------- Step3Plan --
+int mhs::step3_plan(const mhs_grid *g, int64_t tile_edge, Step3Plan &P) {
+    if (tile_edge <= 0) return MHS_OK;
+    if (int rc = mhs_step3_tile_windows(g, tile_edge, STEP3_FIT_OVERLAP, STEP3_KEEP_OVERLAP, &P.nRx, &P.nCx, nullptr, nullptr, 0)) return rc;
+    P.nt = P.nRx * P.nCx;
+    P.fit.resize((size_t)P.nt * 4); P.keep.resize((size_t)P.nt * 4);
+    return mhs_step3_tile_windows(g, tile_edge, STEP3_FIT_OVERLAP, STEP3_KEEP_OVERLAP, &P.nRx, &P.nCx, P.fit.data(), P.keep.data(), P.nt);
+}
+
+mhs_grid mhs::Step3Plan::fit_grid(const mhs_grid *g, int64_t h) const {
+    const int64_t *f = &fit[(size_t)h * 4];
+    return window_geom(*g, Win{f[0], f[1], f[2], f[3]});
+}
+
+void mhs::step3_stations(const Step3Plan &P, int64_t h, const int64_t *rows, const int64_t *cols, const double *xy, const double *resid,
+                         const double *cov1, int64_t n, std::vector<double> &txy, std::vector<double> &sr) {
+    const int64_t *f = &P.fit[(size_t)h * 4];
+    std::vector<double> sy;      // the y block, appended behind the x block
+    txy.clear(); sr.clear();
+    for (int64_t i = 0; i < n; ++i) {
+        if (rows[i] < f[0] || rows[i] >= f[1] || cols[i] < f[2] || cols[i] >= f[3]) continue;
+        if (cov1 && std::isnan(cov1[i])) continue;
+        if (std::isnan(resid[i])) continue;
+        txy.push_back(xy[i]); sy.push_back(xy[n + i]); sr.push_back(resid[i]);
+    }
+    txy.insert(txy.end(), sy.begin(), sy.end());
+}
 
 // finite_tiles: the caller vouches that no tile holds an NA (thin-plate-spline planes: mhs_tps_surface) -- every seam's
 // A + B is then non-NA on the whole overlap and the bounding-box pass (a kernel, a copy back and a host wait) is skipped

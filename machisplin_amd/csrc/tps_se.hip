@@ -26,6 +26,7 @@
 #include <vector>
 #include "common.h"
 #include "devmath.h"
+#include "step3_plan.h"
 #include "tps_host.h"
 #include "tps_se.h"
 
@@ -477,29 +478,18 @@ static int se_launch(std::vector<SeWindow> &wins, hipStream_t s, void **desc_out
     return MHS_OK;
 }
 
-// Step-3 tile windows and the stations of every fit box, as run_tiles (tps_surface.hip) selects them
-static int surface_se_tiles(const mhs_grid *g, const double *xy, const double *resid, int64_t n, const double *cov1,
-                            int64_t tile_edge, double lambda, int gcv_mode, double *out_dev, int64_t ld, int64_t nRx, int64_t nCx,
-                            hipStream_t s) {
-    const int64_t nt = nRx * nCx;
-    std::vector<int64_t> fit((size_t)nt * 4), keep((size_t)nt * 4), rows((size_t)n), cols((size_t)n);
-    if (int rc = mhs_step3_tile_windows(g, tile_edge, 0.2, 0.025, &nRx, &nCx, fit.data(), keep.data(), nt)) return rc;
+// The SE plane of the plan's tiles: the windows, the stations and the packed layout are the Step3Plan's (step3_plan.h), the ones
+// the estimate's own driver (run_tiles, tps_surface.hip) works from; the fits are materialised handles here (mhs_tps_fit_many)
+static int surface_se_tiles(const mhs_grid *g, const Step3Plan &P, const double *xy, const double *resid, int64_t n, const double *cov1,
+                            double lambda, int gcv_mode, double *out_dev, int64_t ld, hipStream_t s) {
+    const int64_t nt = P.nt;
+    std::vector<int64_t> rows((size_t)n), cols((size_t)n);
     if (int rc = mhs_cells_from_xy(g, xy, n, rows.data(), cols.data())) return rc;
     std::vector<std::vector<double>> txy((size_t)nt), ty((size_t)nt);
     std::vector<int64_t> todo;
     for (int64_t h = 0; h < nt; ++h) {
-        const int64_t *f = &fit[(size_t)h * 4];
-        std::vector<double> sx, sy;
-        for (int64_t i = 0; i < n; ++i) {
-            if (rows[i] < f[0] || rows[i] >= f[1] || cols[i] < f[2] || cols[i] >= f[3]) continue;
-            if (cov1 && std::isnan(cov1[i])) continue;
-            if (std::isnan(resid[i])) continue;
-            sx.push_back(xy[i]); sy.push_back(xy[n + i]); ty[(size_t)h].push_back(resid[i]);
-        }
-        if (sx.size() < 10) continue;     // V73:710-721: no spline
-        txy[(size_t)h] = sx;
-        txy[(size_t)h].insert(txy[(size_t)h].end(), sy.begin(), sy.end());
-        todo.push_back(h);
+        step3_stations(P, h, rows.data(), cols.data(), xy, resid, cov1, n, txy[(size_t)h], ty[(size_t)h]);
+        if ((int64_t)ty[(size_t)h].size() >= STEP3_MIN_STATIONS) todo.push_back(h);     // V73:710-721: no spline below that
     }
     // the tiles' fits in one call (what mhs_tps_fit_many gives a caller that composes the same steps)
     const int64_t nf = (int64_t)todo.size();
@@ -532,26 +522,18 @@ static int surface_se_tiles(const mhs_grid *g, const double *xy, const double *r
     for (int64_t q = 0; q < nf; ++q)
         if (rcs[(size_t)q]) { set_error("%s", errs[(size_t)q].c_str()); return rcs[(size_t)q]; }
     // the tiles' keep windows, then ONE launch for all of them
-    size_t total = 0;
-    std::vector<size_t> off((size_t)nt);
-    for (int64_t h = 0; h < nt; ++h) {
-        const int64_t *k = &keep[(size_t)h * 4];
-        off[(size_t)h] = total;
-        total += ((size_t)((k[1] - k[0]) * (k[3] - k[2])) + 31) & ~(size_t)31;
-    }
+    const std::vector<size_t> off = P.pack();
     DevBuf<double> buf;
-    MHS_HIP(buf.alloc(total));
+    MHS_HIP(buf.alloc(off[(size_t)nt]));
     std::vector<SeWindow> wins;
     std::vector<const double *> ptrs((size_t)nt);
     int64_t q = 0;
     for (int64_t h = 0; h < nt; ++h) {
-        const int64_t *f = &fit[(size_t)h * 4], *k = &keep[(size_t)h * 4];
         double *o = buf.p + off[(size_t)h];
         ptrs[(size_t)h] = o;
-        mhs_grid gf = *g;            // terra::rast(rb): the fit raster, evaluated on the keep window (V73:726)
-        gf.xmin = g->xmin + (double)f[2] * g->xres;
-        gf.ymax = g->ymax - (double)f[0] * g->yres;
-        gf.nrow = f[1] - f[0]; gf.ncol = f[3] - f[2];
+        const mhs_grid gf = P.fit_grid(g, h);      // terra::rast(rb): the fit raster, evaluated on the keep window (V73:726)
+        int64_t r0, r1, c0, c1;
+        P.keep_in_fit(h, &r0, &r1, &c0, &c1);
         SeWindow w;
         if (q < nf && todo[(size_t)q] == h) {
             double rho = 0;
@@ -559,12 +541,12 @@ static int surface_se_tiles(const mhs_grid *g, const double *xy, const double *r
             w = se_window(fits[(size_t)q], st[(size_t)q], rho);
             ++q;
         } else w = se_window(nullptr, nullptr, 0.0);
-        se_grid_geom(w, &gf, k[0] - f[0], k[1] - f[0], k[2] - f[2], k[3] - f[2], o, k[3] - k[2]);
+        se_grid_geom(w, &gf, r0, r1, c0, c1, o, c1 - c0);
         wins.push_back(w);
     }
     void *desc = nullptr;
     int rc = se_launch(wins, s, &desc);
-    if (!rc) rc = mosaic_feather_impl(g, nRx, nCx, keep.data(), ptrs.data(), 0, out_dev, ld, nullptr, s, false);  // NA-aware
+    if (!rc) rc = mosaic_feather_impl(g, P.nRx, P.nCx, P.keep.data(), ptrs.data(), 0, out_dev, ld, nullptr, s, false);  // NA-aware
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = MHS_ERR_HIP;
     pool_release(desc);
     return rc;
@@ -639,16 +621,8 @@ int mhs_tps_predict_se_grid(const mhs_tps *t, const mhs_grid *g, int64_t r0, int
     MHS_REQUIRE(t && g && out_host, "NULL argument");
     MHS_REQUIRE(0 <= r0 && r0 <= r1 && 0 <= c0 && c0 <= c1, "bad window");
     const int64_t nr = r1 - r0, nc = c1 - c0;
-    // the plane comes from the library's persistent arena and is written on its own stream (mhs_tps_predict_grid)
-    std::lock_guard<std::mutex> lk(pipe_mutex());
-    if (int rc = host_pipe(sizeof(double) * (size_t)std::max<int64_t>(1, nr * nc))) return rc;
-    double *buf = (double *)ctx().pipe_arena;
-    hipStream_t s = ctx().pipe_comp;
-    if (int rc = mhs_tps_predict_se_grid_dev(t, g, r0, r1, c0, c1, sigma2, buf, std::max<int64_t>(nc, 1), s)) return rc;
-    if (nr * nc == 0) return MHS_OK;
-    MHS_HIP(hipMemcpyAsync(out_host, buf, sizeof(double) * (size_t)(nr * nc), hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipStreamSynchronize(s));
-    return MHS_OK;
+    return plane_to_host(nr, nc, out_host, [&](double *buf, hipStream_t s) {      // an empty window is still validated by the _dev twin
+        return mhs_tps_predict_se_grid_dev(t, g, r0, r1, c0, c1, sigma2, buf, std::max<int64_t>(nc, 1), s); });
 }
 
 int mhs_tps_predict_se_points(const mhs_tps *t, const double *xy, int64_t n, double sigma2, double *out_host) {
@@ -680,12 +654,11 @@ int mhs_tps_surface_se_dev(const mhs_grid *g, const double *xy, const double *re
                            void *stream) {
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(g && xy && resid && out_dev && n > 0 && ld >= g->ncol, "bad arguments");
-    int64_t nRx = 1, nCx = 1;
-    if (tile_edge > 0)
-        if (int rc = mhs_step3_tile_windows(g, tile_edge, 0.2, 0.025, &nRx, &nCx, nullptr, nullptr, 0)) return rc;
-    if (tiles_out) { tiles_out[0] = nRx; tiles_out[1] = nCx; }
+    Step3Plan P;
+    if (int rc = step3_plan(g, tile_edge, P)) return rc;
+    if (tiles_out) { tiles_out[0] = P.nRx; tiles_out[1] = P.nCx; }
     hipStream_t s = pick_stream(stream);
-    if (nRx * nCx == 1) {  // V73:748-753: the global fit
+    if (P.nt == 1) {  // V73:748-753: the global fit
         mhs_tps *t = nullptr;
         if (int rc = mhs_tps_fit(xy, resid, n, lambda, gcv_mode, &t)) return rc;
         int rc = mhs_tps_predict_se_grid_dev(t, g, 0, g->nrow, 0, g->ncol, NAN, out_dev, ld, s);
@@ -693,22 +666,15 @@ int mhs_tps_surface_se_dev(const mhs_grid *g, const double *xy, const double *re
         mhs_tps_free(t);
         return rc;
     }
-    return surface_se_tiles(g, xy, resid, n, cov1_at_stations, tile_edge, lambda, gcv_mode, out_dev, ld, nRx, nCx, s);
+    return surface_se_tiles(g, P, xy, resid, n, cov1_at_stations, lambda, gcv_mode, out_dev, ld, s);
 }
 
 int mhs_tps_surface_se(const mhs_grid *g, const double *xy, const double *resid, int64_t n, const double *cov1_at_stations,
                        int64_t tile_edge, double lambda, int gcv_mode, double *out_host, int64_t *tiles_out) {
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(g && out_host && g->nrow > 0 && g->ncol > 0, "bad arguments");
-    std::lock_guard<std::mutex> lk(pipe_mutex());
-    if (int rc = host_pipe(sizeof(double) * (size_t)(g->nrow * g->ncol))) return rc;
-    double *out = (double *)ctx().pipe_arena;
-    hipStream_t s = ctx().pipe_comp;
-    if (int rc = mhs_tps_surface_se_dev(g, xy, resid, n, cov1_at_stations, tile_edge, lambda, gcv_mode, out, g->ncol, tiles_out, s))
-        return rc;
-    MHS_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * (size_t)(g->nrow * g->ncol), hipMemcpyDeviceToHost, s));
-    MHS_HIP(hipStreamSynchronize(s));
-    return MHS_OK;
+    return plane_to_host(g->nrow, g->ncol, out_host, [&](double *out, hipStream_t s) {
+        return mhs_tps_surface_se_dev(g, xy, resid, n, cov1_at_stations, tile_edge, lambda, gcv_mode, out, g->ncol, tiles_out, s); });
 }
 
 }  // extern "C"

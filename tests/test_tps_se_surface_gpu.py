@@ -24,10 +24,12 @@ def _stations(g, n, seed, empty_box=None):
     return xy, y
 
 
-def _composed(hip, g, xy, y, tile_edge):
+def _composed(hip, g, xy, y, tile_edge, cov1=None):
     nRx, nCx, fit_win, keep_win = hip.tiles.step3_tile_windows(g, tile_edge)
     rows, cols = hip.tiles.cells_from_xy(g, xy)
     ok = rows >= 0
+    if cov1 is not None:
+        ok &= ~np.isnan(cov1)
     sels = [np.flatnonzero(ok & (rows >= f[0]) & (rows < f[1]) & (cols >= f[2]) & (cols < f[3])) for f in fit_win]
     todo = [h for h in range(nRx * nCx) if sels[h].size >= 10]
     fits = dict(zip(todo, hip.tps.fit_many([xy[sels[h]] for h in todo], [y[sels[h]] for h in todo])))
@@ -91,3 +93,30 @@ def test_estimate_plane_unchanged_by_an_se_call(hip):
     after = hip.tps_residual_surface(g, xy, y, tile_edge=80).cpu().numpy()
     assert np.isfinite(se).all()
     assert np.array_equal(before, after)
+
+
+def test_tiled_se_surface_drops_stations_on_na_covariate_cells(hip):
+    g = hip.Geometry(-78.0, -5.0, 1.0 / 120, 1.0 / 120, 200, 220)
+    xy, y = _stations(g, 400, 15)
+    cov1 = np.ones(xy.shape[0])
+    cov1[::37] = np.nan
+    got = hip.mltps.tps_residual_surface_se(g, xy, y, cov1_at_stations=cov1, tile_edge=80).cpu().numpy()
+    want, nRx, nCx, fit_win, keep_win, sels = _composed(hip, g, xy, y, 80, cov1=cov1)
+    assert nRx * nCx == 9
+    assert min(s.size for s in sels) >= 10      # no zero tile: every tile's spline is compared
+    assert not np.isnan(cov1[np.concatenate(sels)]).any()
+    assert np.isfinite(got).all()
+    assert np.array_equal(got, want.cpu().numpy())
+
+
+def test_nan_residual_station_equals_its_removal(hip):
+    g = hip.Geometry(-78.0, -5.0, 1.0 / 120, 1.0 / 120, 200, 220)
+    xy, y = _stations(g, 400, 15)
+    y = y.copy()
+    y[::41] = np.nan
+    keep = ~np.isnan(y)
+    for surface in (hip.tps_residual_surface, hip.mltps.tps_residual_surface_se):
+        got = surface(g, xy, y, tile_edge=80).cpu().numpy()
+        want = surface(g, xy[keep], y[keep], tile_edge=80).cpu().numpy()
+        assert np.isfinite(want).all()
+        assert np.array_equal(got, want)
