@@ -603,7 +603,7 @@ MHS_API int mhs_mess_points(const mhs_mess *m, const double *X, int64_t n, doubl
  * Topographic covariates from an elevation model: what the reference package's README sends its users to SAGA, GRASS and
  * terra for ("Need help with the high-resolution topography data?") -- slope, aspect, relative elevation, geomorphons.  The
  * reference has no such step.  THE RULES (this text is the specification; parity with terra, SAGA and GRASS is not pinned).
- * TWI needs flow accumulation and is not here.
+ * TWI needs flow accumulation: section "hydrology" below.
  *
  * Input: layer `layer` of an mhs_stack on an mhs_grid (int16, float32 or float64).  A cell is NA if it is NaN or equals
  * the stack's nodata; values are converted exactly to double.  Cells outside the raster count as NA.
@@ -687,6 +687,74 @@ MHS_API int mhs_relief(const mhs_grid *g, const mhs_stack *dem, int layer, const
                        int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned stats, void *out_host, int out_dtype);
 MHS_API int mhs_geomorphon(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
                            double flat_deg, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int16_t *out_host);
+
+/* ---------------------------------------------------------------- hydrology --
+ * The topographic wetness index of an elevation model (the reference package bundles a TWI.tif and sends its users to SAGA
+ * or GRASS for their own) with what it is made from: the flat-filled surface, the D8 flow direction and the flow
+ * accumulation.  The reference has no such step.  THE RULES (this text is the specification; parity with SAGA, GRASS and
+ * terra is not pinned).
+ *
+ * Input and ground units as in "terrain" above: layer `layer` of the stack, converted exactly to double, NA = NaN or the
+ * stack's nodata; mhs_terrain_units unchanged.  A call always treats the WHOLE plane -- there is no window, because a cell's
+ * fill, direction and accumulation depend on cells anywhere in the raster.
+ * Neighbours k = 0 .. 7 = E, SE, S, SW, W, NW, N, NE at the distances d_k = dx_c, g, dy, g, dx_c, g, dy, g with dx_c = dx or
+ * dx_row[row of the centre] and g = sqrt(dx_c * dx_c + dy * dy).  Cells outside the raster and NA cells are never neighbours.
+ * An OUTLET is a valid cell on the raster's outer ring or 8-adjacent to an NA cell.
+ *
+ * 1. Filled surface W (flat fill, no epsilon): the greatest surface with W = z at outlets and
+ *    W(c) = max(z(c), min_k W(k)) elsewhere -- the minimum, over the paths from c to an outlet, of the highest z on the path.
+ *    Only min and max of input values occur: W is exact and independent of the order of evaluation.  NA where z is NA.
+ * 2. Flat distance D (int32, internal): 0 at outlets and at cells with a neighbour of strictly lower W, elsewhere
+ *    1 + min D(k) over the neighbours with W(k) == W(c).  Every valid cell gets a finite D.
+ * 3. Direction (int8): with s_k = (W(c) - W(k)) / d_k, the k of the largest s_k > 0, the lowest k on ties; if there is none
+ *    and D(c) > 0, the lowest k with W(k) == W(c) and D(k) == D(c) - 1; if there is none and D(c) == 0 (an outlet with
+ *    nothing lower), -1: the water leaves.  NA cells get -2.  (W, D) falls strictly along every step, so the directions form
+ *    a forest rooted at the -1 cells.
+ * 4. Accumulation A(c) = 1 + the sum of A over the cells whose direction points at c: a count of cells, c included, kept
+ *    exactly (doubles holding integers), returned as float64 (exact below 2^53) or float32 rounded once.  NA where z is NA.
+ * 5. TWI: t = the slope_tan that rule 1 of "terrain" makes from the nine FILLED values, z_factor applied; NA where any of the
+ *    nine is NA (the raster's outer ring, beside NA cells).  L = sqrt(dx_c * dy), a = A * L,
+ *    twi = log(a / max(t, min_slope_tan)), each operation rounded once; only log can differ from another math library's.
+ *    min_slope_tan > 0 is required (tan(0.1 degree) is a common choice; the library never calls tan).
+ *
+ * W, D and A are fixed points of MONOTONE updates (W and D only fall from +inf, A only rises from 1): the library solves
+ * each tile by tile in passes (csrc/hydro.hip) and the result is the same exact function of the input whatever the
+ * schedule.  A phase (fill, flat distance, accumulation) runs passes until one changes nothing, at most max_passes of them;
+ * max_passes = 0 is the default 16 * (tile rows + tile columns) + 64 with tiles of 32 x 64 cells -- a policy cap the caller
+ * may raise, not a proof.  A phase that still changes at the cap returns MHS_ERR_NUMERIC with a message naming the phase
+ * and the cap; the outputs are then unspecified and the library stays usable.
+ * Scratch: 22 bytes per cell of stream-ordered device memory for the length of the call; MHS_ERR_ALLOC if there is none.
+ * Every argument is checked before the first device call (MHS_ERR_INVALID, the message names the argument); a plane of more
+ * than 2^56 cells is refused there too.                                                                                  */
+typedef struct mhs_hydro_out {   /* the planes to make; any may be NULL, not all */
+    void *filled;       /* W, out_dtype */
+    int8_t *flowdir;    /* 0 .. 7, -1 the water leaves, -2 NA */
+    void *flowacc;      /* A, out_dtype */
+    void *twi;          /* out_dtype */
+} mhs_hydro_out;
+typedef struct mhs_hydro_info {
+    int passes_fill, passes_flat, passes_acc;   /* passes each phase took, the last (unchanged) one included */
+    int64_t n_valid;    /* cells that are not NA */
+    int64_t n_raised;   /* cells with W > z */
+    int64_t n_sinks;    /* cells with direction -1 */
+    int64_t n_tiles;    /* tiles of 32 x 64 cells in the plane */
+    int64_t solves_fill, solves_flat, solves_acc;   /* tile solves of each phase, all passes: / (passes * n_tiles) = the share of tiles that were dirty */
+    double ms_fill, ms_flat, ms_acc;                /* host wall-clock time of each phase: its seeding kernel and the stream
+                                                     * synchronisation after every pass included -- a diagnostic (tools/hydro_speed.py),
+                                                     * not a kernel time */
+} mhs_hydro_info;
+/* DEVICE planes: dem->data covers the whole grid; every plane of `out` is nrow x ld row-major on the device, out_dtype
+ * MHS_F64 or MHS_F32 (flowdir int8).  info may be NULL.  Unlike every other _dev entry point this one does not only
+ * enqueue: the host decides after each pass whether another is needed, so it SYNCHRONISES `stream` once per pass (and
+ * cannot be captured into a graph). */
+MHS_API int mhs_hydro_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units,
+                          double min_slope_tan, int max_passes, const mhs_hydro_out *out, int out_dtype, int64_t ld,
+                          void *stream, mhs_hydro_info *info);
+/* same, HOST planes: dem->data and the planes of `out` (nrow x ncol dense) on the host -- what the R shim hands over.  The
+ * whole plane goes up and the requested planes come down; no row bands, because the problem is not local.  Blocks until
+ * done. */
+MHS_API int mhs_hydro(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, double min_slope_tan,
+                      int max_passes, const mhs_hydro_out *out, int out_dtype, mhs_hydro_info *info);
 
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;

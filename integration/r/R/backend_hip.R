@@ -166,6 +166,34 @@ mhs_terrain <- function(dem.ras, v = "slope_deg", radius = 17L, search = 10L, fl
   out
 }
 
+# ---- the topographic wetness index of the DEM (the package bundles a TWI.tif and sends its users to SAGA or GRASS for
+# their own) and what it is made from --------------------------------------------------------------------------------------
+# v: any of "filled" (the flat-filled surface), "flowdir" (D8: 0 .. 7 = E, SE, S, SW, W, NW, N, NE, -1 where the water leaves
+# the raster), "flowacc" (cells draining through the cell, itself included) and "twi" = log(flowacc * sqrt(dx * dy) /
+# max(slope of the filled surface, tan(min.slope.deg))).  Always the whole raster: flow accumulation is not local.  Returns a
+# SpatRaster with one layer per entry of v; attr(, "info") holds the passes each phase took and the counts of valid, raised
+# and sink cells.  max.passes = 0 is the library's cap on the passes of a phase (an error names the phase that reaches it).
+.mhs_hydro_products <- c("filled", "flowdir", "flowacc", "twi")
+mhs_hydro <- function(dem.ras, v = "twi", min.slope.deg = 0.1, max.passes = 0L, z.factor = 1, lonlat = terra::is.lonlat(dem.ras)) {
+  bad <- setdiff(v, .mhs_hydro_products)
+  if (length(bad) || !length(v)) stop("mhs_hydro: v must name some of ", paste(.mhs_hydro_products, collapse = ", "))
+  res <- terra::res(dem.ras)
+  if (isTRUE(lonlat)) {
+    lat <- terra::yFromRow(dem.ras, seq_len(terra::nrow(dem.ras)))
+    dx.row <- res[1] * (pi / 180) * 6378137 * cos(lat * (pi / 180))
+    units <- c(NA_real_, res[2] * (pi / 180) * 6378137, z.factor)
+  } else {
+    dx.row <- NULL
+    units <- c(res[1], res[2], z.factor)
+  }
+  h <- .Call("mhsr_hydro", .mhs_geom(dem.ras), as.numeric(terra::values(dem.ras[[1]])), units, dx.row,
+             as.integer(sum(2^(match(unique(v), .mhs_hydro_products) - 1))), c(tan(min.slope.deg * (pi / 180)), as.numeric(max.passes)))
+  out <- do.call(c, lapply(v, function(n) terra::setValues(terra::rast(dem.ras[[1]]), h[[match(n, .mhs_hydro_products)]])))
+  names(out) <- v
+  attr(out, "info") <- stats::setNames(h[[5]], c("passes_fill", "passes_flat", "passes_acc", "n_valid", "n_raised", "n_sinks"))
+  out
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

@@ -293,6 +293,43 @@ SEXP mhsr_geomorphon(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP search, 
     return out;
 }
 
+/* Hydrology of the DEM (machisplin_hip.h "hydrology"): the bundled TWI.tif's recipe.  products: bit mask (1 filled, 2 flowdir,
+ * 4 flowacc, 8 twi); opts: c(min_slope_tan, max_passes).  Returns list(filled, flowdir, flowacc, twi, info) in terra cell order,
+ * NULL where a plane was not asked for: numeric vectors (NaN at NA cells), flowdir an integer vector (0 .. 7 = E, SE, S, SW, W,
+ * NW, N, NE, -1 the water leaves, NA_integer_ at NA cells), info = c(passes_fill, passes_flat, passes_acc, n_valid, n_raised,
+ * n_sinks).  Runs on the HOST entry point: the whole plane goes up, there are no row bands. */
+SEXP mhsr_hydro(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP products, SEXP opts) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_hydro");
+    mhs_terrain_units u = units_from(units, dx_row, &g, "mhsr_hydro");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 15) Rf_error("mhsr_hydro: products must be a bit mask of 1 filled, 2 flowdir, 4 flowacc, 8 twi");
+    if (Rf_length(opts) != 2) Rf_error("mhsr_hydro: opts must be c(min_slope_tan, max_passes)");
+    if (!(REAL(opts)[1] >= 0.0 && REAL(opts)[1] <= 2147483647.0)) Rf_error("mhsr_hydro: max_passes must be 0 (the default cap) or a positive count");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 5));
+    SEXP plane[4] = { R_NilValue, R_NilValue, R_NilValue, R_NilValue };
+    int n_protect = 1;
+    for (int k = 0; k < 4; ++k)
+        if (mask & (1 << k)) { plane[k] = PROTECT(Rf_allocVector(k == 1 ? INTSXP : REALSXP, n)); ++n_protect; }
+    int8_t *dirs = (mask & 2) ? (int8_t *)R_alloc((size_t)(n ? n : 1), sizeof(int8_t)) : NULL;
+    mhs_hydro_out o = { (mask & 1) ? REAL(plane[0]) : NULL, dirs, (mask & 4) ? REAL(plane[2]) : NULL, (mask & 8) ? REAL(plane[3]) : NULL };
+    mhs_hydro_info info = { 0 };
+    int rc = mhs_hydro(&g, &st, 0, &u, REAL(opts)[0], (int)REAL(opts)[1], &o, MHS_F64, &info);
+    if (rc == MHS_OK) {
+        if (dirs)
+            for (R_xlen_t k = 0; k < n; ++k) INTEGER(plane[1])[k] = dirs[k] == -2 ? NA_INTEGER : (int)dirs[k];
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 6)); ++n_protect;
+        REAL(inf)[0] = info.passes_fill; REAL(inf)[1] = info.passes_flat; REAL(inf)[2] = info.passes_acc;
+        REAL(inf)[3] = (double)info.n_valid; REAL(inf)[4] = (double)info.n_raised; REAL(inf)[5] = (double)info.n_sinks;
+        for (int k = 0; k < 4; ++k) SET_VECTOR_ELT(out, k, plane[k]);
+        SET_VECTOR_ELT(out, 4, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

@@ -71,6 +71,18 @@ class TerrainUnits(C.Structure):
     _fields_ = [("dx", C.c_double), ("dx_row", C.c_void_p), ("dy", C.c_double), ("z_factor", C.c_double)]
 
 
+class HydroOut(C.Structure):
+    """struct mhs_hydro_out"""
+    _fields_ = [("filled", C.c_void_p), ("flowdir", C.c_void_p), ("flowacc", C.c_void_p), ("twi", C.c_void_p)]
+
+
+class HydroInfo(C.Structure):
+    """struct mhs_hydro_info"""
+    _fields_ = [("passes_fill", C.c_int), ("passes_flat", C.c_int), ("passes_acc", C.c_int), ("n_valid", C.c_int64),
+                ("n_raised", C.c_int64), ("n_sinks", C.c_int64), ("n_tiles", C.c_int64), ("solves_fill", C.c_int64),
+                ("solves_flat", C.c_int64), ("solves_acc", C.c_int64), ("ms_fill", C.c_double), ("ms_flat", C.c_double), ("ms_acc", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -169,6 +181,10 @@ SIGNATURES = {
                              _vp, C.c_int]),
     "mhs_geomorphon": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.c_double, _i64, _i64, _i64,
                                  _i64, _vp]),
+    "mhs_hydro_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int,
+                                C.POINTER(HydroOut), C.c_int, _i64, _vp, C.POINTER(HydroInfo)]),
+    "mhs_hydro": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int,
+                            C.POINTER(HydroOut), C.c_int, C.POINTER(HydroInfo)]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

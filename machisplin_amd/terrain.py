@@ -2,9 +2,11 @@
 
 What the reference package's README sends its users to SAGA, GRASS and terra for ("Need help with the high-resolution
 topography data?"): the covariate rasters derived from the DEM -- ``slope``, ``rel_alt`` / ``relative_elevation500m`` and
-their kin (TWI needs flow accumulation and is not here).  include/machisplin_hip.h, section "terrain", states the rules.
-All arithmetic runs in libmachisplin_hip.so (csrc/terrain.hip); this module only marshals arguments -- and, for a lon/lat
-raster, makes the rows' ground widths with numpy, because the library never calls cos.
+their kin -- and ``TWI``, with the filled surface, the D8 flow direction and the flow accumulation it is made from
+(:func:`hydro`).  include/machisplin_hip.h, sections "terrain" and "hydrology", states the rules.
+All arithmetic runs in libmachisplin_hip.so (csrc/terrain.hip, csrc/hydro.hip); this module only marshals arguments -- and,
+for a lon/lat raster, makes the rows' ground widths with numpy, because the library never calls cos (nor tan: the slope floor
+of the wetness index is made here too).
 """
 from __future__ import annotations
 
@@ -18,6 +20,8 @@ from .raster import RasterStack
 VARS = ("dzdx", "dzdy", "slope_tan", "slope_deg", "eastness", "northness", "aspect_deg", "tpi", "tri", "roughness")
 STATS = ("above_min", "below_max", "minus_mean")
 FORMS = ("flat", "peak", "ridge", "shoulder", "spur", "slope", "hollow", "footslope", "valley", "pit")       # codes 1 .. 10
+HYDRO = ("filled", "flowdir", "flowacc", "twi")                     # the planes of mhs_hydro_out, in its order
+HYDRO_SPEC = {"twi": ("twi", False), "log_flowacc": ("flowacc", True)}      # covariates(): spec name -> (product, take its log)
 GEOMORPHON_NA = -32768
 EARTH_RADIUS = 6378137.0
 
@@ -142,12 +146,59 @@ def geomorphon(stack: RasterStack, search, flat_deg=1.0, layer=0, lonlat=False, 
     return out
 
 
+class HydroResult(dict):
+    """what :func:`hydro` returns for several products: the planes by name, and ``.info``"""
+    info = None
+
+
+def hydro(stack: RasterStack, layer=0, products=("twi",), lonlat=False, z_factor=1.0, min_slope_deg=0.1, max_passes=0, out_dtype=None,
+          stream=None, dx=None, dy=None, dx_row=None):
+    """Hydrology of layer ``layer`` (include/machisplin_hip.h, section "hydrology"): ``products`` names some of
+    :data:`HYDRO` -- ``filled`` (the flat-filled surface), ``flowdir`` (int8: 0 .. 7 = E, SE, S, SW, W, NW, N, NE, -1 the
+    water leaves, -2 NA), ``flowacc`` (cells draining through the cell, itself included) and ``twi`` =
+    log(flowacc sqrt(dx dy) / max(slope_tan of the filled surface, tan(min_slope_deg))).  Always the whole plane: there is no
+    window, flow accumulation is not local.  Returns ``(planes, info)``: a dict of device tensors by name (``.info`` too) --
+    or the single tensor when ``products`` is one name -- and the call's counts, a dict of the fields of mhs_hydro_info.
+    ``max_passes`` = 0 is the library's cap on the passes of a phase; MhsError (ERR_NUMERIC) when a phase reaches it.
+    The call synchronises ``stream`` once per pass."""
+    import torch
+    one = isinstance(products, str)
+    names = (products,) if one else tuple(products)
+    for n in names:
+        if n not in HYDRO:
+            raise ValueError(f"unknown product {n!r}: one of {', '.join(HYDRO)}")
+    if not names or len(set(names)) != len(names):
+        raise ValueError("give every product once")
+    out_dtype = out_dtype or torch.float64
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError("out_dtype must be torch.float64 or torch.float32")
+    if not min_slope_deg > 0.0:
+        raise ValueError("min_slope_deg must be positive")
+    g = stack.geom
+    units = ground_units(g, lonlat, z_factor, dx, dy, dx_row)
+    planes = {n: torch.empty((g.nrow, g.ncol), dtype=torch.int8 if n == "flowdir" else out_dtype, device=stack.planes.device) for n in names}
+    out = _lib.HydroOut(*[planes[n].data_ptr() if n in planes else None for n in HYDRO])
+    info = _lib.HydroInfo()
+    cg, cs, cu = g.c_struct(), stack.c_struct(), _c_units(units)
+    _lib.check(_lib.lib().mhs_hydro_dev(C.byref(cg), C.byref(cs), int(layer), C.byref(cu), float(np.tan(np.deg2rad(min_slope_deg))),
+                                        int(max_passes), C.byref(out), _lib.F64 if out_dtype == torch.float64 else _lib.F32, g.ncol,
+                                        _stream(stack, stream), C.byref(info)))
+    info = {k: getattr(info, k) for k, _ in _lib.HydroInfo._fields_}          # counts are ints, the phases' ms floats
+    if one:
+        return planes[names[0]], info
+    res = HydroResult(planes)
+    res.info = info
+    return res, info
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
       a name of :data:`VARS`                      that 3 x 3 variable (all of them in one pass)
       (a name of :data:`STATS`, radius)           that relief statistic in a window of ``radius`` cells
       ("geomorphon", search[, flat_deg])          the geomorphon code (1 .. 10)
+      "twi"                                       the topographic wetness index (:func:`hydro`, its defaults)
+      "log_flowacc"                               log of the flow accumulation, taken by torch on the float64 plane
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -159,10 +210,17 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
         demf = torch.where(dem == dem_stack.nodata, torch.full_like(demf, float("nan")), demf)
     planes[0] = demf
     names = ["dem"]
-    tv = [e[0] for e in spec if len(e) == 1]
+    by_name = {}
+    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
-        by_name = dict(zip(dict.fromkeys(tv), got))
+        by_name.update(zip(dict.fromkeys(tv), got))
+    hv = [e[0] for e in spec if len(e) == 1 and e[0] in HYDRO_SPEC]
+    if hv:                                        # one hydrology call makes both
+        hp, _ = hydro(dem_stack, layer, tuple(dict.fromkeys(HYDRO_SPEC[n][0] for n in hv)), lonlat, z_factor)
+        for n in hv:
+            product, log = HYDRO_SPEC[n]
+            by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
     for k, e in enumerate(spec):
         if len(e) == 1:
             planes[1 + k] = by_name[e[0]]
