@@ -756,6 +756,52 @@ MHS_API int mhs_hydro_dev(const mhs_grid *g, const mhs_stack *dem, int layer, co
 MHS_API int mhs_hydro(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, double min_slope_tan,
                       int max_passes, const mhs_hydro_out *out, int out_dtype, mhs_hydro_info *info);
 
+/* ------------------------------------- hydrology, multiple flow direction --
+ * The same, with the water of a cell SHARED among all its lower neighbours in proportion to a power of the slope (Freeman
+ * 1991, Holmgren 1994; SAGA's catchment area and the bundled TWI.tif use it with the exponent 1.1) instead of sent to one:
+ * a smooth, dispersive accumulation without D8's parallel one-cell streaks.  Input, ground units, neighbours k = 0 .. 7,
+ * the distances d_k, outlets, and rules 1 and 2 (W, D) are those of "hydrology".  `exponent` = x is checked: finite,
+ * 0 < x <= 64, else MHS_ERR_INVALID naming it.
+ *
+ * 6. Shares of a valid cell c, the donor (d_k with the width of c's OWN row): s_k = (W(c) - W(k)) / d_k for the neighbours k,
+ *    s_max = the largest s_k.
+ *    If s_max > 0 (c is steep): p_k = s_k / s_max where s_k > 0, else 0; if x != 1, p_k = pow(p_k, x) (pow is not called when
+ *    x == 1, nor for p_k = 0 and p_k = 1, which it leaves as they are); S = p_0 + ... + p_7 in k order -- S >= 1, because the
+ *    steepest neighbour has p = 1 exactly, so no water can underflow away --; f(c -> k) = p_k / S.
+ *    Else if D(c) > 0: the m neighbours with W(k) == W(c) and D(k) == D(c) - 1 get f = 1 / m each (m >= 1 by rule 2).
+ *    Else (an outlet with nothing lower): no shares, the water leaves.  These are the cells that rule 3 gives the direction
+ *    -1, and n_sinks counts them.
+ *    (W, D) falls strictly along every positive share: the flow graph is acyclic.
+ * 7. Accumulation A(c) = 1 + the sum over k = 0 .. 7 of f(k -> c) * A(k), over the neighbours k with f(k -> c) > 0: product
+ *    first, then the add, in k order, each rounded once.  A is held as a double, NA where z is NA, returned as float64 or as
+ *    float32 rounded once.  The sum of A over the cells without shares is the number of valid cells, to rounding.
+ * 8. TWI: rule 5 with this A (the slope from the nine filled values, L = sqrt(dx_c * dy), the same min_slope_tan).
+ *
+ * With x = 1 only subtraction, division, multiplication and sums occur, and a restatement in another language gives the
+ * same bits for A; for other x the shares go through pow, and the TWI through log.
+ * The shares are static and >= 0 and rounding is monotone, so the iteration of rule 7 from A = 1 only rises; the graph is
+ * acyclic, so its fixed point is unique -- the value one walk in topological order gives -- and a cell is final one sweep
+ * after its donors are: the result is the same exact function of the input whatever the schedule, as in "hydrology".
+ * max_passes, the pass cap policy, MHS_ERR_NUMERIC at the cap (the message names the phase: fill, flat distance or
+ * accumulation), MHS_ERR_ALLOC and the checking of every argument before the first device call are those of "hydrology".
+ * mhs_hydro_info is filled the same way; passes_acc, solves_acc and ms_acc refer to the MFD accumulation (the shares kernel
+ * included).
+ * Scratch: 85 bytes per cell of stream-ordered device memory for the length of the call (W 8, D 4, A 8, flags 1, and the
+ * eight incoming shares of the cell as doubles, 64), plus 2 bytes per tile and dx_row.                                     */
+typedef struct mhs_hydro_mfd_out {   /* the planes to make; any may be NULL, not all */
+    void *filled;       /* W, out_dtype */
+    void *flowacc;      /* A, out_dtype */
+    void *twi;          /* out_dtype */
+} mhs_hydro_mfd_out;
+/* DEVICE planes, as mhs_hydro_dev: every plane of `out` is nrow x ld row-major on the device; synchronises `stream` once per
+ * pass.  info may be NULL. */
+MHS_API int mhs_hydro_mfd_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units,
+                              double min_slope_tan, int max_passes, double exponent, const mhs_hydro_mfd_out *out, int out_dtype,
+                              int64_t ld, void *stream, mhs_hydro_info *info);
+/* same, HOST planes (nrow x ncol dense), as mhs_hydro.  Blocks until done. */
+MHS_API int mhs_hydro_mfd(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, double min_slope_tan,
+                          int max_passes, double exponent, const mhs_hydro_mfd_out *out, int out_dtype, mhs_hydro_info *info);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

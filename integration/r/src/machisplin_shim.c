@@ -330,6 +330,39 @@ SEXP mhsr_hydro(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP products, SEX
     return out;
 }
 
+/* The same with multiple flow direction (machisplin_hip.h "hydrology, multiple flow direction": what SAGA makes the bundled
+ * TWI.tif with).  products: bit mask (1 filled, 2 flowacc, 4 twi); opts: c(min_slope_tan, max_passes, exponent).  Returns
+ * list(filled, flowacc, twi, info), NULL where a plane was not asked for; info as mhsr_hydro's, passes_acc of the MFD
+ * accumulation. */
+SEXP mhsr_hydro_mfd(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP products, SEXP opts) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_hydro_mfd");
+    mhs_terrain_units u = units_from(units, dx_row, &g, "mhsr_hydro_mfd");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 7) Rf_error("mhsr_hydro_mfd: products must be a bit mask of 1 filled, 2 flowacc, 4 twi");
+    if (Rf_length(opts) != 3) Rf_error("mhsr_hydro_mfd: opts must be c(min_slope_tan, max_passes, exponent)");
+    if (!(REAL(opts)[1] >= 0.0 && REAL(opts)[1] <= 2147483647.0)) Rf_error("mhsr_hydro_mfd: max_passes must be 0 (the default cap) or a positive count");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 4));
+    SEXP plane[3] = { R_NilValue, R_NilValue, R_NilValue };
+    int n_protect = 1;
+    for (int k = 0; k < 3; ++k)
+        if (mask & (1 << k)) { plane[k] = PROTECT(Rf_allocVector(REALSXP, n)); ++n_protect; }
+    mhs_hydro_mfd_out o = { (mask & 1) ? REAL(plane[0]) : NULL, (mask & 2) ? REAL(plane[1]) : NULL, (mask & 4) ? REAL(plane[2]) : NULL };
+    mhs_hydro_info info = { 0 };
+    int rc = mhs_hydro_mfd(&g, &st, 0, &u, REAL(opts)[0], (int)REAL(opts)[1], REAL(opts)[2], &o, MHS_F64, &info);
+    if (rc == MHS_OK) {
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 6)); ++n_protect;
+        REAL(inf)[0] = info.passes_fill; REAL(inf)[1] = info.passes_flat; REAL(inf)[2] = info.passes_acc;
+        REAL(inf)[3] = (double)info.n_valid; REAL(inf)[4] = (double)info.n_raised; REAL(inf)[5] = (double)info.n_sinks;
+        for (int k = 0; k < 3; ++k) SET_VECTOR_ELT(out, k, plane[k]);
+        SET_VECTOR_ELT(out, 3, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

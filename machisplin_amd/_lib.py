@@ -76,6 +76,11 @@ class HydroOut(C.Structure):
     _fields_ = [("filled", C.c_void_p), ("flowdir", C.c_void_p), ("flowacc", C.c_void_p), ("twi", C.c_void_p)]
 
 
+class HydroMfdOut(C.Structure):
+    """struct mhs_hydro_mfd_out"""
+    _fields_ = [("filled", C.c_void_p), ("flowacc", C.c_void_p), ("twi", C.c_void_p)]
+
+
 class HydroInfo(C.Structure):
     """struct mhs_hydro_info"""
     _fields_ = [("passes_fill", C.c_int), ("passes_flat", C.c_int), ("passes_acc", C.c_int), ("n_valid", C.c_int64),
@@ -185,6 +190,10 @@ SIGNATURES = {
                                 C.POINTER(HydroOut), C.c_int, _i64, _vp, C.POINTER(HydroInfo)]),
     "mhs_hydro": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int,
                             C.POINTER(HydroOut), C.c_int, C.POINTER(HydroInfo)]),
+    "mhs_hydro_mfd_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int, C.c_double,
+                                    C.POINTER(HydroMfdOut), C.c_int, _i64, _vp, C.POINTER(HydroInfo)]),
+    "mhs_hydro_mfd": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int, C.c_double,
+                                C.POINTER(HydroMfdOut), C.c_int, C.POINTER(HydroInfo)]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

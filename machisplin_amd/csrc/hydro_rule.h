@@ -2,7 +2,9 @@
 // accumulation and the topographic wetness index of one elevation plane.  Free of any HIP header: the kernels of hydro.hip and
 // a plain C++ check program (tests/hydro_check.cpp) share it.  The header states the rules; the operations stand here in that
 // order, each rounded once (the library is built with -ffp-contract=off), so a numpy restatement gives the same bits -- except
-// through log, which no two math libraries need round alike.
+// through log, which no two math libraries need round alike.  Rules 6 and 7 (section "hydrology, multiple flow direction":
+// the shares and the accumulation over them; tests/hydro_mfd_check.cpp) follow the five; there pow joins log unless the
+// exponent is 1.
 //
 // A rule sees the eight neighbours of its cell as arrays indexed by k = 0 .. 7 = E, SE, S, SW, W, NW, N, NE:
 //   wn[k]   the neighbour's filled value W, NaN where that cell is outside the raster or NA ("not a neighbour")
@@ -104,6 +106,54 @@ MHS_TERRAIN_HD inline double hydro_twi(const double w9[9], double acc, double dx
     const double len = sqrt(dx * dy);
     const double a = acc * len;
     return log(a / (t > min_slope_tan ? t : min_slope_tan));
+}
+
+// The rules of section "hydrology, multiple flow direction".  Rules 1 and 2 (W, D) are the ones above.
+constexpr double HYDRO_MFD_MAX_EXPONENT = 64.0;
+
+// 6. SHARES of a valid cell, the DONOR: f[k] = the part of its water that goes to neighbour k, dx = the width of the donor's
+// row.  Steep (some s_k > 0): p_k = s_k / s_max, raised to x unless x == 1, over their sum in k order; else D > 0: 1 / m to each
+// of the m neighbours of equal W one step nearer the flat's exit; else none (false): the water leaves.  pow is called only
+// for 0 < p_k < 1: pow(0, x) = 0 and pow(1, x) = 1 exactly, so the steepest neighbour has p = 1 and the sum is >= 1.
+MHS_TERRAIN_HD inline bool hydro_mfd_shares(double w, int32_t dist, const double wn[8], const int32_t dn[8], double dx, double dy, double x,
+                                            double f[8]) {
+    double d[8], s[8];
+    hydro_distances(dx, dy, d);
+    double s_max = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        s[k] = (w - wn[k]) / d[k];                              // NaN where there is no neighbour
+        if (s[k] > s_max) s_max = s[k];
+    }
+    if (s_max > 0.0) {
+        double sum = 0.0;
+        for (int k = 0; k < 8; ++k) {
+            double p = s[k] > 0.0 ? s[k] / s_max : 0.0;
+            if (x != 1.0 && p > 0.0 && p < 1.0) p = pow(p, x);
+            f[k] = p;
+            sum = sum + p;
+        }
+        for (int k = 0; k < 8; ++k) f[k] = f[k] / sum;
+        return true;
+    }
+    int m = 0;
+    for (int k = 0; k < 8; ++k) {
+        f[k] = 0.0;
+        m += (dist > 0 && wn[k] == w && dn[k] == dist - 1) ? 1 : 0;
+    }
+    if (m == 0) return false;
+    const double each = 1.0 / (double)m;
+    for (int k = 0; k < 8; ++k)
+        if (wn[k] == w && dn[k] == dist - 1) f[k] = each;
+    return true;
+}
+
+// 7. one step of the MFD ACCUMULATION: fin[k] = f(k -> c), the share neighbour k sends to the cell (0 where it sends none or
+// is no neighbour); product first, then the add, in k order
+MHS_TERRAIN_HD inline double hydro_mfd_step(const double fin[8], const double an[8]) {
+    double a = 1.0;
+    for (int k = 0; k < 8; ++k)
+        if (fin[k] > 0.0) a = a + fin[k] * an[k];
+    return a;
 }
 
 }  // namespace mhs

@@ -3,7 +3,8 @@
 What the reference package's README sends its users to SAGA, GRASS and terra for ("Need help with the high-resolution
 topography data?"): the covariate rasters derived from the DEM -- ``slope``, ``rel_alt`` / ``relative_elevation500m`` and
 their kin -- and ``TWI``, with the filled surface, the D8 flow direction and the flow accumulation it is made from
-(:func:`hydro`).  include/machisplin_hip.h, sections "terrain" and "hydrology", states the rules.
+(:func:`hydro`), or with the multiple-flow-direction accumulation SAGA makes it from (:func:`hydro_mfd`).
+include/machisplin_hip.h, sections "terrain", "hydrology" and "hydrology, multiple flow direction", states the rules.
 All arithmetic runs in libmachisplin_hip.so (csrc/terrain.hip, csrc/hydro.hip); this module only marshals arguments -- and,
 for a lon/lat raster, makes the rows' ground widths with numpy, because the library never calls cos (nor tan: the slope floor
 of the wetness index is made here too).
@@ -22,6 +23,8 @@ STATS = ("above_min", "below_max", "minus_mean")
 FORMS = ("flat", "peak", "ridge", "shoulder", "spur", "slope", "hollow", "footslope", "valley", "pit")       # codes 1 .. 10
 HYDRO = ("filled", "flowdir", "flowacc", "twi")                     # the planes of mhs_hydro_out, in its order
 HYDRO_SPEC = {"twi": ("twi", False), "log_flowacc": ("flowacc", True)}      # covariates(): spec name -> (product, take its log)
+HYDRO_MFD = ("filled", "flowacc", "twi")                            # the planes of mhs_hydro_mfd_out, in its order
+HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True)}      # the same, made by hydro_mfd at its defaults
 GEOMORPHON_NA = -32768
 EARTH_RADIUS = 6378137.0
 
@@ -161,12 +164,28 @@ def hydro(stack: RasterStack, layer=0, products=("twi",), lonlat=False, z_factor
     or the single tensor when ``products`` is one name -- and the call's counts, a dict of the fields of mhs_hydro_info.
     ``max_passes`` = 0 is the library's cap on the passes of a phase; MhsError (ERR_NUMERIC) when a phase reaches it.
     The call synchronises ``stream`` once per pass."""
+    return _hydro(stack, layer, products, None, lonlat, z_factor, min_slope_deg, max_passes, out_dtype, stream, dx, dy, dx_row)
+
+
+def hydro_mfd(stack: RasterStack, layer=0, products=("twi",), exponent=1.1, lonlat=False, z_factor=1.0, min_slope_deg=0.1, max_passes=0,
+              out_dtype=None, stream=None, dx=None, dy=None, dx_row=None):
+    """Hydrology of layer ``layer`` with MULTIPLE FLOW DIRECTION (include/machisplin_hip.h, section "hydrology, multiple
+    flow direction"): a cell shares its water among all its lower neighbours in proportion to slope ** ``exponent`` (Freeman
+    1991, Holmgren 1994; 1.1 is SAGA's default, 0 < exponent <= 64) where :func:`hydro` sends all of it to the steepest.
+    ``products`` names some of :data:`HYDRO_MFD`: ``filled``, ``flowacc`` (a real number >= 1) and ``twi``.  Everything
+    else, and what is returned, as in :func:`hydro`; the info's ``*_acc`` fields refer to the MFD accumulation."""
+    return _hydro(stack, layer, products, float(exponent), lonlat, z_factor, min_slope_deg, max_passes, out_dtype, stream, dx, dy, dx_row)
+
+
+def _hydro(stack, layer, products, exponent, lonlat, z_factor, min_slope_deg, max_passes, out_dtype, stream, dx, dy, dx_row):
+    """:func:`hydro` (``exponent`` None: mhs_hydro_dev) and :func:`hydro_mfd` (mhs_hydro_mfd_dev)"""
     import torch
+    table = HYDRO if exponent is None else HYDRO_MFD
     one = isinstance(products, str)
     names = (products,) if one else tuple(products)
     for n in names:
-        if n not in HYDRO:
-            raise ValueError(f"unknown product {n!r}: one of {', '.join(HYDRO)}")
+        if n not in table:
+            raise ValueError(f"unknown product {n!r}: one of {', '.join(table)}")
     if not names or len(set(names)) != len(names):
         raise ValueError("give every product once")
     out_dtype = out_dtype or torch.float64
@@ -177,12 +196,17 @@ def hydro(stack: RasterStack, layer=0, products=("twi",), lonlat=False, z_factor
     g = stack.geom
     units = ground_units(g, lonlat, z_factor, dx, dy, dx_row)
     planes = {n: torch.empty((g.nrow, g.ncol), dtype=torch.int8 if n == "flowdir" else out_dtype, device=stack.planes.device) for n in names}
-    out = _lib.HydroOut(*[planes[n].data_ptr() if n in planes else None for n in HYDRO])
+    ptrs = [planes[n].data_ptr() if n in planes else None for n in table]
     info = _lib.HydroInfo()
     cg, cs, cu = g.c_struct(), stack.c_struct(), _c_units(units)
-    _lib.check(_lib.lib().mhs_hydro_dev(C.byref(cg), C.byref(cs), int(layer), C.byref(cu), float(np.tan(np.deg2rad(min_slope_deg))),
-                                        int(max_passes), C.byref(out), _lib.F64 if out_dtype == torch.float64 else _lib.F32, g.ncol,
-                                        _stream(stack, stream), C.byref(info)))
+    head = (C.byref(cg), C.byref(cs), int(layer), C.byref(cu), float(np.tan(np.deg2rad(min_slope_deg))), int(max_passes))
+    tail = (_lib.F64 if out_dtype == torch.float64 else _lib.F32, g.ncol, _stream(stack, stream), C.byref(info))
+    if exponent is None:
+        out = _lib.HydroOut(*ptrs)
+        _lib.check(_lib.lib().mhs_hydro_dev(*head, C.byref(out), *tail))
+    else:
+        out = _lib.HydroMfdOut(*ptrs)
+        _lib.check(_lib.lib().mhs_hydro_mfd_dev(*head, exponent, C.byref(out), *tail))
     info = {k: getattr(info, k) for k, _ in _lib.HydroInfo._fields_}          # counts are ints, the phases' ms floats
     if one:
         return planes[names[0]], info
@@ -199,6 +223,7 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       ("geomorphon", search[, flat_deg])          the geomorphon code (1 .. 10)
       "twi"                                       the topographic wetness index (:func:`hydro`, its defaults)
       "log_flowacc"                               log of the flow accumulation, taken by torch on the float64 plane
+      "twi_mfd", "log_flowacc_mfd"                the same two with multiple flow direction (:func:`hydro_mfd`, its defaults)
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -211,16 +236,17 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     planes[0] = demf
     names = ["dem"]
     by_name = {}
-    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC]
+    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
-    hv = [e[0] for e in spec if len(e) == 1 and e[0] in HYDRO_SPEC]
-    if hv:                                        # one hydrology call makes both
-        hp, _ = hydro(dem_stack, layer, tuple(dict.fromkeys(HYDRO_SPEC[n][0] for n in hv)), lonlat, z_factor)
-        for n in hv:
-            product, log = HYDRO_SPEC[n]
-            by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
+    for table, call in ((HYDRO_SPEC, hydro), (HYDRO_MFD_SPEC, hydro_mfd)):
+        hv = [e[0] for e in spec if len(e) == 1 and e[0] in table]
+        if hv:                                    # one hydrology call of a route makes both of its layers
+            hp, _ = call(dem_stack, layer, tuple(dict.fromkeys(table[n][0] for n in hv)), lonlat=lonlat, z_factor=z_factor)
+            for n in hv:
+                product, log = table[n]
+                by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
     for k, e in enumerate(spec):
         if len(e) == 1:
             planes[1 + k] = by_name[e[0]]
