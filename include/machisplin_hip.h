@@ -688,6 +688,78 @@ MHS_API int mhs_relief(const mhs_grid *g, const mhs_stack *dem, int layer, const
 MHS_API int mhs_geomorphon(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
                            double flat_deg, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int16_t *out_host);
 
+/* -------------------------------------------------------------------- solar --
+ * Radiation covariates from an elevation model: the local horizon, the sky-view factor (how much sky a cell sees: night-time
+ * cooling, cold-air pooling), potential direct insolation (clear-sky beam energy on the tilted cell, shadowed by the
+ * surrounding relief) and sun hours -- SAGA's "Potential Incoming Solar Radiation" and "Sky View Factor", GRASS's r.horizon
+ * and r.sun.  The reference has no such step.  THE RULES (this text is the specification; parity with SAGA and GRASS is not
+ * pinned).
+ *
+ * Input, NA, ground units (mhs_terrain_units: dx / dx_row / dy / z_factor) and the window are those of "terrain".  The device
+ * does only + - * /, sqrt and comparisons, each in the order written and rounded once: NO atan, sin, cos, pow, exp or log.
+ * Every plane is therefore an exact function of the input and a numpy restatement gives the same bits, every product
+ * included.  All trigonometry is the caller's: it comes in through the sun tables of (c).
+ *
+ * (a) Sixteen rays.  Direction j = 0 .. 15, clockwise from north, with integer step vectors (dr rows south, dc columns east):
+ *       0 N (-1, 0)     1 NNE (-2, 1)    2 NE (-1, 1)     3 ENE (-1, 2)    4 E (0, 1)      5 ESE (1, 2)     6 SE (1, 1)     7 SSE (2, 1)
+ *       8 S (1, 0)      9 SSW (2, -1)   10 SW (1, -1)    11 WSW (1, -2)   12 W (0, -1)    13 WNW (-1, -2)  14 NW (-1, -1)  15 NNW (-2, -1)
+ *     Steps m = 1, 2, ... while max(|m dr|, |m dc|) <= L and the cell is inside the raster, so the eight knight rays take
+ *     L / 2 steps (integer division).  Search length 1 <= L <= MHS_TERRAIN_MAX_RADIUS.
+ *       len_j = sqrt((|dr| dy) * (|dr| dy) + (|dc| dx) * (|dc| dx)),  dx of the CENTRE's row
+ *       s_m   = ((z_m - e) * z_factor) / ((double)m * len_j)
+ *     An NA cell on a ray is SKIPPED and the ray goes on (unlike the geomorphons' rays: the sea does not hide an island
+ *     behind it).  The HORIZON TANGENT H_j = the largest s_m if that is > 0, else 0; a ray without a valid step gives 0, an
+ *     open horizon.  Only an NA centre makes a cell NA.
+ * (b) Slope of the cell: dzdx and dzdy are the Horn values of rule 1 of "terrain" (dzdy is south minus north),
+ *     nrm = sqrt((1 + dzdx * dzdx) + dzdy * dzdy).  NA where any of the nine cells is NA.
+ * (c) Sun tables (mhs_sun_tables), made by the HOST; the device only reads them.  Table b serves the rows r with
+ *     tab_row[r] == b (all rows when tab_row is NULL).  Its entries whose azimuth lies between direction j and j + 1 (mod 16)
+ *     are [start[16 b + j], start[16 b + j + 1]): grouping by sector replaces a direction index in the entry.  Per entry:
+ *     t in [0, 1] the position of the sun's azimuth between the two directions, tan_h > 0 the tangent of its elevation,
+ *     (ux, uy, uz) its east, north and up components (a unit length is not checked), w >= 0 its energy weight, d >= 0 its
+ *     time weight.  omega[16 b + j] >= 0 is the share of the sky's azimuths that direction j stands for.  Checked before the
+ *     first device call: every value finite and in its range, start[0] = 0 and start non-decreasing, omega >= 0, tab_row
+ *     within 0 .. n_tab - 1, at most MHS_SOLAR_MAX_ENTRIES entries in total.
+ * (d) Products.  Bit k of `products` selects product k; the planes come out of ONE pass in ascending bit order:
+ *       0 svf        = sum over j ascending, from 0.0, of omega[j] / (1 + H_j * H_j): the ratio is the squared cosine of the
+ *                      horizon's elevation
+ *       1 direct     : acc = 0; for the table of the cell's row, sectors j ascending and entries in order:
+ *                        Hs = H_j + t * (H_j1 - H_j), j1 = (j + 1) & 15;  c = (uz - dzdx * ux) + dzdy * uy;
+ *                        if tan_h > Hs and c > 0: acc = acc + w * c
+ *                      direct = acc / nrm.  NA where the slope is.
+ *       2 sun_hours  = the sum, from 0.0 in the same order, of d over the entries with tan_h > Hs.  The cell's own slope is
+ *                      not looked at, so it is defined wherever the centre is valid.
+ *       3 horizon    = the sixteen planes H_0 .. H_15
+ *     Output float64, or float32 as the float64 result rounded once.  `tables` may be NULL when only horizon is asked for.
+ *
+ * What the rule leaves out: sixteen directions and cell centres only -- a narrow obstacle between two rays is not seen, and
+ * the horizon between two rays is their linear blend; the knight rays see every second ring of cells; nothing beyond
+ * L <= 45 cells (1.35 km at 30 m) is seen, so this is the LOCAL horizon and far ridges are missed; no diffuse or reflected
+ * light, no refraction, no curvature of the earth; grid north is taken as true north.
+ *
+ * tab_row, start, entries, omega and dx_row are HOST arrays in every entry point; they go up once per call on the call's
+ * stream into stream-ordered memory that is given back behind the kernel.  No atomics; a window gives the whole-grid call's
+ * bits.  Every argument is checked before the first device call (MHS_ERR_INVALID, the message names the argument).        */
+#define MHS_SOLAR_MAX_ENTRIES 262144
+typedef struct mhs_sun_entry { double t, tan_h, ux, uy, uz, w, d, pad; } mhs_sun_entry;   /* 64 bytes */
+typedef struct mhs_sun_tables {
+    int32_t n_tab;                  /* >= 1 */
+    const int64_t *start;           /* HOST, n_tab * 16 + 1 offsets into entries, non-decreasing, start[0] = 0 */
+    const mhs_sun_entry *entries;   /* HOST, start[n_tab * 16] of them */
+    const double *omega;            /* HOST, n_tab * 16 sector weights */
+    const int32_t *tab_row;         /* HOST, g->nrow table indices by absolute row, or NULL: table 0 */
+} mhs_sun_tables;
+/* DEVICE planes: out_dev holds the requested planes (horizon: sixteen), each (r1-r0) x ld row-major, plane_stride elements
+ * apart, of out_dtype MHS_F64 or MHS_F32.  Only enqueues on `stream`. */
+MHS_API int mhs_solar_dev(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
+                          const mhs_sun_tables *tables, int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned products,
+                          void *out_dev, int out_dtype, int64_t ld, int64_t plane_stride, void *stream);
+/* same, HOST planes: row bands of the window go up with their halo rows (MHS_HOST_BANDS as for mhs_terrain); blocks until
+ * done. */
+MHS_API int mhs_solar(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, int search,
+                      const mhs_sun_tables *tables, int64_t r0, int64_t r1, int64_t c0, int64_t c1, unsigned products,
+                      void *out_host, int out_dtype);
+
 /* ---------------------------------------------------------------- hydrology --
  * The topographic wetness index of an elevation model (the reference package bundles a TWI.tif and sends its users to SAGA
  * or GRASS for their own) with what it is made from: the flat-filled surface, the D8 flow direction and the flow

@@ -221,6 +221,52 @@ mhs_hydro_mfd <- function(dem.ras, v = "twi", convergence = 1.1, min.slope.deg =
   out
 }
 
+# ---- solar covariates of the DEM: what SAGA's "Potential Incoming Solar Radiation" / "Sky View Factor" and GRASS's r.horizon +
+# r.sun are used for ----------------------------------------------------------------------------------------------------
+# v: any of "svf" (the sky-view factor), "direct" (potential direct insolation on the tilted cell, shadowed by the relief, in
+# the units of the tables' w), "sun_hours" (the units of the tables' d) and "horizon" (sixteen layers: the tangent of the
+# horizon along N, NNE, NE, ... NNW within `search` cells).  tables: list(entries = n x 8 matrix with the columns t, tan_h, ux,
+# uy, uz, w, d, pad; start = 16 offsets per table into its rows and one more, 0-based; omega = 16 weights per table; tab_row =
+# NULL or one table number per row of the raster, 1-based) -- section "solar" of machisplin_hip.h says what they mean.  The
+# library does no trigonometry: the tables carry the sun.  Making them (the Python package's sun_tables) is not restated in R;
+# write them from Python or build them with the formulas of that section.  tables = NULL serves v = "horizon" alone.
+.mhs_solar_products <- c("svf", "direct", "sun_hours", "horizon")
+.mhs_solar_dirs <- c("N", "NNE", "NE", "ENE", "E", "ESE", "SE", "SSE", "S", "SSW", "SW", "WSW", "W", "WNW", "NW", "NNW")
+mhs_solar <- function(dem.ras, search = 10L, tables = NULL, v = "svf", z.factor = 1, lonlat = terra::is.lonlat(dem.ras)) {
+  bad <- setdiff(v, .mhs_solar_products)
+  if (length(bad) || !length(v)) stop("mhs_solar: v must name some of ", paste(.mhs_solar_products, collapse = ", "))
+  res <- terra::res(dem.ras)
+  if (isTRUE(lonlat)) {
+    lat <- terra::yFromRow(dem.ras, seq_len(terra::nrow(dem.ras)))
+    dx.row <- res[1] * (pi / 180) * 6378137 * cos(lat * (pi / 180))
+    units <- c(NA_real_, res[2] * (pi / 180) * 6378137, z.factor)
+  } else {
+    dx.row <- NULL
+    units <- c(res[1], res[2], z.factor)
+  }
+  if (!is.null(tables)) {
+    entries <- as.matrix(tables$entries); storage.mode(entries) <- "double"
+    tables <- list(entries, as.numeric(tables$start), as.numeric(tables$omega),
+                   if (is.null(tables$tab_row)) NULL else as.integer(tables$tab_row) - 1L)
+  }
+  v <- unique(v)
+  pv <- intersect(.mhs_solar_products, v)                     # ascending bit order: the order of the columns that come back
+  m <- .Call("mhsr_solar", .mhs_geom(dem.ras), as.numeric(terra::values(dem.ras[[1]])), units, dx.row, as.integer(search),
+             as.integer(sum(2^(match(pv, .mhs_solar_products) - 1))), tables)
+  first <- cumsum(c(1L, ifelse(pv == "horizon", 16L, 1L)))
+  layers <- list()
+  for (n in v) {
+    k <- first[match(n, pv)]
+    cols <- if (n == "horizon") k:(k + 15L) else k
+    for (j in seq_along(cols)) {
+      r <- terra::setValues(terra::rast(dem.ras[[1]]), m[, cols[j]])
+      names(r) <- if (n == "horizon") paste0("horizon_", .mhs_solar_dirs[j]) else n
+      layers <- c(layers, list(r))
+    }
+  }
+  do.call(c, layers)
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

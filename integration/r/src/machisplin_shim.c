@@ -293,6 +293,52 @@ SEXP mhsr_geomorphon(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP search, 
     return out;
 }
 
+/* Solar covariates of the DEM (machisplin_hip.h "solar"): products is a bit mask (1 svf, 2 direct, 4 sun_hours, 8 horizon), search
+ * the length of the sixteen rays in cells.  tables: NULL (horizon alone) or list(entries, start, omega, tab_row) -- entries an
+ * n x 8 numeric matrix with the columns t, tan_h, ux, uy, uz, w, d, pad, start n_tab * 16 + 1 offsets into its rows (0-based,
+ * numeric or integer), omega n_tab * 16 weights, tab_row NULL or one 0-based table index per row of the raster (integer).
+ * Returns an ncell x n matrix in terra cell order, columns in ascending bit order, horizon as sixteen columns N, NNE, ... NNW;
+ * NaN at NA cells.  Runs on the HOST entry point. */
+SEXP mhsr_solar(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP search, SEXP products, SEXP tables) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = dem_from(dem, &g, "mhsr_solar");
+    mhs_terrain_units u = units_from(units, dx_row, &g, "mhsr_solar");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 15) Rf_error("mhsr_solar: products must be a bit mask of 1 svf, 2 direct, 4 sun_hours, 8 horizon");
+    int n = mask_planes(mask & 7) + ((mask & 8) ? 16 : 0);
+    mhs_sun_tables t = { 0, NULL, NULL, NULL, NULL };
+    if (!Rf_isNull(tables)) {
+        if (TYPEOF(tables) != VECSXP || Rf_length(tables) != 4) Rf_error("mhsr_solar: tables must be list(entries, start, omega, tab_row)");
+        SEXP entries = VECTOR_ELT(tables, 0), start = VECTOR_ELT(tables, 1), omega = VECTOR_ELT(tables, 2), tab_row = VECTOR_ELT(tables, 3);
+        if (!Rf_isReal(entries) || !Rf_isMatrix(entries) || Rf_ncols(entries) != 8) Rf_error("mhsr_solar: entries must be a numeric matrix of 8 columns");
+        if (!Rf_isReal(omega) || Rf_length(omega) < 16 || Rf_length(omega) % 16) Rf_error("mhsr_solar: omega must hold 16 weights per table");
+        int n_tab = Rf_length(omega) / 16, n_ent = Rf_nrows(entries), n_start = n_tab * 16 + 1;
+        if (Rf_length(start) != n_start) Rf_error("mhsr_solar: start must hold 16 offsets per table and one more");
+        int64_t *s64 = (int64_t *)R_alloc((size_t)n_start, sizeof(int64_t));
+        for (int k = 0; k < n_start; ++k) {
+            double v = TYPEOF(start) == INTSXP ? (double)INTEGER(start)[k] : REAL(start)[k];
+            if (!(v >= 0.0 && v <= (double)n_ent)) Rf_error("mhsr_solar: start[%d] is not an offset into the %d rows of entries", k + 1, n_ent);
+            s64[k] = (int64_t)v;
+        }
+        mhs_sun_entry *e = (mhs_sun_entry *)R_alloc((size_t)(n_ent ? n_ent : 1), sizeof(mhs_sun_entry));
+        const double *m = REAL(entries);                 /* column-major */
+        for (int i = 0; i < n_ent; ++i) {
+            mhs_sun_entry r = { m[i], m[i + (size_t)n_ent], m[i + 2 * (size_t)n_ent], m[i + 3 * (size_t)n_ent], m[i + 4 * (size_t)n_ent],
+                                m[i + 5 * (size_t)n_ent], m[i + 6 * (size_t)n_ent], 0.0 };
+            e[i] = r;
+        }
+        if (!Rf_isNull(tab_row) && (TYPEOF(tab_row) != INTSXP || (int64_t)Rf_length(tab_row) != g.nrow))
+            Rf_error("mhsr_solar: tab_row must be NULL or one integer table index per row");
+        t.n_tab = n_tab; t.start = s64; t.entries = e; t.omega = REAL(omega);
+        t.tab_row = Rf_isNull(tab_row) ? NULL : (const int32_t *)INTEGER(tab_row);
+    }
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(g.nrow * g.ncol), n));
+    int rc = mhs_solar(&g, &st, 0, &u, Rf_asInteger(search), Rf_isNull(tables) ? NULL : &t, 0, g.nrow, 0, g.ncol, (unsigned)mask, REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* Hydrology of the DEM (machisplin_hip.h "hydrology"): the bundled TWI.tif's recipe.  products: bit mask (1 filled, 2 flowdir,
  * 4 flowacc, 8 twi); opts: c(min_slope_tan, max_passes).  Returns list(filled, flowdir, flowacc, twi, info) in terra cell order,
  * NULL where a plane was not asked for: numeric vectors (NaN at NA cells), flowdir an integer vector (0 .. 7 = E, SE, S, SW, W,

@@ -16,7 +16,7 @@ from .tps import Tps, fit_many, interpolate, interpolate_se, eval_mode, EVAL_AUT
 from .tps import se_max_n, se_build_mode, SE_BUILD_AUTO, SE_BUILD_HOST, SE_BUILD_DEVICE
 from . import tiles, mltps, cv, varimp, mess, terrain
 from .mess import Mess
-from .terrain import relief, geomorphon, hydro, hydro_mfd, covariates      # the 3 x 3 variables: terrain.terrain (the module keeps its name)
+from .terrain import relief, geomorphon, hydro, hydro_mfd, covariates, solar, sun_tables, SunTables      # the 3 x 3 variables: terrain.terrain (the module keeps its name)
 from .cv import fit_layer, fit_nnet_folds, fit_ksvm_folds, kfold
 from .mltps import mltps as mltps_layers, mltps_predict, tps_residual_surface, tps_residual_surface_se
 
@@ -24,4 +24,5 @@ __all__ = ["MhsError", "init", "Geometry", "RasterStack", "Tps", "interpolate", 
            "se_max_n", "se_build_mode", "SE_BUILD_AUTO", "SE_BUILD_HOST", "SE_BUILD_DEVICE", "predict",
            "ensemble_predict", "models", "tiles", "mltps", "mltps_predict",
            "tps_residual_surface", "tps_residual_surface_se", "nnet_fit_many", "ksvm_fit_many", "sigest", "fit_layer",
-           "fit_nnet_folds", "fit_ksvm_folds", "kfold", "varimp", "mess", "Mess", "terrain", "relief", "geomorphon", "hydro", "hydro_mfd", "covariates", "_lib"]
+           "fit_nnet_folds", "fit_ksvm_folds", "kfold", "varimp", "mess", "Mess", "terrain", "relief", "geomorphon", "hydro", "hydro_mfd", "covariates", "solar", "sun_tables",
+           "SunTables", "_lib"]

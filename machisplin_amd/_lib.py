@@ -71,6 +71,11 @@ class TerrainUnits(C.Structure):
     _fields_ = [("dx", C.c_double), ("dx_row", C.c_void_p), ("dy", C.c_double), ("z_factor", C.c_double)]
 
 
+class SunTablesC(C.Structure):
+    """struct mhs_sun_tables"""
+    _fields_ = [("n_tab", C.c_int32), ("start", C.c_void_p), ("entries", C.c_void_p), ("omega", C.c_void_p), ("tab_row", C.c_void_p)]
+
+
 class HydroOut(C.Structure):
     """struct mhs_hydro_out"""
     _fields_ = [("filled", C.c_void_p), ("flowdir", C.c_void_p), ("flowacc", C.c_void_p), ("twi", C.c_void_p)]
@@ -186,6 +191,10 @@ SIGNATURES = {
                              _vp, C.c_int]),
     "mhs_geomorphon": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.c_double, _i64, _i64, _i64,
                                  _i64, _vp]),
+    "mhs_solar_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.POINTER(SunTablesC), _i64,
+                                _i64, _i64, _i64, C.c_uint, _vp, C.c_int, _i64, _i64, _vp]),
+    "mhs_solar": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_int, C.POINTER(SunTablesC), _i64, _i64,
+                            _i64, _i64, C.c_uint, _vp, C.c_int]),
     "mhs_hydro_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int,
                                 C.POINTER(HydroOut), C.c_int, _i64, _vp, C.POINTER(HydroInfo)]),
     "mhs_hydro": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int,

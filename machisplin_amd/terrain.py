@@ -4,10 +4,12 @@ What the reference package's README sends its users to SAGA, GRASS and terra for
 topography data?"): the covariate rasters derived from the DEM -- ``slope``, ``rel_alt`` / ``relative_elevation500m`` and
 their kin -- and ``TWI``, with the filled surface, the D8 flow direction and the flow accumulation it is made from
 (:func:`hydro`), or with the multiple-flow-direction accumulation SAGA makes it from (:func:`hydro_mfd`).
-include/machisplin_hip.h, sections "terrain", "hydrology" and "hydrology, multiple flow direction", states the rules.
-All arithmetic runs in libmachisplin_hip.so (csrc/terrain.hip, csrc/hydro.hip); this module only marshals arguments -- and,
-for a lon/lat raster, makes the rows' ground widths with numpy, because the library never calls cos (nor tan: the slope floor
-of the wetness index is made here too).
+And the radiation covariates such a study makes with SAGA or GRASS's r.sun: the local horizon, the sky-view factor, potential
+direct insolation and sun hours (:func:`solar`, with the sun's positions from :func:`sun_tables`).
+include/machisplin_hip.h, sections "terrain", "solar", "hydrology" and "hydrology, multiple flow direction", states the rules.
+All arithmetic on the cells runs in libmachisplin_hip.so (csrc/terrain.hip, csrc/hydro.hip); this module only marshals
+arguments -- and, for a lon/lat raster, makes the rows' ground widths with numpy, because the library never calls cos (nor tan:
+the slope floor of the wetness index is made here too; nor any trigonometry for the sun: the sun tables are made here).
 """
 from __future__ import annotations
 
@@ -25,6 +27,11 @@ HYDRO = ("filled", "flowdir", "flowacc", "twi")                     # the planes
 HYDRO_SPEC = {"twi": ("twi", False), "log_flowacc": ("flowacc", True)}      # covariates(): spec name -> (product, take its log)
 HYDRO_MFD = ("filled", "flowacc", "twi")                            # the planes of mhs_hydro_mfd_out, in its order
 HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True)}      # the same, made by hydro_mfd at its defaults
+SOLAR = ("svf", "direct", "sun_hours", "horizon")                   # the products of mhs_solar, in its order; horizon is 16 planes
+# the sixteen ray directions of section "solar", clockwise from north: (rows south, columns east)
+SOLAR_DIRECTIONS = ((-1, 0), (-2, 1), (-1, 1), (-1, 2), (0, 1), (1, 2), (1, 1), (2, 1),
+                    (1, 0), (2, -1), (1, -1), (1, -2), (0, -1), (-1, -2), (-1, -1), (-2, -1))
+SOLAR_CONSTANT = 1367.0                                             # W / m^2
 GEOMORPHON_NA = -32768
 EARTH_RADIUS = 6378137.0
 
@@ -149,6 +156,140 @@ def geomorphon(stack: RasterStack, search, flat_deg=1.0, layer=0, lonlat=False, 
     return out
 
 
+class SunTables:
+    """The sun tables of a solar call (struct mhs_sun_tables; include/machisplin_hip.h, section "solar", (c)), as host
+    arrays: ``start`` int64 (n_tab * 16 + 1), ``entries`` float64 (n, 8) with the columns t, tan_h, ux, uy, uz, w, d, pad,
+    ``omega`` float64 (n_tab * 16), ``tab_row`` int32 (one table index per row of the whole grid) or None.  ``phi``
+    (n_tab, 16) holds the directions' azimuths the tables were made with, radians clockwise from north (None when the
+    tables did not come from :func:`sun_tables`)."""
+
+    def __init__(self, start, entries, omega, tab_row=None, phi=None):
+        self.start = np.ascontiguousarray(start, dtype=np.int64)
+        self.entries = np.ascontiguousarray(entries, dtype=np.float64).reshape(-1, 8)
+        self.omega = np.ascontiguousarray(omega, dtype=np.float64).ravel()
+        self.tab_row = None if tab_row is None else np.ascontiguousarray(tab_row, dtype=np.int32)
+        self.phi = phi
+        if self.omega.size % 16 or self.omega.size == 0 or self.start.shape != (self.omega.size + 1,):
+            raise ValueError("omega must hold 16 weights per table and start one offset more")
+        self.n_tab = self.omega.size // 16
+
+    def c_struct(self):
+        """the struct; it points into this object's arrays, which must outlive the call"""
+        return _lib.SunTablesC(self.n_tab, self.start.ctypes.data, self.entries.ctypes.data, self.omega.ctypes.data,
+                               None if self.tab_row is None else self.tab_row.ctypes.data)
+
+
+def _sun_table(lat_deg, dx, dy, days, step_minutes, transmittance):
+    """one table: (entries (n, 8) grouped by sector, the 17 offsets, omega (16), phi (16))"""
+    two_pi = 2.0 * np.pi
+    phi = np.array([np.arctan2(dc * dx, -dr * dy) for dr, dc in SOLAR_DIRECTIONS]) % two_pi       # ascending: the rays go clockwise
+    width = (np.roll(phi, -1) - phi) % two_pi                       # of the sector from direction j to j + 1
+    omega = 0.5 * ((np.roll(phi, -1) - np.roll(phi, 1)) % two_pi) / two_pi
+    lat = np.deg2rad(float(lat_deg))
+    dt = float(step_minutes) / 60.0
+    hours = (np.arange(int(round(24.0 / dt))) + 0.5) * dt           # local solar time at the midpoints of the steps
+    rows = []
+    for n in days:
+        delta = np.deg2rad(23.45) * np.sin(two_pi * (284.0 + float(n)) / 365.0)           # Cooper (1969)
+        om = np.deg2rad(15.0) * (hours - 12.0)
+        up = np.sin(lat) * np.sin(delta) + np.cos(lat) * np.cos(delta) * np.cos(om)
+        north = np.cos(lat) * np.sin(delta) - np.sin(lat) * np.cos(delta) * np.cos(om)
+        east = -np.cos(delta) * np.sin(om)
+        k = up > 0.0
+        up, north, east = up[k], north[k], east[k]
+        az = np.arctan2(east, north) % two_pi
+        j = np.clip(np.searchsorted(phi, az, side="right") - 1, 0, 15)
+        t = np.clip(((az - phi[j]) % two_pi) / width[j], 0.0, 1.0)
+        with np.errstate(divide="ignore"):
+            tan_h = np.minimum(up / np.sqrt(east * east + north * north), 1e12)           # the sun in the zenith: finite
+        w = SOLAR_CONSTANT * float(transmittance) ** (1.0 / up) * dt / len(days)
+        d = np.full(up.shape, dt / len(days))
+        rows.append(np.column_stack([t, tan_h, east, north, up, w, d, np.zeros(up.shape), j]))
+    rows = np.concatenate(rows) if rows else np.zeros((0, 9))
+    order = np.argsort(rows[:, 8], kind="stable")                   # by sector; within one, the days and times in order
+    rows = rows[order]
+    start = np.searchsorted(rows[:, 8], np.arange(17), side="left").astype(np.int64)
+    return np.ascontiguousarray(rows[:, :8]), start, omega, phi
+
+
+def sun_tables(geom, days=(80, 172, 266, 355), step_minutes=30, lonlat=False, lat=None, transmittance=0.7, lat_step=0.25, dx=None,
+               dy=None) -> SunTables:
+    """The sun tables :func:`solar` hands to the library, made here with numpy (the library never calls sin, cos or atan).
+    For every day ``n`` of ``days`` (day of the year) and every step of ``step_minutes`` of local solar time, at the step's
+    midpoint: declination delta = 23.45 deg sin(2 pi (284 + n) / 365) (Cooper), hour angle 15 deg (time - 12), and at
+    latitude phi  up = sin phi sin delta + cos phi cos delta cos omega,  north = cos phi sin delta - sin phi cos delta
+    cos omega,  east = -cos delta sin omega.  An entry where up > 0: tan_h = up / sqrt(east^2 + north^2), its azimuth
+    atan2(east, north) placed between the two of the sixteen ray directions it lies between -- their azimuths
+    atan2(dc dx, -dr dy) come from the table's own ``dx``, ``dy`` --, the energy weight w = 1367 transmittance ** (1 / up)
+    dt / len(days) (the mean daily W h / m^2 on a surface facing the beam) and the time weight d = dt / len(days) (hours).
+    omega_j = half the angle between direction j's two neighbours over 2 pi.
+
+    A projected grid has one table at latitude ``lat`` degrees (required).  ``lonlat=True``: one table per band of
+    ``lat_step`` degrees, counted from the grid's northern edge, made at the band's centre latitude with that latitude's
+    ``dx``, and ``tab_row`` from the rows' latitudes.  The library's rays use each row's OWN dx (``dx_row``) while the
+    sectors' azimuths come from the band's: that mismatch, at most half a ``lat_step`` of latitude, is this wrapper's
+    approximation, not the library's."""
+    days = tuple(days)
+    if not days or not 0.0 < float(step_minutes) <= 720.0 or not 0.0 < float(transmittance) <= 1.0:
+        raise ValueError("days must not be empty, step_minutes in (0, 720], transmittance in (0, 1]")
+    if not lonlat:
+        if lat is None:
+            raise ValueError("a projected grid needs lat, the latitude in degrees the sun tables are made for")
+        e, start, omega, phi = _sun_table(lat, dx if dx is not None else geom.xres, dy if dy is not None else geom.yres, days,
+                                          step_minutes, transmittance)
+        return SunTables(start, e, omega, None, phi[None])
+    if not float(lat_step) > 0.0:
+        raise ValueError("lat_step must be positive")
+    lats = np.asarray(geom.y_from_row(np.arange(geom.nrow)), dtype=np.float64)
+    tab_row = np.floor((geom.ymax - lats) / float(lat_step)).astype(np.int32)
+    tab_row -= tab_row.min()
+    n_tab = int(tab_row.max()) + 1
+    first = int(np.floor((geom.ymax - lats[0]) / float(lat_step)))
+    ents, starts, omegas, phis, n = [], [np.zeros(1, dtype=np.int64)], [], [], 0
+    for b in range(n_tab):
+        centre = geom.ymax - (first + b + 0.5) * float(lat_step) if lat is None else float(lat)
+        bdx = dx if dx is not None else geom.xres * (np.pi / 180.0) * EARTH_RADIUS * np.cos(np.deg2rad(centre))
+        bdy = dy if dy is not None else geom.yres * (np.pi / 180.0) * EARTH_RADIUS
+        e, start, omega, phi = _sun_table(centre, bdx, bdy, days, step_minutes, transmittance)
+        ents.append(e); starts.append(start[1:] + n); omegas.append(omega); phis.append(phi)
+        n += len(e)
+    return SunTables(np.concatenate(starts), np.concatenate(ents), np.concatenate(omegas), tab_row, np.stack(phis))
+
+
+def solar(stack: RasterStack, search, products=("svf",), tables=None, layer=0, lonlat=False, lat=None, z_factor=1.0, window=None,
+          out_dtype=None, out=None, stream=None, dx=None, dy=None, dx_row=None):
+    """Solar covariates of layer ``layer`` (include/machisplin_hip.h, section "solar"): ``products`` names some of
+    :data:`SOLAR` -- ``svf`` the sky-view factor, ``direct`` the potential direct insolation on the tilted cell, shadowed by
+    the horizon (in the units of the tables' ``w``: mean daily W h / m^2 with :func:`sun_tables`), ``sun_hours`` (the units of
+    ``d``: mean hours per day) and ``horizon``, the SIXTEEN planes of the horizon's tangent along the rays N, NNE, NE, ... NNW
+    within ``search`` cells (1 .. :func:`max_radius`).  Shapes, ``window``, ``out`` and the plane order as in :func:`terrain`;
+    ``horizon`` contributes 16 planes, so a single ``"horizon"`` returns (16, rows, cols).  ``tables``: a :class:`SunTables`;
+    None makes them with :func:`sun_tables` at its defaults (``lonlat``, ``lat``, ``dx``, ``dy`` passed on) when a product
+    needs them -- ``horizon`` alone needs none.  NaN where the centre is NA; ``direct`` also where any of the nine cells is."""
+    import torch
+    one, names, mask, _ = _mask(products, SOLAR, "product")
+    r0, r1, c0, c1 = _window(stack, window)
+    units = ground_units(stack.geom, lonlat, z_factor, dx, dy, dx_row)
+    if tables is None and mask & 7:
+        tables = sun_tables(stack.geom, lonlat=lonlat, lat=lat, dx=dx, dy=dy)
+    width = {n: 16 if n == "horizon" else 1 for n in SOLAR}
+    lib_order = sorted(names, key=SOLAR.index)
+    first, n_planes = {}, 0
+    for n in lib_order:
+        first[n] = n_planes
+        n_planes += width[n]
+    out, code = _planes(stack, (r1 - r0, c1 - c0), n_planes, out_dtype or torch.float64, out)
+    g, s, u = stack.geom.c_struct(), stack.c_struct(), _c_units(units)
+    t = tables.c_struct() if tables is not None else None
+    _lib.check(_lib.lib().mhs_solar_dev(C.byref(g), C.byref(s), int(layer), C.byref(u), int(search), C.byref(t) if t is not None else None,
+                                        r0, r1, c0, c1, mask, out.data_ptr(), code, out.stride(1), out.stride(0), _stream(stack, stream)))
+    if one:
+        return out if names[0] == "horizon" else out[0]
+    if list(names) == lib_order:
+        return out
+    return out[[first[n] + k for n in names for k in range(width[n])]]
+
+
 class HydroResult(dict):
     """what :func:`hydro` returns for several products: the planes by name, and ``.info``"""
     info = None
@@ -215,7 +356,7 @@ def _hydro(stack, layer, products, exponent, lonlat, z_factor, min_slope_deg, ma
     return res, info
 
 
-def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0):
+def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
       a name of :data:`VARS`                      that 3 x 3 variable (all of them in one pass)
@@ -224,6 +365,9 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       "twi"                                       the topographic wetness index (:func:`hydro`, its defaults)
       "log_flowacc"                               log of the flow accumulation, taken by torch on the float64 plane
       "twi_mfd", "log_flowacc_mfd"                the same two with multiple flow direction (:func:`hydro_mfd`, its defaults)
+      ("svf" | "direct" | "sun_hours", search)    that solar product within ``search`` cells (:func:`solar`; one call per
+                                                  distinct search length makes all of its layers) with the tables ``sun``, a
+                                                  :class:`SunTables`, or those of :func:`sun_tables` at ``lat`` degrees
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -247,8 +391,16 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             for n in hv:
                 product, log = table[n]
                 by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
+    sun_names = SOLAR[:3]
+    for L in dict.fromkeys(int(e[1]) for e in spec if len(e) > 1 and e[0] in sun_names):
+        sv = tuple(dict.fromkeys(e[0] for e in spec if len(e) > 1 and e[0] in sun_names and int(e[1]) == L))
+        got = solar(dem_stack, L, sv, sun, layer, lonlat, lat, z_factor, out_dtype=torch.float32)
+        by_name.update({(n, L): p for n, p in zip(sv, got)})
     for k, e in enumerate(spec):
-        if len(e) == 1:
+        if len(e) > 1 and e[0] in sun_names:
+            planes[1 + k] = by_name[(e[0], int(e[1]))]
+            names.append(f"{e[0]}{int(e[1])}")
+        elif len(e) == 1:
             planes[1 + k] = by_name[e[0]]
             names.append(e[0])
         elif e[0] == "geomorphon":
