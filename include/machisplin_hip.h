@@ -874,6 +874,65 @@ MHS_API int mhs_hydro_mfd_dev(const mhs_grid *g, const mhs_stack *dem, int layer
 MHS_API int mhs_hydro_mfd(const mhs_grid *g, const mhs_stack *dem, int layer, const mhs_terrain_units *units, double min_slope_tan,
                           int max_passes, double exponent, const mhs_hydro_mfd_out *out, int out_dtype, mhs_hydro_info *info);
 
+/* ----------------------------------------------------------------- resample --
+ * Rasters onto one grid.  The reference's README asks for rasters of one resolution, projection and extent and sends its
+ * users to terra::crop and terra::extract for the rest; this section brings a stack on grid S onto an axis-aligned grid T in
+ * the SAME coordinate system (resolution, origin and extent may differ; no reprojection) and interpolates it at points.
+ * csrc/resample_rule.h holds the rules as they stand here, every operation in this order and rounded once (the library is
+ * built with -ffp-contract=off; there is no transcendental), so every method equals a restatement in any IEEE double
+ * arithmetic bit for bit.
+ *
+ * Source: the C layers of an mhs_stack on S (int16, float32 or float64; a value is converted exactly to double; NA = NaN or the
+ * stack's nodata).  Target: the window [r0,r1) x [c0,c1) of T.  Output: C planes of MHS_F64, or MHS_F32 = the float64 result
+ * rounded once; NA is written as NaN.
+ *
+ * Centre of target cell (r, c):  x = T.xmin + ((double)c + 0.5) T.xres,  y = T.ymax - ((double)r + 0.5) T.yres.
+ *
+ * The interpolating methods give NA unless the centre has a cell of S under the rule of mhs_cells_from_xy (terra's colFromX /
+ * rowFromY: the east and south edges belong to the last column and row).
+ *   MHS_RS_NEAR      the value of that cell.
+ *   MHS_RS_BILINEAR  fx = (x - S.xmin) / S.xres - 0.5, j0 = floor(fx), tx = fx - j0;  fy = (S.ymax - y) / S.yres - 0.5, i0, ty
+ *                    likewise.  wx = {1 - tx, tx}, wy = {1 - ty, ty}, w = wy_i wx_j.  The taps (i0, j0), (i0, j0+1), (i0+1, j0),
+ *                    (i0+1, j0+1) in that order: a tap outside the raster, NA or with w == 0 is skipped, otherwise
+ *                    num = num + w z, den = den + w.  The value is num / den (the division is always made) when den > 0, else
+ *                    NA.  So an NA neighbour of weight 0 does not poison a cell, and on a grid on which fx and fy come out
+ *                    whole (the same grid, with an origin and a cell size that make (x - S.xmin) / S.xres exact) the value is
+ *                    the source's.
+ *   MHS_RS_CUBIC     Catmull-Rom (a = -0.5, GDAL's cubic).  The same i0, j0, tx, ty; taps i0-1 .. i0+2 by j0-1 .. j0+2.  Weights
+ *                    of t, as written:  ((-0.5 t + 1.0) t - 0.5) t,  ((1.5 t - 2.5) t) t + 1.0,  ((-1.5 t + 2.0) t + 0.5) t,
+ *                    ((0.5 t - 0.5) t) t.  Row value r_i = ((wx0 z_i0 + wx1 z_i1) + wx2 z_i2) + wx3 z_i3, value
+ *                    ((wy0 r_0 + wy1 r_1) + wy2 r_2) + wy3 r_3.  If a tap with wx_j != 0 and wy_i != 0 is outside the raster or
+ *                    NA the cell takes the BILINEAR value instead; a tap without a value whose weight is 0 enters as z = 0.
+ * The aggregates MHS_RS_MEAN, MIN, MAX, SUM, COUNT take the source cells whose CENTRE lies in the target cell.  The footprint
+ * of target column c is the source columns [j_lo, j_hi):  j_lo = ceil((x0 - S.xmin) / S.xres - 0.5),
+ * j_hi = ceil((x1 - S.xmin) / S.xres - 0.5), x0 = T.xmin + (double)c T.xres, x1 = T.xmin + (double)(c+1) T.xres, both held in
+ * [0, S.ncol]; x1 of c is the expression x0 of c + 1, so the footprints partition the columns.  Rows likewise from
+ * S.ymax - (T.ymax - (double)r T.yres), north to south.  NA cells are skipped.  The sum is a sum of row sums: each footprint row
+ * is added west to east from 0.0, the row sums north to south from 0.0.  MIN and MAX are the first smallest / largest value in
+ * that order.  MEAN = sum / (double)count.  COUNT is the count as a floating value and SUM is 0 where the count is 0; MEAN, MIN
+ * and MAX are NA there -- also where a target finer than the source has an empty footprint.
+ *
+ * Every argument is checked before the first device call (MHS_ERR_INVALID, the message names the argument): NULL pointers, a
+ * cell size or dimension that is not positive, a window outside the target, an unknown method, an aggregate method for points,
+ * an output type other than MHS_F64 / MHS_F32, a bad stack type. */
+enum { MHS_RS_NEAR = 0, MHS_RS_BILINEAR, MHS_RS_CUBIC, MHS_RS_MEAN, MHS_RS_MIN, MHS_RS_MAX, MHS_RS_SUM, MHS_RS_COUNT };
+/* DEVICE planes: src_stack describes device planes covering S; out_dev holds C planes, each (r1-r0) x out_ld row-major,
+ * out_plane_stride elements apart, of out_dtype.  All layers go through one launch.  Only enqueues on `stream`. */
+MHS_API int mhs_resample_dev(const mhs_grid *src_grid, const mhs_stack *src_stack, const mhs_grid *dst_grid, int64_t r0, int64_t r1,
+                             int64_t c0, int64_t c1, int method, void *out_dev, int64_t out_ld, int64_t out_plane_stride,
+                             int out_dtype, void *stream);
+/* same, HOST planes in and out (C planes of (r1-r0) x (c1-c0)): row bands of the target window go up with exactly the source
+ * rows they read (MHS_HOST_BANDS as for mhs_terrain); blocks until done. */
+MHS_API int mhs_resample(const mhs_grid *src_grid, const mhs_stack *src_stack, const mhs_grid *dst_grid, int64_t r0, int64_t r1,
+                         int64_t c0, int64_t c1, int method, void *out_host, int out_dtype);
+/* the interpolating methods at n points: xy is n x 2 column-major (as mhs_cells_from_xy takes it), out n x C column-major
+ * double, NaN where the point has no cell or the method gives NA.  _dev: stack, xy and out on the device, only enqueues;
+ * the host form sends up the source rows between the points' outermost taps and blocks until done. */
+MHS_API int mhs_extract_points_dev(const mhs_grid *src_grid, const mhs_stack *src_stack, const double *xy_dev, int64_t n, int method,
+                                   double *out_dev, void *stream);
+MHS_API int mhs_extract_points(const mhs_grid *src_grid, const mhs_stack *src_stack, const double *xy, int64_t n, int method,
+                               double *out);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

@@ -267,6 +267,34 @@ mhs_solar <- function(dem.ras, search = 10L, tables = NULL, v = "svf", z.factor 
   do.call(c, layers)
 }
 
+# ---- rasters onto one grid: what the README's "All rasters must be the same: resolution, projection and extent" leaves to
+# terra::crop, terra::resample and terra::extract ---------------------------------------------------------------------------
+# x: a SpatRaster in the coordinate system of y (no reprojection); y: the SpatRaster whose grid the result takes.  method: "near",
+# "bilinear", "cubic" interpolate at y's cell centres; "mean", "min", "max", "sum", "count" take x's cells whose centre lies
+# in y's cell (a 30 m product onto the 1 km grid the stations were sampled from).  Every layer of x goes through one call.
+# Section "resample" of machisplin_hip.h states the rules; they are the library's own, not terra's bit for bit.
+.mhs_resample_methods <- c("near", "bilinear", "cubic", "mean", "min", "max", "sum", "count")
+mhs_resample <- function(x, y, method = "bilinear") {
+  m <- match(method, .mhs_resample_methods)
+  if (length(method) != 1L || is.na(m)) stop("mhs_resample: method must be one of ", paste(.mhs_resample_methods, collapse = ", "))
+  v <- terra::values(x); storage.mode(v) <- "double"
+  out <- .Call("mhsr_resample", .mhs_geom(x), v, NA_real_, .mhs_geom(y), as.integer(m - 1L))
+  r <- terra::rast(y[[1]], nlyrs = terra::nlyr(x))
+  r <- terra::setValues(r, out)
+  names(r) <- names(x)
+  r
+}
+# terra::extract(x, xy, method = ) for a matrix of coordinates: "simple" (the cell that holds the point), "bilinear", "cubic"
+mhs_extract <- function(x, xy, method = "simple") {
+  m <- match(method, c("simple", "bilinear", "cubic"))
+  if (length(method) != 1L || is.na(m)) stop("mhs_extract: method must be simple, bilinear or cubic")
+  xy <- as.matrix(xy[, 1:2]); storage.mode(xy) <- "double"
+  v <- terra::values(x); storage.mode(v) <- "double"
+  out <- .Call("mhsr_extract", .mhs_geom(x), v, NA_real_, xy, as.integer(m - 1L))
+  colnames(out) <- names(x)
+  out
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

@@ -409,6 +409,43 @@ SEXP mhsr_hydro_mfd(SEXP geom, SEXP dem, SEXP units, SEXP dx_row, SEXP products,
     return out;
 }
 
+/* Rasters onto one grid (machisplin_hip.h "resample"): what the package's README sends its users to terra::crop, terra::resample
+ * and terra::extract for.  planes: terra::values(src.ras), an ncell x C numeric matrix (or a vector for one layer; NA_real_ =
+ * NA); nodata: a value that also means NA, or NA_real_; method: 0 near, 1 bilinear, 2 cubic, 3 mean, 4 min, 5 max, 6 sum,
+ * 7 count.  Both run on the HOST entry points. */
+static mhs_stack planes_from(SEXP planes, SEXP nodata, const mhs_grid *g, const char *who) {
+    if (!Rf_isReal(planes)) Rf_error("%s: planes must be numeric (terra::values)", who);
+    int C = Rf_isMatrix(planes) ? Rf_ncols(planes) : 1;
+    if (C < 1 || (int64_t)Rf_xlength(planes) != g->nrow * g->ncol * C) Rf_error("%s: planes must have one row per cell", who);
+    mhs_stack st = { REAL(planes), C, MHS_F64, (int64_t)g->nrow * g->ncol, g->ncol, Rf_asReal(nodata) };
+    return st;
+}
+
+/* every layer on the grid geom_dst: an ncell(dst) x C matrix in terra cell order, NaN where the method gives NA */
+SEXP mhsr_resample(SEXP geom_src, SEXP planes, SEXP nodata, SEXP geom_dst, SEXP method) {
+    mhs_grid gs = grid_from(geom_src), gd = grid_from(geom_dst);
+    mhs_stack st = planes_from(planes, nodata, &gs, "mhsr_resample");
+    if (!(gd.nrow > 0 && gd.ncol > 0 && (double)gd.nrow * (double)gd.ncol <= 2147483647.0)) Rf_error("mhsr_resample: bad target dimension");
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(gd.nrow * gd.ncol), st.n_layers));
+    int rc = mhs_resample(&gs, &st, &gd, 0, gd.nrow, 0, gd.ncol, Rf_asInteger(method), REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
+/* terra::extract(src.ras, xy, method =): xy an n x 2 numeric matrix (x, y); method 0 simple, 1 bilinear, 2 cubic.  An n x C matrix. */
+SEXP mhsr_extract(SEXP geom, SEXP planes, SEXP nodata, SEXP xy, SEXP method) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_extract");
+    if (!Rf_isReal(xy) || !Rf_isMatrix(xy) || Rf_ncols(xy) != 2) Rf_error("mhsr_extract: xy must be a numeric matrix of 2 columns");
+    int n = Rf_nrows(xy);
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n, st.n_layers));
+    int rc = mhs_extract_points(&g, &st, REAL(xy), (int64_t)n, Rf_asInteger(method), REAL(out));
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

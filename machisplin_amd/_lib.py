@@ -203,6 +203,11 @@ SIGNATURES = {
                                     C.POINTER(HydroMfdOut), C.c_int, _i64, _vp, C.POINTER(HydroInfo)]),
     "mhs_hydro_mfd": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(TerrainUnits), C.c_double, C.c_int, C.c_double,
                                 C.POINTER(HydroMfdOut), C.c_int, C.POINTER(HydroInfo)]),
+    "mhs_resample_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_int, _vp, _i64, _i64,
+                                   C.c_int, _vp]),
+    "mhs_resample": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_int, _vp, C.c_int]),
+    "mhs_extract_points_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp, _vp]),
+    "mhs_extract_points": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

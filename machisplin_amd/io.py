@@ -97,6 +97,20 @@ def read_stack(paths, ifd: int = 0, geom: Geometry | None = None) -> RasterStack
     return RasterStack(g0, torch.stack(planes), nodata)
 
 
+def read_aligned(paths, geom: Geometry | None = None, methods="bilinear", ifd: int = 0) -> RasterStack:
+    """One float32 stack from GeoTIFFs on DIFFERENT grids of one coordinate system (a 30 m DEM and a 1 km climate raster, say):
+    each file is read as it is and brought onto ``geom`` (default: the first file's grid) by ``resample.align`` with
+    ``methods`` -- one for all, or one per file.  ``read_stack`` stays the strict reader of layers that share a grid."""
+    from .resample import align
+    stacks = []
+    for p in paths:
+        g, pl, nd = read_raster(p, ifd)
+        if g is None:
+            raise ValueError(f"{p}: no georeference found (tags or .tfw)")
+        stacks.append(RasterStack(g, pl[None], nd))
+    return align(stacks, geom, methods)
+
+
 def write_geotiff(path: str, geom: Geometry, plane, nodata: float = float("nan"), compress: bool = True) -> None:
     """terra::writeRaster(layer, "<name>.tif") (V73:1011,1020): FLT4S strips, deflate; NaN -> nodata if given."""
     import torch
