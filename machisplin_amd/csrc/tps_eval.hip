@@ -11,15 +11,21 @@
 //     cost no VALU or LDS bandwidth;
 //   * log(r2) is computed in-kernel from a 1024-entry {1/c, log c} table staged in
 //     LDS: r2 = 2^e m, log r2 = e ln2 + log c_i + log1p(m/c_i - 1), |m/c_i - 1| <= 2^-11,
-//     cubic log1p => absolute error < 2e-14 (ocml's log costs ~70 FP64 instructions).
+//     cubic log1p => log m to 2e-14; log r2 itself to 1.85e-13 absolute near r2 = 1 (L = e ln2 + log c and L + log1p are
+//     rounded at ~709, where half an ulp is 5.7e-14, and the bias constant is rounded there too): the bound is derived in
+//     tests/test_devmath_host.py, 1.7e-13 measured on the host restatement tests/devmath_ref.py against a 50-digit
+//     reference (2.9e-13 for r2 up to 2^1000), profiles/devmath_bounds.txt.  (ocml's log costs ~70 FP64 instructions.)
 //     Neighbouring lanes see neighbouring r2, so table reads mostly broadcast.
 //
 // Large windows take the FAR-FIELD-INTERPOLATED path (tps_ff_*): the window is cut into
 // tiles that are square in the spline's scaled coordinates; for a tile, knots outside the
 // 3 x 3 block of tiles around it are at least 1.5 tile widths from its centre, where
 // sum_j c_j phi(r_j) is analytic and a 16 x 16 tensor Chebyshev interpolant reproduces it to
-// FP64 rounding (measured 1.5e-15 of sum_j |c_j phi_j| with every far knot on the block's
-// boundary).  So the far knots are summed at the tile's 256 nodes only (one wave per tile, the
+// 5.8e-15 of sum_j |c_j phi_j| over the far knots for square tiles, 4.7e-14 and 8.5e-14 at the tile aspects
+// 1.245 and 0.837, the ends of the window far_plan_choose accepts (the interpolant in long double against the
+// exact sum, 44 far knots within a cell of the block's boundary or on it; the worst single knot: 6.0e-13, 5.2e-11
+// and 2.1e-11 of its own largest |phi| on the tile -- tests/test_devmath_host.py, profiles/devmath_bounds.txt;
+// on the device: test_far_field_rule_at_its_worst_accepted_geometry).  So the far knots are summed at the tile's 256 nodes only (one wave per tile, the
 // same inner loop), each cell gets  Ly F Lx'  (32 FMAs) plus the direct sum over the few knots of
 // the 3 x 3 block.  Same result as the direct sum to rounding, ~100x fewer kernel evaluations at
 // 5 000 knots on a 10 000 x 10 000 grid.  mhs_tps_eval_mode() forces either path.

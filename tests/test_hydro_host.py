@@ -150,14 +150,23 @@ def test_invariants_on_the_test_planes(kind, shape):
 
 
 class _Call:
-    """the two entry points on HOST arrays that are never read: every refusal comes before the first device call"""
+    """the two entry points on HOST arrays that are never read: every refusal comes before the first device call.  Where an
+    earlier test of the session has initialised a device, a call with good arguments does run: the _dev entry then gets
+    device planes (it would take the host arrays' addresses for device memory), the host entry keeps the host arrays."""
 
-    def __init__(self):
+    def __init__(self, fn):
         self.lib = _lib.load()
         self.grid = _lib.Grid(0.0, 10.0, 1.0, 1.0, 10, 12)
         self.z = np.zeros((2, 10, 12), dtype=np.float32)
-        self.stack = _lib.Stack(self.z.ctypes.data, 2, _lib.F32, 120, 12, NAN)
         self.planes = np.zeros((4, 10, 12))
+        zp, self.pp = self.z.ctypes.data, [self.planes[k].ctypes.data for k in range(4)]
+        if fn.endswith("_dev") and _lib._inited_device is not None:
+            import torch
+            dev = torch.device("cuda", _lib._inited_device)
+            self.zd = torch.zeros((2, 10, 12), dtype=torch.float32, device=dev)
+            self.pd = torch.zeros((4, 10, 12), dtype=torch.float64, device=dev)
+            zp, self.pp = self.zd.data_ptr(), [self.pd[k].data_ptr() for k in range(4)]
+        self.stack = _lib.Stack(zp, 2, _lib.F32, 120, 12, NAN)
         self.units = dict(dx=30.0, dx_row=None, dy=30.0, z_factor=1.0)
 
     def __call__(self, fn, grid=None, stack=None, layer=0, min_slope_tan=0.001, max_passes=0, out="default", which=(0, 1, 2, 3),
@@ -165,7 +174,7 @@ class _Call:
         u = dict(self.units, **unit_kw)
         rows = None if u["dx_row"] is None else np.ascontiguousarray(u["dx_row"], dtype=np.float64)
         cu = _lib.TerrainUnits(u["dx"], None if rows is None else rows.ctypes.data, u["dy"], u["z_factor"])
-        o = _lib.HydroOut(*[self.planes[k].ctypes.data if k in which else None for k in range(4)])
+        o = _lib.HydroOut(*[self.pp[k] if k in which else None for k in range(4)])
         op = None if out is None else C.byref(o)
         info = _lib.HydroInfo()
         head = (C.byref(grid or self.grid), C.byref(stack or self.stack), layer, None if units is None else C.byref(cu), min_slope_tan,
@@ -179,7 +188,7 @@ class _Call:
 
 @pytest.mark.parametrize("fn", ["mhs_hydro_dev", "mhs_hydro"])
 def test_refusals_come_before_any_device_call(fn):
-    call = _Call()
+    call = _Call(fn)
 
     def refused(needle, **kw):
         rc, msg = call(fn, **kw)

@@ -81,19 +81,28 @@ def test_hand_worked_shares():
 
 
 class _Call:
-    """the two entry points on HOST arrays that are never read: every refusal comes before the first device call"""
+    """the two entry points on HOST arrays that are never read: every refusal comes before the first device call.  Where an
+    earlier test of the session has initialised a device, a call with good arguments does run: the _dev entry then gets
+    device planes (it would take the host arrays' addresses for device memory), the host entry keeps the host arrays."""
 
-    def __init__(self):
+    def __init__(self, fn):
         self.lib = _lib.load()
         self.grid = _lib.Grid(0.0, 10.0, 1.0, 1.0, 10, 12)
         self.z = np.zeros((2, 10, 12), dtype=np.float32)
-        self.stack = _lib.Stack(self.z.ctypes.data, 2, _lib.F32, 120, 12, NAN)
         self.planes = np.zeros((3, 10, 12))
+        zp, self.pp = self.z.ctypes.data, [self.planes[k].ctypes.data for k in range(3)]
+        if fn.endswith("_dev") and _lib._inited_device is not None:
+            import torch
+            dev = torch.device("cuda", _lib._inited_device)
+            self.zd = torch.zeros((2, 10, 12), dtype=torch.float32, device=dev)
+            self.pd = torch.zeros((3, 10, 12), dtype=torch.float64, device=dev)
+            zp, self.pp = self.zd.data_ptr(), [self.pd[k].data_ptr() for k in range(3)]
+        self.stack = _lib.Stack(zp, 2, _lib.F32, 120, 12, NAN)
 
     def __call__(self, fn, layer=0, min_slope_tan=0.001, max_passes=0, exponent=1.1, out="default", which=(0, 1, 2), out_dtype=_lib.F64,
                  ld=12, dx=30.0):
         cu = _lib.TerrainUnits(dx, None, 30.0, 1.0)
-        o = _lib.HydroMfdOut(*[self.planes[k].ctypes.data if k in which else None for k in range(3)])
+        o = _lib.HydroMfdOut(*[self.pp[k] if k in which else None for k in range(3)])
         info = _lib.HydroInfo()
         head = (C.byref(self.grid), C.byref(self.stack), layer, C.byref(cu), min_slope_tan, max_passes, exponent,
                 None if out is None else C.byref(o), out_dtype)
@@ -106,7 +115,7 @@ class _Call:
 
 @pytest.mark.parametrize("fn", ["mhs_hydro_mfd_dev", "mhs_hydro_mfd"])
 def test_refusals_come_before_any_device_call(fn):
-    call = _Call()
+    call = _Call(fn)
 
     def refused(needle, **kw):
         rc, msg = call(fn, **kw)

@@ -97,14 +97,23 @@ def test_restatement_relief_with_one_na():
 
 
 class _Call:
-    """the six entry points on HOST arrays that are never read: every refusal comes before the first device call"""
+    """the six entry points on HOST arrays that are never read: every refusal comes before the first device call.  Where an
+    earlier test of the session has initialised a device, a call with good arguments does run: a _dev entry then gets
+    device planes (it would take the host arrays' addresses for device memory), a host entry keeps the host arrays."""
 
-    def __init__(self):
+    def __init__(self, fn):
         self.lib = _lib.load()
         self.grid = _lib.Grid(0.0, 10.0, 1.0, 1.0, 10, 12)
         self.z = np.zeros((2, 10, 12), dtype=np.float32)
-        self.stack = _lib.Stack(self.z.ctypes.data, 2, _lib.F32, 120, 12, float("nan"))
         self.out = np.zeros((10, 10, 12))
+        zp, self.op = self.z.ctypes.data, self.out.ctypes.data
+        if fn.endswith("_dev") and _lib._inited_device is not None:
+            import torch
+            dev = torch.device("cuda", _lib._inited_device)
+            self.zd = torch.zeros((2, 10, 12), dtype=torch.float32, device=dev)
+            self.od = torch.zeros((10, 10, 12), dtype=torch.float64, device=dev)
+            zp, self.op = self.zd.data_ptr(), self.od.data_ptr()
+        self.stack = _lib.Stack(zp, 2, _lib.F32, 120, 12, float("nan"))
         self.units = dict(dx=30.0, dx_row=None, dy=30.0, z_factor=1.0)
 
     def __call__(self, fn, grid=None, stack=None, layer=0, window=(0, 10, 0, 12), mask=1, out="default", out_dtype=_lib.F64, ld=12,
@@ -115,7 +124,7 @@ class _Call:
         g = C.byref(grid or self.grid)
         s = C.byref(stack or self.stack)
         up = None if units is None else C.byref(cu)
-        o = self.out.ctypes.data if out == "default" else out
+        o = self.op if out == "default" else out
         dev = fn.endswith("_dev")
         tail = (o, out_dtype, ld, plane_stride, None) if dev else (o, out_dtype)
         f = getattr(self.lib, fn)
@@ -133,7 +142,7 @@ ALL = ("mhs_terrain_dev", "mhs_relief_dev", "mhs_geomorphon_dev", "mhs_terrain",
 
 @pytest.mark.parametrize("fn", ALL)
 def test_refusals_come_before_any_device_call(fn):
-    call = _Call()
+    call = _Call(fn)
     kind = fn.replace("_dev", "")
 
     def refused(needle, **kw):

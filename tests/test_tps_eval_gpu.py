@@ -3,8 +3,10 @@ predict.Krig restatement, same coefficients, same cell centres."""
 import numpy as np
 import pytest
 
+import devmath_ref as R
 from conftest import synth_stations
 from oracle import tps as otps
+from test_devmath_host import r2logr2_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -86,8 +88,12 @@ def test_far_field_path_equals_direct_sum(hip, n, nrow, ncol, xres, yres, window
         d2 = (x[None, :] - m["knots"][j, 0]) ** 2 + (yy[:, None] - m["knots"][j, 1]) ** 2
         with np.errstate(divide="ignore", invalid="ignore"):
             S = S + np.abs(m["c"][j]) * np.abs(np.where(d2 > 0, d2 * np.log(d2), 0.0)) * (0.5 / (8 * np.pi))
-    # 1e-13 S: both paths carry the table log's 2e-14 absolute error per term (devmath.h), at different
-    # points; the interpolation itself contributes ~1e-15 S
+    # 1e-13 S: both paths carry the table log's absolute error per term, at different points -- up to 1.85e-13 on
+    # log r2 near r2 = 1 (two roundings at e ln 2 ~ 709 and the rounded bias; the 2e-14 in devmath.h is log m alone:
+    # tests/test_devmath_host.py derives the bound, profiles/devmath_bounds.txt holds the 1.7e-13 measured), which is
+    # ~1e-13 of a term only where |log r2| >= 2, and the terms' errors do not add up in one direction; the interpolation
+    # itself contributes 6e-15 S on square tiles and up to 8e-14 S at the ends of the accepted aspect window
+    # (test_far_field_rule_at_its_worst_accepted_geometry)
     assert np.abs(far - direct).max() <= 1e-13 * S.max(), (np.abs(far - direct).max(), S.max())
     assert np.abs(far - direct).max() / scale < 1e-10
     assert np.abs(far - want).max() / scale < RTOL
@@ -209,3 +215,109 @@ def test_bad_arguments_are_rejected(hip):
         hip.interpolate(g, t, window=(0, 11, 0, 10))
     with pytest.raises(hip.MhsError):
         hip.Tps.from_coef(np.random.rand(5, 2), np.zeros(5), [0, 0, 0], 0.0, [0, 0], [0, 1])
+
+
+def _term_bounds(knots, cw, u, v):
+    """sum_j |cw_j| r2logr2_bound(|(u, v) - knot_j|^2) at the points u[None, :] x v[:, None]: the log bound of
+    tests/test_devmath_host.py summed over the terms"""
+    u, v = np.asarray(u)[None, :], np.asarray(v)[:, None]
+    s = np.zeros((v.shape[0], u.shape[1]))
+    for (ku, kv), w in zip(knots, cw):
+        d2 = (u - ku) ** 2 + (v - kv) ** 2
+        s = s + abs(w) * np.where(d2 > 0, r2logr2_bound(np.where(d2 > 0, d2, 1.0)), 0.0)
+    return s
+
+
+def far_field_worst_case(hip, k4, ty, lo=0.8, hi=1.25):
+    """The body of test_far_field_rule_at_its_worst_accepted_geometry for the layout devmath_ref.far_layout(k4);
+    returns the figures it asserted on."""
+    e, ty_l, kn, c = R.far_layout(k4)
+    assert ty_l == ty
+    g = hip.Geometry(e.xmin, e.ymax, e.xres, e.yres, e.nr, e.nc)
+    t = hip.Tps.from_coef(kn, c, [0.0, 0.0, 0.0], 0.0, [0.0, 0.0], [1.0, 1.0])
+    try:
+        hip.eval_mode(hip.EVAL_FAR_FIELD)
+        far = hip.interpolate(g, t).cpu().numpy()
+        tiles = t.eval_plan()[:2]
+        hip.eval_mode(hip.EVAL_DIRECT)
+        direct = hip.interpolate(g, t).cpu().numpy()
+    finally:
+        hip.eval_mode(hip.EVAL_AUTO)
+    plan = R.far_plan_choose(kn, e, lo=lo, hi=hi)
+    print("4 * aspect", k4, "device tiles", tiles, "restated plan", plan and (plan["tx"], plan["ty"], plan["tile_aspect"]))
+    assert tiles == (64, ty)
+    assert plan is not None and (plan["tx"], plan["ty"]) == tiles          # the restated far_plan_choose agrees
+    share, fi, ni = R.far_method_error(e, plan, kn, c, 2, 2)
+    print("method error, share of the far knots' sum:", share)
+    assert len(fi) >= 32 and share <= 1e-10                                # what the aspect window has to keep
+    rows, cols = slice(2 * ty, 3 * ty), slice(128, 192)
+    want64, Lx, Ly, F = R.far_tile_f64(e, plan, kn, c, [0.0, 0.0, 0.0], 2, 2)
+    uc, vc = R.cell_coords(e, range(128, 192), range(2 * ty, 3 * ty))
+    exact = R.phi_sum_ld(kn, c, uc, vc)
+    S_far = R.phi_sum_ld(kn[fi], c[fi], uc, vc, absolute=True).astype(np.float64)
+    cw = c * R.TPS_KK
+    un, vn = R.ff_node_coords(e, plan, 2, 2, R.cheb_points())
+    lam = np.abs(Lx).sum(1).max() * np.abs(Ly).sum(1).max()                 # largest absolute row sums
+    assert 1.0 < lam < 2.73 ** 2                                             # (2 / pi) ln 16 + 0.9625 per direction
+    allow_far = lam * _term_bounds(kn[fi], cw[fi], un, vn).max()
+    allow = allow_far + _term_bounds(kn[ni], cw[ni], uc, vc)
+    allow_direct = _term_bounds(kn, cw, uc, vc)
+    d64 = np.abs(far[rows, cols] - want64)
+    dex = np.abs((far[rows, cols].astype(R.LD) - exact).astype(np.float64))
+    ddi = np.abs((direct[rows, cols].astype(R.LD) - exact).astype(np.float64))
+    method = 1.5 * share * S_far.max()
+    out = {"far_vs_f64": (d64 / allow).max(), "far_vs_exact": (dex / (method + allow)).max(), "direct_vs_exact": (ddi / allow_direct).max(),
+           "far_vs_exact_abs": dex.max(), "method_abs": share * S_far.max(), "allow": allow.max(), "S_far": S_far.max()}
+    print(out)
+    assert (d64 <= allow).all(), out                 # device far against the float64 restatement of the same interpolant
+    assert (dex <= method + allow).all(), out        # device far against the exact sum
+    assert (ddi <= allow_direct).all(), out          # device direct against the exact sum: the log bound alone
+    other = np.ones(far.shape, dtype=bool)
+    other[rows, cols] = False
+    rest = np.abs(far - direct)[other].max()
+    print("other cells, far - direct:", rest, "of max |direct|", rest / np.abs(direct).max())
+    assert not np.array_equal(far, direct)
+    assert rest <= 1e-9 * np.abs(direct).max()
+    return out
+
+
+@pytest.mark.parametrize("k4,ty", [(4.0, 64), (2.49, 32), (2.51, 48)])
+def test_far_field_rule_at_its_worst_accepted_geometry(hip, k4, ty):
+    """5 x 5 tiles of 64 columns by ty rows with 4 * aspect = 4.0, 2.49, 2.51 (tile aspect 1.0, 1.245, 0.837: the
+    square tile and the two ends of far_plan_choose's window), 48 knots with positive c: 44 in the ring of bins at
+    Chebyshev distance 2 from the centre tile, within a cell of the edge that faces it (some exactly on it), or
+    collapsed onto the rim bins; 4 on the bin edges of the 3 x 3 block.  On the centre tile's cells:
+
+      far - float64 restatement of the same interpolant (devmath_ref.far_tile_f64)   <= rounding allowance
+      far - exact sum (long double)      <= 1.5 * the interpolant's own error in long double + rounding allowance
+      direct - exact sum                 <= the log bound summed over the terms
+
+    The rounding allowance is the log bound of tests/test_devmath_host.py (r2logr2_bound) summed over the terms: for
+    the interpolated part the largest such sum over the tile's nodes times the product of the largest absolute row
+    sums of Lx and Ly, for the near knots the cell's own sum.  The 1.5 covers float64 nodes against long-double nodes,
+    nothing else.  The interpolant's own error must stay under 1e-10 of the far knots' sum.  On all other cells: far
+    against direct at 1e-9 of the surface, as test_far_field_equals_direct_on_random_geometries has it."""
+    far_field_worst_case(hip, k4, ty)
+
+
+@pytest.mark.parametrize("k4,ty,aspect", [(1.26, 16, 1.26), (1.59, 32, 0.795)])
+def test_far_field_rule_is_refused_just_outside_the_aspect_window(hip, k4, ty, aspect):
+    """The same layout with tiles of aspect 1.26 and 0.795, just outside far_plan_choose's 0.8 .. 1.25: asked for the
+    far-field path, the evaluation must still take the direct sum, as the restated far_plan_choose says, and give the
+    direct sum's values.  (test_far_field_rule_at_its_worst_accepted_geometry holds the window's accepted ends; with
+    this the window cannot widen unnoticed.)"""
+    e, ty_l, kn, c = R.far_layout(k4)
+    assert ty_l == ty and R.far_plan_choose(kn, e) is None
+    wide = R.far_plan_choose(kn, e, lo=0.5, hi=2.0)                       # what a wider window would have tiled
+    assert (wide["tx"], wide["ty"]) == (64, ty) and abs(wide["tile_aspect"] - aspect) < 1e-12
+    g = hip.Geometry(e.xmin, e.ymax, e.xres, e.yres, e.nr, e.nc)
+    t = hip.Tps.from_coef(kn, c, [0.0, 0.0, 0.0], 0.0, [0.0, 0.0], [1.0, 1.0])
+    try:
+        hip.eval_mode(hip.EVAL_FAR_FIELD)
+        far = hip.interpolate(g, t).cpu().numpy()
+        assert t.eval_plan() == (0, 0, 0, 0)
+        hip.eval_mode(hip.EVAL_DIRECT)
+        direct = hip.interpolate(g, t).cpu().numpy()
+    finally:
+        hip.eval_mode(hip.EVAL_AUTO)
+    assert np.array_equal(far, direct)
