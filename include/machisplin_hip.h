@@ -933,6 +933,72 @@ MHS_API int mhs_extract_points_dev(const mhs_grid *src_grid, const mhs_stack *sr
 MHS_API int mhs_extract_points(const mhs_grid *src_grid, const mhs_stack *src_stack, const double *xy, int64_t n, int method,
                                double *out);
 
+/* ---------------------------------------------------------------- proximity --
+ * Distance-to-feature covariates: distance to the coast, to open water, to the channel network, and what follows from knowing
+ * WHICH cell is nearest (the direction to it, another layer's value there, the height above the nearest stream).  The
+ * reference has no such step; its users go to terra::distance.  THE RULE (this text is the specification; csrc/proximity_rule.h
+ * holds it as code).
+ *
+ * Grid of nrow x ncol cells.  A call always treats the WHOLE plane -- there is no window, distance is not local.  Nothing is
+ * known outside the grid: there are no features there.
+ *
+ * FEATURES.  A cell is a feature when the value v of layer `layer`, converted exactly to double, satisfies `where`:
+ *   MHS_PROX_NA      the cell is NA: v is NaN or equals the stack's nodata
+ *   MHS_PROX_VALID   the cell is not NA
+ *   MHS_PROX_LT / LE / GT / GE / EQ / NE     v < / <= / > / >= / == / != threshold; an NA cell never satisfies a comparison
+ *
+ * SEARCH, in exact integers, in units of cells:
+ *   d2(r, c)    = the minimum over the features (fr, fc) of (r - fr)^2 + (c - fc)^2
+ *   index(r, c) = the smallest fr * ncol + fc among the features that attain it: ties go to the smaller row, then to the
+ *                 smaller column
+ *
+ * PRODUCTS, from the (fr, fc) of index; any subset, not none:
+ *   d2      int32
+ *   index   int32
+ *   dist    sqrt((double)d2) * unit: the square root is rounded, then the product
+ *   dir_x   (double)(fc - c) / sqrt((double)d2)
+ *   dir_y   (double)(r - fr) / sqrt((double)d2): the unit vector towards the feature, y positive to the north (row 0 is the
+ *           north edge); both components are 0 at a feature cell
+ *   value   layer `value_layer` of the same stack at cell index, NaN where that cell is NA
+ * The float products are written as out_dtype MHS_F64, or MHS_F32 = the float64 value converted once.  Only + - * /, sqrt and
+ * comparisons occur, so every plane equals a restatement in any IEEE double arithmetic bit for bit.
+ * NO FEATURE ANYWHERE: d2 = -1, index = -1, every float product NaN; the call succeeds and the info says n_features = 0.
+ *
+ * UNITS.  The library does not look at the grid's resolution: `unit` is the ground length of a cell's side, finite and > 0.
+ * OUT OF SCOPE: non-square cells; geodesic distance on lon/lat grids (there the result is in degrees times unit); cost or path
+ * distance; a search radius cap.
+ *
+ * LIMITS, checked with every other argument before the first device call (MHS_ERR_INVALID, the message names the argument):
+ * (nrow - 1)^2 + (ncol - 1)^2 <= INT32_MAX (d2 is an int32) and nrow * ncol <= INT32_MAX (index is an int32).
+ *
+ * The algorithm is exact (csrc/proximity.hip; no jump flooding): the nearest feature of each cell in its own row by wave
+ * scans, per column the lower envelope of the rows' parabolas (Meijster's scan, its separators in int64 with a true floor
+ * division), per cell its envelope segment.  Scratch: 12 bytes per cell of stream-ordered device memory for the length of
+ * the call (the in-row nearest column 4, the envelope's rows 4 and first rows 4), plus 4 bytes per column; MHS_ERR_ALLOC if
+ * there is none. */
+enum { MHS_PROX_NA = 0, MHS_PROX_VALID, MHS_PROX_LT, MHS_PROX_LE, MHS_PROX_GT, MHS_PROX_GE, MHS_PROX_EQ, MHS_PROX_NE };
+typedef struct mhs_proximity_out {   /* the planes to make; any may be NULL, not all */
+    int32_t *d2;
+    int32_t *index;
+    void *dist, *dir_x, *dir_y, *value;   /* out_dtype */
+} mhs_proximity_out;
+typedef struct mhs_proximity_info {
+    int64_t n_features;      /* cells that satisfy `where` */
+    int64_t max_d2;          /* the largest d2 of the plane; -1 without a feature */
+    int64_t scratch_bytes;   /* the call's block of device scratch: 12 per cell, 4 per column and 256-byte alignments */
+} mhs_proximity_info;
+/* DEVICE planes: stack->data covers the whole grid; every plane of `out` is nrow x ld row-major on the device.  value_layer is
+ * looked at only when out->value is set.  Only enqueues on `stream` -- unless info is given: then the stream is synchronised
+ * once, behind the last kernel, to read the two counts. */
+MHS_API int mhs_proximity_dev(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int value_layer,
+                              double unit, const mhs_proximity_out *out, int out_dtype, int64_t ld, void *stream,
+                              mhs_proximity_info *info);
+/* same, HOST planes: stack->data and the planes of `out` (nrow x ncol dense) on the host -- what the R shim hands over.  The
+ * whole plane goes up in one piece and the requested planes come down; no row bands, because the nearest feature of a cell may
+ * lie in any row of the raster, so a band would need the whole plane anyway.  Blocks until done. */
+MHS_API int mhs_proximity(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int value_layer,
+                          double unit, const mhs_proximity_out *out, int out_dtype, mhs_proximity_info *info);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

@@ -295,6 +295,43 @@ mhs_extract <- function(x, xy, method = "simple") {
   out
 }
 
+# ---- distance-to-feature covariates: what terra::distance and terra::gridDist are used for ---------------------------------
+# x: a SpatRaster with square cells.  A cell is a feature where layer `layer` is NA (where = "na": the sea of a land-only DEM),
+# not NA ("valid"), or "lt" "le" "gt" "ge" "eq" "ne" `threshold`.  v: any of "d2" (squared distance in cells, exact), "index"
+# (the nearest feature's cell number; ties go to the smaller row, then the smaller column), "dist" (sqrt(d2) * unit), "dir_x",
+# "dir_y" (the unit vector towards the feature, y to the north) and "value" (layer `value.layer` at the nearest feature).
+# unit = NULL takes the cell width.  Section "proximity" of machisplin_hip.h states the rule; geodesic distance on lon/lat
+# rasters, cost distance and a search radius are out of scope.
+.mhs_proximity_where <- c("na", "valid", "lt", "le", "gt", "ge", "eq", "ne")
+.mhs_proximity_products <- c("d2", "index", "dist", "dir_x", "dir_y", "value")
+mhs_proximity <- function(x, where = "na", threshold = NA_real_, v = "dist", layer = 1L, value.layer = NA_integer_, unit = NULL) {
+  w <- match(where, .mhs_proximity_where)
+  if (length(where) != 1L || is.na(w)) stop("mhs_proximity: where must be one of ", paste(.mhs_proximity_where, collapse = ", "))
+  if (w > 2L && is.na(threshold)) stop("mhs_proximity: where = \"", where, "\" needs a threshold")
+  bad <- setdiff(v, .mhs_proximity_products)
+  if (length(bad) || !length(v)) stop("mhs_proximity: v must name some of ", paste(.mhs_proximity_products, collapse = ", "))
+  if ("value" %in% v && is.na(value.layer)) stop("mhs_proximity: the value product needs value.layer")
+  res <- terra::res(x)
+  if (is.null(unit)) {
+    if (abs(res[1] - res[2]) > 1e-9 * max(res)) stop("mhs_proximity: the cells are not square; resample x (mhs_resample) or give unit")
+    unit <- res[1]
+  }
+  v <- unique(v)
+  pv <- match(v, .mhs_proximity_products)
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  out <- .Call("mhsr_proximity", .mhs_geom(x), vals, NA_real_,
+               c(layer - 1, w - 1, if (w > 2L) threshold else 0, if (is.na(value.layer)) -1 else value.layer - 1, unit),
+               as.integer(sum(2^(pv - 1))))
+  layers <- lapply(seq_along(v), function(j) {
+    r <- terra::setValues(terra::rast(x[[1]]), out[[pv[j]]])
+    names(r) <- v[j]
+    r
+  })
+  r <- do.call(c, layers)
+  attr(r, "info") <- stats::setNames(out[[7]], c("n_features", "max_d2"))
+  r
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

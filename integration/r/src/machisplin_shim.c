@@ -446,6 +446,50 @@ SEXP mhsr_extract(SEXP geom, SEXP planes, SEXP nodata, SEXP xy, SEXP method) {
     return out;
 }
 
+/* Distance to the nearest feature cell (machisplin_hip.h "proximity"): what terra::distance and terra::gridDist are used for.
+ * planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, unit) with layer and value_layer 0-based
+ * (value_layer is read only for the value product) and where 0 na, 1 valid, 2 lt, 3 le, 4 gt, 5 ge, 6 eq, 7 ne; products: bit
+ * mask (1 d2, 2 index, 4 dist, 8 dir_x, 16 dir_y, 32 value).  Returns list(d2, index, dist, dir_x, dir_y, value, info) in terra
+ * cell order, NULL where a plane was not asked for: d2 and index integer vectors -- index the nearest feature's terra cell
+ * NUMBER (1-based), both NA_integer_ where the raster has no feature --, the others numeric (NaN there); info = c(n_features,
+ * max_d2).  Runs on the HOST entry point: the whole plane goes up, there are no row bands. */
+SEXP mhsr_proximity(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP products) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_proximity");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 63) Rf_error("mhsr_proximity: products must be a bit mask of 1 d2, 2 index, 4 dist, 8 dir_x, 16 dir_y, 32 value");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 5) Rf_error("mhsr_proximity: opts must be c(layer, where, threshold, value_layer, unit)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_proximity: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 7.0)) Rf_error("mhsr_proximity: where must be 0 .. 7");
+    int value_layer = (o[3] >= 0.0 && o[3] <= 2147483647.0) ? (int)o[3] : -1;
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_proximity: bad grid dimension");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 7));
+    SEXP plane[6] = { R_NilValue, R_NilValue, R_NilValue, R_NilValue, R_NilValue, R_NilValue };
+    int n_protect = 1;
+    for (int k = 0; k < 6; ++k)
+        if (mask & (1 << k)) { plane[k] = PROTECT(Rf_allocVector(k < 2 ? INTSXP : REALSXP, n)); ++n_protect; }
+    mhs_proximity_out po = { (mask & 1) ? (int32_t *)INTEGER(plane[0]) : NULL, (mask & 2) ? (int32_t *)INTEGER(plane[1]) : NULL,
+                             (mask & 4) ? REAL(plane[2]) : NULL, (mask & 8) ? REAL(plane[3]) : NULL, (mask & 16) ? REAL(plane[4]) : NULL,
+                             (mask & 32) ? REAL(plane[5]) : NULL };
+    mhs_proximity_info info = { 0 };
+    int rc = mhs_proximity(&g, &st, (int)o[0], (int)o[1], o[2], value_layer, o[4], &po, MHS_F64, &info);
+    if (rc == MHS_OK) {
+        if (mask & 1)
+            for (R_xlen_t k = 0; k < n; ++k) if (INTEGER(plane[0])[k] < 0) INTEGER(plane[0])[k] = NA_INTEGER;
+        if (mask & 2)
+            for (R_xlen_t k = 0; k < n; ++k) INTEGER(plane[1])[k] = INTEGER(plane[1])[k] < 0 ? NA_INTEGER : INTEGER(plane[1])[k] + 1;
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 2)); ++n_protect;
+        REAL(inf)[0] = (double)info.n_features; REAL(inf)[1] = (double)info.max_d2;
+        for (int k = 0; k < 6; ++k) SET_VECTOR_ELT(out, k, plane[k]);
+        SET_VECTOR_ELT(out, 6, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

@@ -93,6 +93,17 @@ class HydroInfo(C.Structure):
                 ("solves_flat", C.c_int64), ("solves_acc", C.c_int64), ("ms_fill", C.c_double), ("ms_flat", C.c_double), ("ms_acc", C.c_double)]
 
 
+class ProximityOut(C.Structure):
+    """struct mhs_proximity_out"""
+    _fields_ = [("d2", C.c_void_p), ("index", C.c_void_p), ("dist", C.c_void_p), ("dir_x", C.c_void_p), ("dir_y", C.c_void_p),
+                ("value", C.c_void_p)]
+
+
+class ProximityInfo(C.Structure):
+    """struct mhs_proximity_info"""
+    _fields_ = [("n_features", C.c_int64), ("max_d2", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -208,6 +219,10 @@ SIGNATURES = {
     "mhs_resample": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_int, _vp, C.c_int]),
     "mhs_extract_points_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp, _vp]),
     "mhs_extract_points": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp]),
+    "mhs_proximity_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                    C.POINTER(ProximityOut), C.c_int, _i64, _vp, C.POINTER(ProximityInfo)]),
+    "mhs_proximity": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                C.POINTER(ProximityOut), C.c_int, C.POINTER(ProximityInfo)]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

@@ -27,6 +27,8 @@ HYDRO = ("filled", "flowdir", "flowacc", "twi")                     # the planes
 HYDRO_SPEC = {"twi": ("twi", False), "log_flowacc": ("flowacc", True)}      # covariates(): spec name -> (product, take its log)
 HYDRO_MFD = ("filled", "flowacc", "twi")                            # the planes of mhs_hydro_mfd_out, in its order
 HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True)}      # the same, made by hydro_mfd at its defaults
+DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covariates(): spec name -> the predicate of proximity
+STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
 SOLAR = ("svf", "direct", "sun_hours", "horizon")                   # the products of mhs_solar, in its order; horizon is 16 planes
 # the sixteen ray directions of section "solar", clockwise from north: (rows south, columns east)
 SOLAR_DIRECTIONS = ((-1, 0), (-2, 1), (-1, 1), (-1, 2), (0, 1), (1, 2), (1, 1), (2, 1),
@@ -356,6 +358,24 @@ def _hydro(stack, layer, products, exponent, lonlat, z_factor, min_slope_deg, ma
     return res, info
 
 
+def _stream_layers(dem_stack, demf, flowacc, thresholds, spec):
+    """the ("dist_stream", A) and ("above_stream", A) layers of :func:`covariates`: one proximity call per threshold A on a
+    float64 stack of the D8 flow accumulation and the DEM (NA as NaN), which makes the distance and the DEM's value at the
+    nearest stream cell; keyed (name, A)"""
+    import torch
+    from . import proximity as _prox
+    pair = RasterStack(dem_stack.geom, torch.stack([flowacc.to(torch.float64), demf.to(torch.float64)]), float("nan"))
+    out = {}
+    for a in thresholds:
+        want = tuple(dict.fromkeys(STREAM_SPEC[e[0]] for e in spec if len(e) == 2 and e[0] in STREAM_SPEC and float(e[1]) == a))
+        got, _ = _prox.proximity(pair, 0, "ge", a, want, value_layer=1)
+        if "dist" in got:
+            out[("dist_stream", a)] = got["dist"].to(torch.float32)
+        if "value" in got:
+            out[("above_stream", a)] = (pair.planes[1] - got["value"]).to(torch.float32)
+    return out
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
@@ -368,6 +388,13 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       ("svf" | "direct" | "sun_hours", search)    that solar product within ``search`` cells (:func:`solar`; one call per
                                                   distinct search length makes all of its layers) with the tables ``sun``, a
                                                   :class:`SunTables`, or those of :func:`sun_tables` at ``lat`` degrees
+      "dist_na"                                   distance to the nearest NA cell of the DEM -- the sea, for a land-only DEM
+                                                  (:func:`proximity.proximity`, in the geometry's cell width; square cells)
+      ("dist_le" | "dist_ge", t)                  distance to the nearest cell whose elevation is <= t / >= t
+      ("dist_stream", A)                          distance to the nearest cell whose D8 ``flowacc`` is >= A (the one
+                                                  :func:`hydro` call that makes ``twi`` / ``log_flowacc`` serves these too)
+      ("above_stream", A)                         the DEM minus the DEM at that nearest stream cell, in elevation units:
+                                                  Euclidean height above the nearest drainage
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -380,14 +407,23 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     planes[0] = demf
     names = ["dem"]
     by_name = {}
-    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC]
+    for e in spec:
+        if e[0] in STREAM_SPEC and len(e) != 2:
+            raise ValueError(f"{e[0]!r} takes one argument, the flow accumulation from which a cell is a stream")
+        if e[0] in DIST_SPEC and len(e) != (1 if e[0] == "dist_na" else 2):
+            raise ValueError(f"{e[0]!r} takes {'no argument' if e[0] == 'dist_na' else 'one threshold'}")
+    stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
+    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
     for table, call in ((HYDRO_SPEC, hydro), (HYDRO_MFD_SPEC, hydro_mfd)):
         hv = [e[0] for e in spec if len(e) == 1 and e[0] in table]
-        if hv:                                    # one hydrology call of a route makes both of its layers
-            hp, _ = call(dem_stack, layer, tuple(dict.fromkeys(table[n][0] for n in hv)), lonlat=lonlat, z_factor=z_factor)
+        extra = ("flowacc",) if stream_a and call is hydro else ()          # the streams are cut from the D8 accumulation
+        if hv or extra:                           # one hydrology call of a route makes all of its layers
+            hp, _ = call(dem_stack, layer, tuple(dict.fromkeys([table[n][0] for n in hv] + list(extra))), lonlat=lonlat, z_factor=z_factor)
+            if extra:
+                by_name.update(_stream_layers(dem_stack, demf, hp["flowacc"], stream_a, spec))
             for n in hv:
                 product, log = table[n]
                 by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
@@ -396,8 +432,14 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
         sv = tuple(dict.fromkeys(e[0] for e in spec if len(e) > 1 and e[0] in sun_names and int(e[1]) == L))
         got = solar(dem_stack, L, sv, sun, layer, lonlat, lat, z_factor, out_dtype=torch.float32)
         by_name.update({(n, L): p for n, p in zip(sv, got)})
+    from . import proximity as _prox
+    for e in dict.fromkeys(e for e in spec if e[0] in DIST_SPEC):
+        by_name[e] = _prox.proximity(dem_stack, layer, DIST_SPEC[e[0]], float(e[1]) if len(e) > 1 else None, "dist", out_dtype=torch.float32)[0]
     for k, e in enumerate(spec):
-        if len(e) > 1 and e[0] in sun_names:
+        if e[0] in DIST_SPEC or e[0] in STREAM_SPEC:
+            planes[1 + k] = by_name[e if e[0] in DIST_SPEC else (e[0], float(e[1]))]
+            names.append(e[0] + (f"{float(e[1]):g}" if len(e) > 1 else ""))
+        elif len(e) > 1 and e[0] in sun_names:
             planes[1 + k] = by_name[(e[0], int(e[1]))]
             names.append(f"{e[0]}{int(e[1])}")
         elif len(e) == 1:
