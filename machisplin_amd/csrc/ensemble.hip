@@ -1260,9 +1260,19 @@ static int launch_tree_kernel(const mhs_model *m, K lds_kern, K global_kern, dim
 template <bool GBM, bool NA_ONLY>
 static int launch_trees(const mhs_model *m, const StackDev &s, const PredGeom &g, double w, int acc,
                         double *out, hipStream_t st, int64_t total, const unsigned *na_gate = nullptr) {
+    const size_t xs_bytes = (size_t)m->p * TREE_R * 256 * sizeof(double);
+    if (xs_bytes > LDS_MAX) {
+        // p >= 41 (the loaders take up to 64): the predictors of two cells per lane do not fit LDS at all -- one cell per lane,
+        // nodes from global memory (finish_trees has cleared lds_ok: its budget is this xs_bytes)
+        const size_t xs1 = (size_t)m->p * 256 * sizeof(double);
+        const auto kern = tree_kernel<GBM, false, 1, NA_ONLY>;
+        MHS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs1));
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), xs1, st, m->nodes, m->tree_off, m->chunks, m->n_chunks,
+                           m->n_trees, m->init_f, m->p, s, g, w, acc, out, na_gate);
+        return MHS_OK;
+    }
     const int64_t half = (total + TREE_R - 1) / TREE_R;
     const unsigned blocks = (unsigned)((half + 255) / 256);
-    const size_t xs_bytes = (size_t)m->p * TREE_R * 256 * sizeof(double);
     if (!NA_ONLY && m->lds_ok && total <= TREE_SPLIT_MAX_CELLS && m->n_chunks >= 4) {
         const int shares = std::min(m->n_chunks, TREE_SPLIT_SHARES);
         mhs_model *mm = const_cast<mhs_model *>(m);

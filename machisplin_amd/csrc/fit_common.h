@@ -135,7 +135,10 @@ inline void fit_sorted_orders(const double *X, int64_t n, int p, int *out) {
 
 inline int fit_check_batch(const char *fn, int count, int p, int max_p, int min_p = 2) {
     FIT_REQUIRE(count >= 1 && count <= 65535, "count out of range");
-    FIT_REQUIRE(p >= min_p && p <= max_p, "p (covariates + LONG + LAT) out of range");
+    if (!(p >= min_p && p <= max_p)) {
+        set_error("%s: p (covariates + LONG + LAT) out of range: this fit takes %d .. %d predictors", fn, min_p, max_p);
+        return MHS_ERR_INVALID;
+    }
     return MHS_OK;
 }
 

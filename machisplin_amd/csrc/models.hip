@@ -43,7 +43,7 @@ int finish_trees(mhs_model *m, const std::vector<Node> &nodes, const std::vector
 int check_common(int p, mhs_model **out) {
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(out != nullptr, "out is NULL");
-    MHS_REQUIRE(p >= 2 && p <= 64, "p (covariates + LONG + LAT) out of range");
+    MHS_REQUIRE(p >= 2 && p <= 64, "p (covariates + LONG + LAT) out of range: the loaders take 2 .. 64 predictors");
     return MHS_OK;
 }
 
@@ -120,7 +120,8 @@ int mhs_lm_load(const double *coef, int p, mhs_model **out) {
 int mhs_nnet_load(const double *wts, int p, int size, double y_scale, double y_shift, mhs_model **out) {
     if (int rc = check_common(p, out)) return rc;
     MHS_REQUIRE(wts != nullptr && size >= 1 && size <= 4096, "bad nnet arguments");
-    MHS_REQUIRE(p <= PMAX, "p exceeds the predictors supported for nnet");
+    static_assert(PMAX == 12, "the message below names the limit");
+    MHS_REQUIRE(p <= PMAX, "p exceeds the 12 predictors supported for nnet");
     Loading m;
     m->kind = K_NNET; m->p = p; m->n0 = size; m->s0 = y_scale; m->s1 = y_shift;
     if (int rc = to_device(wts, (size_t)(p + 1) * size + size + 1, &m->dpar)) return rc;
@@ -164,7 +165,7 @@ int mhs_svr_load(const double *alpha, const double *sv, int64_t nsv, int p, doub
                  mhs_model **out) {
     if (int rc = check_common(p, out)) return rc;
     MHS_REQUIRE(alpha && sv && x_center && x_scale && nsv >= 1 && nsv < (1LL << 30), "bad ksvm arguments");
-    MHS_REQUIRE(p <= PMAX, "p exceeds the predictors supported for ksvm");
+    MHS_REQUIRE(p <= PMAX, "p exceeds the 12 predictors supported for ksvm");
     MHS_REQUIRE(sigma > 0, "sigma must be positive");
     for (int j = 0; j < p; ++j) MHS_REQUIRE(x_scale[j] != 0.0, "x_scale has a zero entry");
     const int stride = ((p + 1) + 3) & ~3;  // doubles per support vector, 32-byte multiple

@@ -23,6 +23,7 @@ void set_error(const char *fmt, ...) {
 
 int hip_fail(hipError_t e, const char *what, const char *file, int line) {
     set_error("HIP error %d (%s) in %s at %s:%d", (int)e, hipGetErrorString(e), what, file, line);
+    (void)hipGetLastError();      // reported here: the next user of the runtime in this process (PyTorch) must not find it again
     return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MHS_ERR_NODEVICE
          : e == hipErrorOutOfMemory ? MHS_ERR_ALLOC : MHS_ERR_HIP;
 }

@@ -42,6 +42,8 @@ class Model:
         X = np.asfortranarray(np.asarray(X, dtype=np.float64))
         if X.ndim != 2 or X.shape[1] != self.p:
             raise ValueError(f"X must be n x {self.p}")
+        if self._h is None:
+            raise ValueError("this model holds a fit's record only: the evaluators take 2 .. 64 predictors")
         out = np.empty(X.shape[0])
         _lib.check(_lib.lib().mhs_predict_points(self._h, X.ctypes.data, X.shape[0], out.ctypes.data))
         return out
@@ -152,7 +154,11 @@ def _nnet_scaled(y):
 
 
 def _nnet_object(w, p, size, mx, mn, value, counts, fail):
-    m = Nnet(w, p, size, mx, mn)
+    if p >= 2:
+        m = Nnet(w, p, size, mx, mn)
+    else:       # the fit takes one predictor, the evaluators start at two (a covariate-free stack has LONG and LAT): the
+        m = Nnet.__new__(Nnet)      # fit's record without a device model
+        Model.__init__(m, None, p)
     m.wts, m.value, m.counts, m.fail = w, float(value), (int(counts[0]), int(counts[1])), int(fail)
     return m
 

@@ -181,9 +181,25 @@ def nnet_value_grad(w, X, y, size):
     return val, np.concatenate([g1.ravel(), g2])
 
 
-def vmmin(b0, fn_gr, maxit=10000, abstol=1e-4, reltol=1e-8):
+TRACE_EVENTS = ("step_reduction", "d1_reset", "periodic_reset", "no_progress_restart", "stop_abstol", "stop_reltol", "uphill",
+                "maxit")
+
+
+def vmmin(b0, fn_gr, maxit=10000, abstol=1e-4, reltol=1e-8, trace=None):
     """R's optim(method = "BFGS"): variable-metric minimiser of J. C. Nash as coded in src/appl/optim.c (vmmin).
-    fn_gr(b) -> (value, gradient).  Returns b, value, function count, gradient count, fail flag."""
+    fn_gr(b) -> (value, gradient).  Returns b, value, function count, gradient count, fail flag.
+
+    ``trace``: a dict (a ``collections.Counter`` does) that counts the branches taken, keyed by TRACE_EVENTS -- a rejected
+    trial step, the ``D1 <= 0`` reset of B, the periodic reset after 2 n gradients, the restart from the identity after a
+    search without progress, a search that ended because the value met ``abstol`` / ``reltol``, a direction that is not
+    downhill, the loop left by ``maxit``.  For every event but the step reductions ``trace[event + "_at"]`` lists the gradient
+    counts at which it happened.  Counting changes no result."""
+    def note(event, at=None):
+        if trace is not None:
+            trace[event] = trace.get(event, 0) + 1
+            if at is not None:
+                trace.setdefault(event + "_at", []).append(at)
+
     stepredn, acctol, reltest = 0.2, 1e-4, 10.0
     b = np.array(b0, dtype=np.float64)
     n = b.size
@@ -216,10 +232,13 @@ def vmmin(b0, fn_gr, maxit=10000, abstol=1e-4, reltol=1e-8):
                     accpoint = bool(np.isfinite(f) and f <= fmin + gradproj * steplength * acctol)
                     if not accpoint:
                         steplength *= stepredn
+                        note("step_reduction")
                 if count == n or accpoint:
                     break
             enough = (f > abstol) and abs(f - fmin) > reltol * (abs(fmin) + reltol)
             if not enough:
+                if count < n:
+                    note("stop_reltol" if f > abstol else "stop_abstol", gradcount)
                 count = n
                 fmin = f
             if count < n:
@@ -236,31 +255,36 @@ def vmmin(b0, fn_gr, maxit=10000, abstol=1e-4, reltol=1e-8):
                     B = B + (D2 * np.outer(t, t) - np.outer(Xc, t) - np.outer(t, Xc)) / D1
                 else:
                     ilast = gradcount
+                    note("d1_reset", gradcount)
             else:
                 if ilast < gradcount:
                     count = 0
                     ilast = gradcount
+                    note("no_progress_restart", gradcount)
         else:
+            note("uphill", gradcount)
             count = 0
             if ilast == gradcount:
                 count = n
             else:
                 ilast = gradcount
         if it >= maxit:
+            note("maxit", gradcount)
             break
         if gradcount - ilast > 2 * n:
             ilast = gradcount
+            note("periodic_reset", gradcount)
         if count == n and ilast == gradcount:
             break
     return b, fmin, funcount, gradcount, int(it >= maxit)
 
 
-def nnet_fit(X, y, wts0, size=10, maxit=10000, abstol=1e-4, reltol=1e-8):
+def nnet_fit(X, y, wts0, size=10, maxit=10000, abstol=1e-4, reltol=1e-8, trace=None):
     """nnet::nnet(mod.form, data = trainNN, size = 10, linout = TRUE, maxit = 10000) (V73:249, V73:463) from the
-    initial weights wts0.  The caller scales the response as V73:455-459 does."""
+    initial weights wts0.  The caller scales the response as V73:455-459 does.  ``trace``: see :func:`vmmin`."""
     X = np.asarray(X, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
-    w, val, nf, ng, fail = vmmin(wts0, lambda w: nnet_value_grad(w, X, y, size), maxit, abstol, reltol)
+    w, val, nf, ng, fail = vmmin(wts0, lambda w: nnet_value_grad(w, X, y, size), maxit, abstol, reltol, trace)
     return w, val, nf, ng, fail
 
 
