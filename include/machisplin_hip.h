@@ -999,6 +999,98 @@ MHS_API int mhs_proximity_dev(const mhs_grid *g, const mhs_stack *stack, int lay
 MHS_API int mhs_proximity(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int value_layer,
                           double unit, const mhs_proximity_out *out, int out_dtype, mhs_proximity_info *info);
 
+/* --------------------------------------------------------------- flow paths --
+ * Drainage covariates ALONG the flow: height above and distance to the first channel cell that a cell's own water meets (HAND,
+ * SAGA's vertical / horizontal distance to channel network), and the basin a cell drains to.  "proximity" takes the stream cell
+ * that is nearest as the crow flies, which on a ridge is often one of the wrong catchment; this section follows the D8 forest
+ * that "hydrology" makes.  THE RULE (this text is the specification; csrc/flowpath_rule.h holds it as code).
+ *
+ * INPUT.  A grid of nrow x ncol cells; an int8 DIRECTION PLANE `flowdir` with the row stride ld_dir in the encoding of
+ * "hydrology" (0 .. 7 = E, SE, S, SW, W, NW, N, NE; -1 the water leaves; -2 NA); a stack whose layer `layer` defines the targets
+ * and whose layer `value_layer` supplies values (int16, float32 or float64, converted exactly to double; NA = NaN or the
+ * stack's nodata).  A call always treats the WHOLE plane: a path may run anywhere in the raster.
+ *
+ * WELL-FORMED.  next(c) is the neighbour that the direction k = 0 .. 7 of c points at.  It must lie inside the raster and must
+ * not be a -2 cell.  Any other code, or a pointer out of the raster or at a -2 cell, is MHS_ERR_INVALID naming flowdir; such
+ * cells are counted on the device by the first kernel, and the call is memory-safe for ANY byte content of the plane.
+ *
+ * TARGETS.  A valid cell (not -2) is a target when the value of layer `layer` satisfies `where`: one of the eight MHS_PROX_*
+ * predicates of "proximity", with their NA semantics.  where = MHS_FLOWPATH_OUTLET: there are no targets.  A ROOT is a cell with
+ * the direction -1.
+ *
+ * PATH.  The path of a valid cell c is c, next(c), next(next(c)), ... up to its root.  t(c) is the first target on it, c itself
+ * included.  If there is none and MHS_FLOWPATH_ROOT_IS_TARGET is set in `flags`, or where is MHS_FLOWPATH_OUTLET, t(c) is the
+ * root.  Otherwise c is UNREACHED.
+ *
+ * PRODUCTS, any subset, not none; n_ew, n_ns, n_d = the exact counts of E-W, N-S and diagonal steps from c to t(c):
+ *   index   int32   the cell number row * ncol + col of t(c); -1 where c is unreached or NA.  With MHS_FLOWPATH_OUTLET these
+ *                   are catchment labels: every cell of a tree carries its root's number
+ *   steps   int32   n_ew + n_ns + n_d; -1 likewise
+ *   dist            ((double)n_ew * dx + (double)n_ns * dy) + (double)n_d * g with g = sqrt(dx * dx + dy * dy), every operation
+ *                   rounded once
+ *   value           layer value_layer at t(c), NaN if that cell is NA
+ *   drop            value(c) - value(t(c)), one subtraction; NaN if either is NA
+ * The float products are NaN where c is unreached or NA; they are written as out_dtype MHS_F64, or MHS_F32 = the float64 value
+ * converted once.  Integers, + - *, one sqrt and comparisons: every plane equals a restatement in any IEEE double arithmetic bit
+ * for bit.
+ *
+ * UNITS.  dx, dy: the ground width and height of a cell, finite and > 0; looked at only when dist is asked for.  OUT OF SCOPE:
+ * a width per row (lon/lat grids) for dist; Strahler order; the longest upstream length; multiple-flow-direction paths.
+ *
+ * LIMITS, checked with every other argument before the first device call (MHS_ERR_INVALID, the message names the argument):
+ * nrow * ncol <= INT32_MAX (index and steps are int32), the layers in range, out not all NULL, ld >= ncol, ld_dir >= ncol, no
+ * unknown bit in flags.
+ *
+ * THE ALGORITHM is pointer doubling (csrc/flowpath.hip).  A cell's record is a pointer and the three step counts to it; roots,
+ * targets and NA cells point at themselves.  (1) seed: validate, evaluate the predicate, write the records.  (2) local: a
+ * workgroup holds a tile of 32 x 64 records in LDS and doubles inside the tile until every cell of it points at a stop cell or
+ * out of the tile, at most ceil(log2 2048) + 1 = 12 rounds; MHS_FLOWPATH_NO_LOCAL skips this phase (a diagnostic: the results
+ * are the same).  (3) global rounds: every cell whose pointer is no stop cell takes its pointer's pointer and adds its pointer's
+ * counts.  A round reads one buffer of records and writes the other, so no launch reads a record that the same launch writes.
+ * A path of L steps resolves in ceil(log2 L) rounds.  The host reads the number of cells that moved after EVERY round -- one
+ * stream synchronisation per round, as mhs_hydro_dev has one per pass -- and stops at zero.  (4) products: one pass writes
+ * every requested plane.
+ * CYCLES.  nrow * ncol <= INT32_MAX, so a path of a well-formed forest has fewer than 2^31 steps: 31 rounds resolve it and the
+ * 32nd launch moves nothing.  This is a proof, not a policy cap: a plane on which cells still move in the 32nd launch has a
+ * cycle, MHS_ERR_INVALID naming flowdir.  A cycle of 2^k cells would fold into self-pointers instead, which look like stop
+ * cells; so a cell that is about to take ITSELF as its pointer's pointer -- no forest has such a cell -- stays as it is and is
+ * counted, and the call ends with the same error after that round.  The outputs are then unspecified and the library stays
+ * usable.
+ * SCRATCH: two buffers of records in one block of stream-ordered device memory for the length of the call -- 32 bytes per cell
+ * (2 x (pointer 4 + counts 12)) when steps or dist is asked for, 8 bytes per cell (2 x pointer 4) otherwise, since index, value
+ * and drop need no counts -- plus 256-byte alignments and the counters; MHS_ERR_ALLOC if there is none. */
+enum { MHS_FLOWPATH_OUTLET = 8 };                                       /* `where`, after the eight MHS_PROX_* */
+enum { MHS_FLOWPATH_ROOT_IS_TARGET = 1, MHS_FLOWPATH_NO_LOCAL = 2 };    /* `flags` */
+typedef struct mhs_flowpath_out {   /* the planes to make; any may be NULL, not all */
+    int32_t *index;
+    int32_t *steps;
+    void *dist, *value, *drop;      /* out_dtype */
+} mhs_flowpath_out;
+typedef struct mhs_flowpath_info {
+    int64_t n_valid;         /* cells that are not -2 */
+    int64_t n_targets;       /* valid cells that satisfy `where`; 0 with MHS_FLOWPATH_OUTLET */
+    int64_t n_roots;         /* cells with the direction -1 */
+    int64_t n_unreached;     /* valid cells without a t(c) */
+    int64_t max_steps;       /* the largest steps of the plane; -1 when no cell is reached, or when neither steps nor dist is
+                              * asked for (the counts are then not carried) */
+    int rounds;              /* global doubling rounds in which a cell moved; the launch that finds nothing to move is not counted */
+    int64_t scratch_bytes;   /* the call's block of device scratch */
+} mhs_flowpath_info;
+/* DEVICE planes: flowdir (nrow x ld_dir) and stack->data on the device and covering the whole grid; every plane of `out` is
+ * nrow x ld row-major on the device.  value_layer is looked at only when out->value or out->drop is set.  Like mhs_hydro_dev
+ * this entry point does not only enqueue: the host decides after each doubling round whether another is needed, so it
+ * SYNCHRONISES `stream` once per round (and cannot be captured into a graph).  info may be NULL. */
+MHS_API int mhs_flowpath_dev(const mhs_grid *g, const int8_t *flowdir, int64_t ld_dir, const mhs_stack *stack, int layer, int where,
+                             double threshold, int value_layer, int flags, double dx, double dy, const mhs_flowpath_out *out,
+                             int out_dtype, int64_t ld, void *stream, mhs_flowpath_info *info);
+/* same, HOST planes: flowdir, stack->data and the planes of `out` (nrow x ncol dense) on the host -- what the R shim hands over.
+ * The whole direction plane and the layers the call reads go up in one piece and the requested planes come down; no row bands,
+ * because the path of a cell may run through any row of the raster, so a band would need the whole plane anyway.  Blocks until
+ * done. */
+MHS_API int mhs_flowpath(const mhs_grid *g, const int8_t *flowdir, int64_t ld_dir, const mhs_stack *stack, int layer, int where,
+                         double threshold, int value_layer, int flags, double dx, double dy, const mhs_flowpath_out *out,
+                         int out_dtype, mhs_flowpath_info *info);
+
 /* ------------------------------------------------------- tile bookkeeping --
  * Integer windows are half-open [r0,r1) x [c0,c1) in the full grid, rows from the north;
  * a window array holds 4 int64 per tile: r0, r1, c0, c1.  Tiles are numbered row-major

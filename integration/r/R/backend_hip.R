@@ -332,6 +332,47 @@ mhs_proximity <- function(x, where = "na", threshold = NA_real_, v = "dist", lay
   r
 }
 
+# ---- flow-path covariates: HAND, SAGA's vertical / horizontal distance to channel network, catchment labels ------------------
+# flowdir: the one-layer SpatRaster of D8 directions that the hydrology call makes (0 .. 7 = E, SE, S, SW, W, NW, N, NE, -1 the
+# water leaves, NA).  x: a SpatRaster on the same grid whose layer `layer` defines the targets -- `where` as for mhs_proximity,
+# or "outlet": no targets, every path runs to its root -- and whose layer `value.layer` supplies values.  v: any of "index" (the
+# cell number of the first target on the cell's own flow path; with "outlet" a catchment label), "steps", "dist" (the path's
+# length; dx, dy default to the cell size), "value" (layer value.layer there) and "drop" (that layer at the cell minus there:
+# the height above the drainage when it is the DEM).  root.is.target: a path that meets no target ends at its root; otherwise
+# its cells are NA.  Section "flow paths" of machisplin_hip.h states the rule; lon/lat rasters are out of scope for "dist".
+.mhs_flowpath_where <- c(.mhs_proximity_where, "outlet")
+.mhs_flowpath_products <- c("index", "steps", "dist", "value", "drop")
+mhs_flowpath <- function(flowdir, x, where = "outlet", threshold = NA_real_, v = "index", layer = 1L, value.layer = NA_integer_,
+                         root.is.target = TRUE, dx = NULL, dy = NULL) {
+  w <- match(where, .mhs_flowpath_where)
+  if (length(where) != 1L || is.na(w)) stop("mhs_flowpath: where must be one of ", paste(.mhs_flowpath_where, collapse = ", "))
+  if (w > 2L && w < 9L && is.na(threshold)) stop("mhs_flowpath: where = \"", where, "\" needs a threshold")
+  bad <- setdiff(v, .mhs_flowpath_products)
+  if (length(bad) || !length(v)) stop("mhs_flowpath: v must name some of ", paste(.mhs_flowpath_products, collapse = ", "))
+  if (any(c("value", "drop") %in% v) && is.na(value.layer)) stop("mhs_flowpath: the value and drop products need value.layer")
+  if ("dist" %in% v && terra::is.lonlat(x, perhaps = TRUE, warn = FALSE) && (is.null(dx) || is.null(dy)))
+    stop("mhs_flowpath: dist on a lon/lat raster is out of scope; project x or give dx and dy")
+  res <- terra::res(x)
+  if (is.null(dx)) dx <- res[1]
+  if (is.null(dy)) dy <- res[2]
+  v <- unique(v)
+  pv <- match(v, .mhs_flowpath_products)
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  dirs <- as.integer(terra::values(flowdir[[1]]))
+  out <- .Call("mhsr_flowpath", .mhs_geom(x), dirs, vals, NA_real_,
+               c(layer - 1, w - 1, if (w > 2L && w < 9L) threshold else 0, if (is.na(value.layer)) -1 else value.layer - 1,
+                 if (root.is.target) 1 else 0, dx, dy),
+               as.integer(sum(2^(pv - 1))))
+  layers <- lapply(seq_along(v), function(j) {
+    r <- terra::setValues(terra::rast(x[[1]]), out[[pv[j]]])
+    names(r) <- v[j]
+    r
+  })
+  r <- do.call(c, layers)
+  attr(r, "info") <- stats::setNames(out[[6]], c("n_valid", "n_targets", "n_roots", "n_unreached", "max_steps", "rounds"))
+  r
+}
+
 # ---- learner fits on the device (SURVEY.md 8f rank 4); every one keeps the CRAN call as its fallback -----------------
 # kernlab::ksvm(mod.form, data = dat) (V73:251, V73:560).  sigma: kernlab draws it with sigest() from a random half
 # of the rows -- do the same here so that the two backends see the same kernel width.

@@ -490,6 +490,59 @@ SEXP mhsr_proximity(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP product
     return out;
 }
 
+/* Along the D8 flow paths (machisplin_hip.h "flow paths"): height above and distance to the first target cell a cell's own water
+ * meets, catchment labels.  flowdir: the integer vector mhsr_hydro returns (0 .. 7, -1 the water leaves, NA_integer_ at NA
+ * cells), one per cell; planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, flags, dx, dy) with
+ * layer and value_layer 0-based (value_layer is read only for value and drop), where 0 .. 7 as for mhsr_proximity or 8 = outlet,
+ * flags 1 = the root counts where a path meets no target, 2 = without the local phase; products: bit mask (1 index, 2 steps,
+ * 4 dist, 8 value, 16 drop).  Returns list(index, steps, dist, value, drop, info) in terra cell order, NULL where a plane was
+ * not asked for: index the terra cell NUMBER (1-based) of the path's end and steps integer vectors, NA_integer_ where the cell
+ * is unreached or NA, the others numeric (NaN there); info = c(n_valid, n_targets, n_roots, n_unreached, max_steps, rounds).
+ * Runs on the HOST entry point: the whole plane goes up, there are no row bands. */
+SEXP mhsr_flowpath(SEXP geom, SEXP flowdir, SEXP planes, SEXP nodata, SEXP opts, SEXP products) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_flowpath");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 31) Rf_error("mhsr_flowpath: products must be a bit mask of 1 index, 2 steps, 4 dist, 8 value, 16 drop");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 7) Rf_error("mhsr_flowpath: opts must be c(layer, where, threshold, value_layer, flags, dx, dy)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_flowpath: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 8.0)) Rf_error("mhsr_flowpath: where must be 0 .. 8");
+    if (!(o[4] >= 0.0 && o[4] <= 3.0)) Rf_error("mhsr_flowpath: flags must be 0 .. 3");
+    int value_layer = (o[3] >= 0.0 && o[3] <= 2147483647.0) ? (int)o[3] : -1;
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_flowpath: bad grid dimension");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    if (TYPEOF(flowdir) != INTSXP || Rf_xlength(flowdir) != n) Rf_error("mhsr_flowpath: flowdir must be an integer vector of one code per cell");
+    int8_t *dirs = (int8_t *)R_alloc((size_t)n, sizeof(int8_t));
+    for (R_xlen_t k = 0; k < n; ++k) {
+        int d = INTEGER(flowdir)[k];
+        dirs[k] = d == NA_INTEGER ? -2 : (d < -1 || d > 7) ? 127 : (int8_t)d;      /* 127: a code the library refuses (-2 is NA's alone) */
+    }
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 6));
+    SEXP plane[5] = { R_NilValue, R_NilValue, R_NilValue, R_NilValue, R_NilValue };
+    int n_protect = 1;
+    for (int k = 0; k < 5; ++k)
+        if (mask & (1 << k)) { plane[k] = PROTECT(Rf_allocVector(k < 2 ? INTSXP : REALSXP, n)); ++n_protect; }
+    mhs_flowpath_out po = { (mask & 1) ? (int32_t *)INTEGER(plane[0]) : NULL, (mask & 2) ? (int32_t *)INTEGER(plane[1]) : NULL,
+                            (mask & 4) ? REAL(plane[2]) : NULL, (mask & 8) ? REAL(plane[3]) : NULL, (mask & 16) ? REAL(plane[4]) : NULL };
+    mhs_flowpath_info info = { 0 };
+    int rc = mhs_flowpath(&g, dirs, g.ncol, &st, (int)o[0], (int)o[1], o[2], value_layer, (int)o[4], o[5], o[6], &po, MHS_F64, &info);
+    if (rc == MHS_OK) {
+        if (mask & 1)
+            for (R_xlen_t k = 0; k < n; ++k) INTEGER(plane[0])[k] = INTEGER(plane[0])[k] < 0 ? NA_INTEGER : INTEGER(plane[0])[k] + 1;
+        if (mask & 2)
+            for (R_xlen_t k = 0; k < n; ++k) if (INTEGER(plane[1])[k] < 0) INTEGER(plane[1])[k] = NA_INTEGER;
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 6)); ++n_protect;
+        REAL(inf)[0] = (double)info.n_valid; REAL(inf)[1] = (double)info.n_targets; REAL(inf)[2] = (double)info.n_roots;
+        REAL(inf)[3] = (double)info.n_unreached; REAL(inf)[4] = (double)info.max_steps; REAL(inf)[5] = (double)info.rounds;
+        for (int k = 0; k < 5; ++k) SET_VECTOR_ELT(out, k, plane[k]);
+        SET_VECTOR_ELT(out, 5, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* predict(model, data.frame) at the stations (V73:477, 501, 525, 586, 608) */
 SEXP mhsr_predict_points(SEXP model, SEXP X) {
     SEXP out = PROTECT(Rf_allocVector(REALSXP, Rf_nrows(X)));

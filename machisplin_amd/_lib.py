@@ -104,6 +104,17 @@ class ProximityInfo(C.Structure):
     _fields_ = [("n_features", C.c_int64), ("max_d2", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class FlowpathOut(C.Structure):
+    """struct mhs_flowpath_out"""
+    _fields_ = [("index", C.c_void_p), ("steps", C.c_void_p), ("dist", C.c_void_p), ("value", C.c_void_p), ("drop", C.c_void_p)]
+
+
+class FlowpathInfo(C.Structure):
+    """struct mhs_flowpath_info"""
+    _fields_ = [("n_valid", C.c_int64), ("n_targets", C.c_int64), ("n_roots", C.c_int64), ("n_unreached", C.c_int64),
+                ("max_steps", C.c_int64), ("rounds", C.c_int), ("scratch_bytes", C.c_int64)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -223,6 +234,10 @@ SIGNATURES = {
                                     C.POINTER(ProximityOut), C.c_int, _i64, _vp, C.POINTER(ProximityInfo)]),
     "mhs_proximity": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
                                 C.POINTER(ProximityOut), C.c_int, C.POINTER(ProximityInfo)]),
+    "mhs_flowpath_dev": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
+                                   C.c_double, C.POINTER(FlowpathOut), C.c_int, _i64, _vp, C.POINTER(FlowpathInfo)]),
+    "mhs_flowpath": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
+                               C.c_double, C.POINTER(FlowpathOut), C.c_int, C.POINTER(FlowpathInfo)]),
     "mhs_crop_window":(C.c_int, [C.POINTER(Grid), _vp, _vp]),
     "mhs_step3_tile_windows": (C.c_int, [C.POINTER(Grid), _i64, C.c_double, C.c_double, C.POINTER(_i64),
                                          C.POINTER(_i64), _vp, _vp, _i64]),

@@ -29,6 +29,8 @@ HYDRO_MFD = ("filled", "flowacc", "twi")                            # the planes
 HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True)}      # the same, made by hydro_mfd at its defaults
 DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covariates(): spec name -> the predicate of proximity
 STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
+FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
+FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
 SOLAR = ("svf", "direct", "sun_hours", "horizon")                   # the products of mhs_solar, in its order; horizon is 16 planes
 # the sixteen ray directions of section "solar", clockwise from north: (rows south, columns east)
 SOLAR_DIRECTIONS = ((-1, 0), (-2, 1), (-1, 1), (-1, 2), (0, 1), (1, 2), (1, 1), (2, 1),
@@ -376,6 +378,28 @@ def _stream_layers(dem_stack, demf, flowacc, thresholds, spec):
     return out
 
 
+def _flow_layers(dem_stack, demf, flowdir, flowacc, thresholds, spec, layer):
+    """the ("hand", A), ("flowdist_stream", A) and "flowdist_outlet" layers of :func:`covariates`: one flowpath call per threshold
+    A on the stack :func:`_stream_layers` makes (the D8 flow accumulation and the DEM, float64, NA as NaN) follows every cell's
+    own flow path to the first stream cell -- or to the root, where it meets none -- and one more call to the root; keyed
+    (name, A) and by the name"""
+    import torch
+    from . import flowpath as _flow
+    out = {}
+    if thresholds:
+        pair = RasterStack(dem_stack.geom, torch.stack([flowacc.to(torch.float64), demf.to(torch.float64)]), float("nan"))
+    for a in thresholds:
+        want = tuple(dict.fromkeys(FLOW_SPEC[e[0]] for e in spec if len(e) == 2 and e[0] in FLOW_SPEC and float(e[1]) == a))
+        got, _ = _flow.flowpath(flowdir, pair, 0, "ge", a, want, value_layer=1, root_is_target=True)
+        if "drop" in got:
+            out[("hand", a)] = got["drop"].to(torch.float32)
+        if "dist" in got:
+            out[("flowdist_stream", a)] = got["dist"].to(torch.float32)
+    if any(e[0] == FLOW_OUTLET for e in spec):
+        out[FLOW_OUTLET] = _flow.flowpath(flowdir, dem_stack, layer, "outlet", None, "dist")[0].to(torch.float32)
+    return out
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
@@ -395,6 +419,13 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                   :func:`hydro` call that makes ``twi`` / ``log_flowacc`` serves these too)
       ("above_stream", A)                         the DEM minus the DEM at that nearest stream cell, in elevation units:
                                                   Euclidean height above the nearest drainage
+      ("hand", A)                                 the DEM minus the DEM at the first cell with D8 ``flowacc`` >= A on the cell's
+                                                  OWN flow path (:func:`flowpath.flowpath`; the path's root where it meets
+                                                  none): height above the nearest drainage along the flow
+      ("flowdist_stream", A)                      the length of that path, in the geometry's cell width and height
+      "flowdist_outlet"                           the length of the flow path to its root, where the water leaves the raster
+                                                  (these three share the ``hydro`` call too, need metric cells and raise
+                                                  ValueError for ``lonlat=True``; one flowpath call per distinct A)
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -408,22 +439,34 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     names = ["dem"]
     by_name = {}
     for e in spec:
+        if e[0] in FLOW_SPEC or e[0] == FLOW_OUTLET:
+            if len(e) != (2 if e[0] in FLOW_SPEC else 1):
+                raise ValueError(f"{e[0]!r} takes " + ("one argument, the flow accumulation from which a cell is a stream" if e[0] in FLOW_SPEC
+                                                       else "no argument"))
+            if lonlat:
+                raise ValueError(f"{e[0]!r} follows flow paths in metric cells: lonlat=True is out of scope (resample.resample onto a metric grid)")
         if e[0] in STREAM_SPEC and len(e) != 2:
             raise ValueError(f"{e[0]!r} takes one argument, the flow accumulation from which a cell is a stream")
         if e[0] in DIST_SPEC and len(e) != (1 if e[0] == "dist_na" else 2):
             raise ValueError(f"{e[0]!r} takes {'no argument' if e[0] == 'dist_na' else 'one threshold'}")
     stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
-    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC]
+    flow_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in FLOW_SPEC))
+    flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec)
+    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC and e[0] != FLOW_OUTLET]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
     for table, call in ((HYDRO_SPEC, hydro), (HYDRO_MFD_SPEC, hydro_mfd)):
         hv = [e[0] for e in spec if len(e) == 1 and e[0] in table]
-        extra = ("flowacc",) if stream_a and call is hydro else ()          # the streams are cut from the D8 accumulation
+        extra = ("flowacc",) if (stream_a or flow_a) and call is hydro else ()          # the streams are cut from the D8 accumulation
+        if flows and call is hydro:
+            extra += ("flowdir",)                                                       # ... and the paths follow the D8 directions
         if hv or extra:                           # one hydrology call of a route makes all of its layers
             hp, _ = call(dem_stack, layer, tuple(dict.fromkeys([table[n][0] for n in hv] + list(extra))), lonlat=lonlat, z_factor=z_factor)
-            if extra:
+            if stream_a and call is hydro:
                 by_name.update(_stream_layers(dem_stack, demf, hp["flowacc"], stream_a, spec))
+            if flows and call is hydro:
+                by_name.update(_flow_layers(dem_stack, demf, hp["flowdir"], hp.get("flowacc"), flow_a, spec, layer))
             for n in hv:
                 product, log = table[n]
                 by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
@@ -436,7 +479,7 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     for e in dict.fromkeys(e for e in spec if e[0] in DIST_SPEC):
         by_name[e] = _prox.proximity(dem_stack, layer, DIST_SPEC[e[0]], float(e[1]) if len(e) > 1 else None, "dist", out_dtype=torch.float32)[0]
     for k, e in enumerate(spec):
-        if e[0] in DIST_SPEC or e[0] in STREAM_SPEC:
+        if e[0] in DIST_SPEC or e[0] in STREAM_SPEC or e[0] in FLOW_SPEC:
             planes[1 + k] = by_name[e if e[0] in DIST_SPEC else (e[0], float(e[1]))]
             names.append(e[0] + (f"{float(e[1]):g}" if len(e) > 1 else ""))
         elif len(e) > 1 and e[0] in sun_names:
