@@ -192,6 +192,41 @@ __device__ __forceinline__ double table_exp_neg_acc(double u, const double *tab,
     return fma(sj, q, acc);
 }
 
+// The same exponential for svr_rt_kernel with TWO integer instructions instead of three; sj, and with it the result, is
+// the same double.  k << 8 = ((e + 1023) << 20) + (j << 8), so an entry whose high word is stored as (mantissa's high 20
+// bits) - (j << 8), mod 2^32, takes the finished exponent field by ONE shift-add (k < 2^23: the shift loses nothing, no mask).
+// The byte offset is one 16-bit shift, (k << 3) & 0xffff = 8 (k mod 8192), which carries bit 12 of k, the exponent's
+// lowest bit, along: the table has 8192 entries, the second half a copy of the first (64 KB; rt_exp_table_stage).
+// The offset is only right where the 16-bit VALU forms write ZEROS to the destination's upper half.  The GFX9 encoding
+// does (gfx90a, gfx942, gfx950; on gfx950 tests/test_ksvm_rowtile_exp_gpu.py shows it); GFX10 and later keep the upper
+// half, and this function must not be compiled for them as it stands.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "table_exp_neg_acc_rt relies on v_lshlrev_b16 zeroing bits 16..31 of its destination (GFX9 encoding only)"
+#endif
+constexpr int EXP_TAB2_N = 2 * EXP_TAB_N;
+__device__ __forceinline__ void rt_exp_table_stage(double *tab2, const double *__restrict__ gtab, int tid, int nthreads) {
+    for (int i = tid; i < EXP_TAB2_N; i += nthreads) {
+        const int j = i & (EXP_TAB_N - 1);
+        const double e = gtab[j];
+        tab2[i] = __hiloint2double((int)(((unsigned)__double2hiint(e) & 0x000fffffu) - ((unsigned)j << 8)), __double2loint(e));
+    }
+}
+__device__ __forceinline__ double table_exp_neg_acc_rt(double u, const double *tab2, double acc) {   // acc + exp(-700 u)
+    const double MAGIC = 0x1.8p52 + 1023.0 * EXP_TAB_N, NK = -EXP_RANGE * EXP_SCALE;
+    const double t = fma(u, NK, MAGIC);
+    const double kd = t - MAGIC;
+    const unsigned k = (unsigned)__double2loint(t);
+    unsigned off;
+    asm("v_lshlrev_b16 %0, 3, %1" : "=v"(off) : "v"(k));
+    const double r = fma(u, NK, -kd);
+    const double mj = *(const double *)((const char *)tab2 + off);
+    const double sj = __hiloint2double((int)((k << 8) + (unsigned)__double2hiint(mj)), __double2loint(mj));
+    const double C1 = 1.0 / EXP_SCALE, C2 = 0.5 / (EXP_SCALE * EXP_SCALE);
+    double q = fma(r, C2, C1);
+    q = fma(q, r, 1.0);
+    return fma(sj, q, acc);
+}
+
 // per support vector: [b_0 .. b_{P-1}, a], b_k = -2 sigma sv_k / 700, a = (sigma |sv|^2 - ln(|alpha| / amax)) / 700:
 // u = a + sigma |x|^2 / 700 + b.x = (sigma |x - sv|^2 - ln(|alpha| / amax)) / 700 >= 0 and exp(-700 u) =
 // |alpha| / amax K(x, sv).  With the coefficient inside the exponent the term is accumulated by the fma that
@@ -265,26 +300,34 @@ __global__ __launch_bounds__(256) void svr_kernel(const double *__restrict__ svp
 // ROW-TILE form of the ksvm kernel (round 3): a wave = 64 R consecutive cells of ONE raster row.  LAT is the last
 // predictor of every model (V73:127-138) and the same for all of the wave's cells, so its term b_LAT x_LAT + a of the
 // exponent is formed ONCE per wave and support vector -- 128 vectors at a time, two per lane, parked in a wave-private
-// 1 KB of LDS and read back as a broadcast -- instead of once per cell: 14 VALU instructions per (cell, SV) instead of
-// 15.  A wave that does NOT fold its cells' q (below) adds exactly what svr_kernel adds, bit for bit; a folding wave's plane
-// agrees with svr_kernel's to ~2e-13 of the prediction (tests: test_ksvm_row_tile_kernel_*).
-template <int P, int R>
-__global__ __launch_bounds__(256) void svr_rt_kernel(const double *__restrict__ svp, int nsv, int stride,
-                                                     int npos, const double *__restrict__ xcs,
-                                                     const double *__restrict__ gtab, double sigma, double b,
-                                                     double amax, double y_center, double y_scale, StackDev s, PredGeom g,
-                                                     int tiles_per_row, double weight, int accumulate, double *__restrict__ out) {
+// 1 KB of LDS and read back as a broadcast -- instead of once per cell.  A wave that does NOT fold its cells' q (below)
+// adds exactly what svr_kernel adds, bit for bit; a folding wave's plane agrees with svr_kernel's to ~2e-13 of the
+// prediction (tests: test_ksvm_row_tile_kernel_*).
+// Vector instructions per (cell, SV) of the loop at P = 5, step by step: 15 lane per cell (svr_kernel), 14 with the LAT term
+// per wave, 13 with q folded (below; 14 where the wave does not fold), and with TAB2 12 (13 where it does not fold).
+// TAB2 chooses the exponential: table_exp_neg_acc_rt and its 64 KB table (the same bits as svr_kernel's form:
+// tests/test_ksvm_rowtile_exp_gpu.py), or table_exp_neg_acc and the 32 KB table.  NW is the block's waves; launch_svr sets
+// both (svr_rt_tab2, svr_rt_waves).  A wave has its own tile and its own slice of aw; the only block-wide barrier is the
+// one behind the table's staging.
+template <int P, int R, int NW, bool TAB2>
+__global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restrict__ svp, int nsv, int stride,
+                                                         int npos, const double *__restrict__ xcs,
+                                                         const double *__restrict__ gtab, double sigma, double b,
+                                                         double amax, double y_center, double y_scale, StackDev s, PredGeom g,
+                                                         int tiles_per_row, double weight, int accumulate, double *__restrict__ out) {
     constexpr int CH = 128;
-    __shared__ double etab[EXP_TAB_N];
-    __shared__ double aw[4][CH];
-    for (int i = threadIdx.x; i < EXP_TAB_N; i += 256) {   // mantissa bits of 2^(j/4096)
-        const double e = gtab[i];
-        etab[i] = __hiloint2double(__double2hiint(e) & 0x000fffff, __double2loint(e));
-    }
+    __shared__ double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
+    __shared__ double aw[NW][CH];
+    if constexpr (TAB2) rt_exp_table_stage(etab, gtab, threadIdx.x, 64 * NW);
+    else
+        for (int i = threadIdx.x; i < EXP_TAB_N; i += 64 * NW) {   // mantissa bits of 2^(j/4096)
+            const double e = gtab[i];
+            etab[i] = __hiloint2double(__double2hiint(e) & 0x000fffff, __double2loint(e));
+        }
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t ntiles = (int64_t)g.nr * tiles_per_row;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t tile = (int64_t)blockIdx.x * NW + wave;
     if (tile >= ntiles) return;
     const int row = (int)(tile / tiles_per_row), tcol = (int)(tile - (int64_t)row * tiles_per_row) * (64 * R);
     double x[R][P], q[R], acc[R], accn[R];
@@ -309,7 +352,7 @@ __global__ __launch_bounds__(256) void svr_rt_kernel(const double *__restrict__ 
     // The cell's own term q = sigma |x|^2 / 700 of the exponent is the one addition per (cell, SV) that is left beside the
     // P - 1 fmas.  With S the LARGEST q of the wave's cells, u + (S - q_c) is still >= 0 and is formed with S folded into the
     // per-wave term above; the cell's sum then comes out scaled by exp(-700 (S - q_c)), which ONE exact exponential per cell
-    // undoes at the end -- 13 VALU instructions per pair instead of 14.  Neighbouring cells: S - q_c is a few hundredths.
+    // undoes at the end -- one vector instruction per pair fewer.  Neighbouring cells: S - q_c is a few hundredths.
     // Where the wave's q spread more than 0.5 (terms would be flushed that the cell's scale brings back) the wave keeps
     // the per-pair addition.
     double qhi = -1.0, qlo = 2e300;
@@ -331,7 +374,7 @@ __global__ __launch_bounds__(256) void svr_rt_kernel(const double *__restrict__ 
 #pragma unroll
                 for (int j = 0; j < P - 1; ++j) arg = fma(sp[j], x[c][j], arg);
                 arg = fmin(fmax(arg, 0.0), 1.0);
-                a[c] = table_exp_neg_acc(arg, etab, a[c]);
+                a[c] = TAB2 ? table_exp_neg_acc_rt(arg, etab, a[c]) : table_exp_neg_acc(arg, etab, a[c]);
             }
         };
         for (int vb = v0; vb < v1; vb += CH) {
@@ -1198,6 +1241,13 @@ static void launch_nnet(const mhs_model *m, const StackDev &s, const PredGeom &g
                         double *out, hipStream_t st, unsigned blocks) {
     hipLaunchKernelGGL((nnet_kernel<P>), dim3(blocks), dim3(256), 0, st, m->dpar, m->n0, m->s0, m->s1, s, g, w, acc, out);
 }
+// The form of svr_rt_kernel by P.  P <= 5 (100 / 112 / 124 VGPRs at P = 3 / 4 / 5 in the built object: four waves per
+// SIMD): table_exp_neg_acc_rt with its 64 KB table in blocks of 8 waves, two per CU; one block of 16 instead is 23 % slower
+// at P = 5.  Larger P keep table_exp_neg_acc, the 32 KB table and blocks of 4: at three waves per SIMD the 64 KB table
+// leaves room for ONE block of 12 waves per CU, and P = 7 lost 7 % of cfg5's step with it (profiles/ksvm_exp_insertion.txt).
+// P = 6 and P = 8 .. 12 were not measured in either form.
+constexpr bool svr_rt_tab2(int P) { return P <= 5; }
+constexpr int svr_rt_waves(int P) { return svr_rt_tab2(P) ? 8 : 4; }
 template <int P>
 static void launch_svr(const mhs_model *m, const StackDev &s, const PredGeom &g, double w, int acc,
                        double *out, hipStream_t st, int64_t total) {
@@ -1206,7 +1256,8 @@ static void launch_svr(const mhs_model *m, const StackDev &s, const PredGeom &g,
     const int tpr = (g.nc + 64 * R - 1) / (64 * R);
     if (!s.all_from_planes && P == s.C + 2 && P >= 3 && !getenv("MHS_SVR_NO_ROWTILE") && (double)g.nc >= 0.93 * (double)tpr * (64 * R)) {
         const int64_t ntiles = (int64_t)g.nr * tpr;
-        hipLaunchKernelGGL((svr_rt_kernel<P, R>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st,
+        constexpr int NW = svr_rt_waves(P);
+        hipLaunchKernelGGL((svr_rt_kernel<P, R, NW, svr_rt_tab2(P)>), dim3((unsigned)((ntiles + NW - 1) / NW)), dim3(64 * NW), 0, st,
                            m->dpar, m->n0, m->n1, m->n2, m->dpar + (size_t)m->n0 * m->n1, ctx().exp_tab, m->s1, m->s0, m->s4,
                            m->s2, m->s3, s, g, tpr, w, acc, out);
         return;
