@@ -877,7 +877,7 @@ MHS_API int mhs_hydro_mfd(const mhs_grid *g, const mhs_stack *dem, int layer, co
 /* ----------------------------------------------------------------- resample --
  * Rasters onto one grid.  The reference's README asks for rasters of one resolution, projection and extent and sends its
  * users to terra::crop and terra::extract for the rest; this section brings a stack on grid S onto an axis-aligned grid T in
- * the SAME coordinate system (resolution, origin and extent may differ; no reprojection) and interpolates it at points.
+ * the SAME coordinate system (resolution, origin and extent may differ; another coordinate system is section "warp") and interpolates it at points.
  * csrc/resample_rule.h holds the rules as they stand here, every operation in this order and rounded once (the library is
  * built with -ffp-contract=off; there is no transcendental), so every method equals a restatement in any IEEE double
  * arithmetic bit for bit.
@@ -932,6 +932,54 @@ MHS_API int mhs_extract_points_dev(const mhs_grid *src_grid, const mhs_stack *sr
                                    double *out_dev, void *stream);
 MHS_API int mhs_extract_points(const mhs_grid *src_grid, const mhs_stack *src_stack, const double *xy, int64_t n, int method,
                                double *out);
+
+/* --------------------------------------------------------------------- warp --
+ * Rasters onto a grid in ANOTHER coordinate system (lon/lat to UTM and back): the third of the reference README's "same
+ * resolution, projection and extent".  The device never sees a projection.  The host evaluates the transform from target to
+ * source coordinates on a CONTROL LATTICE of the target grid T, one node every K cells (machisplin_amd/project.py chooses K so
+ * that the lattice's interpolation error, measured on the host against the exact transform, stays within a tolerance, and
+ * returns the measured error); the device interpolates the lattice at each target cell centre and applies the "resample"
+ * section's rule at that source point.  csrc/warp_rule.h holds the rule as it stands here, every operation in this order
+ * and rounded once (-ffp-contract=off; no transcendental), so the output equals a restatement in any IEEE double arithmetic
+ * bit for bit.
+ *
+ * The lattice covers the WHOLE target grid T: n_node_rows = ceil(T.nrow / K) + 1, n_node_cols = ceil(T.ncol / K) + 1.  Node
+ * (a, b) holds the SOURCE coordinates of the target-grid point X = T.xmin + (b K) T.xres, Y = T.ymax - (a K) T.yres.  Only the
+ * host ever forms X and Y; T's origin and cell size do not enter the device's arithmetic.
+ *
+ * Target cell (r, c):  a = r / K, b = c / K (integer division);  tv = ((double)(r - a K) + 0.5) / (double)K,
+ * tu = ((double)(c - b K) + 0.5) / (double)K  (exact: K is a power of two).  With P00 = node (a, b), P01 = (a, b + 1),
+ * P10 = (a + 1, b), P11 = (a + 1, b + 1) of the array sx:
+ *     sx = (1 - tv) ((1 - tu) P00 + tu P01) + tv ((1 - tu) P10 + tu P11)
+ * evaluated as  u0 = 1 - tu, v0 = 1 - tv;  top = u0 P00 + tu P01;  bot = u0 P10 + tu P11;  sx = v0 top + tv bot,  each product
+ * and each sum rounded once; sy the same from the array sy.  If any of the eight node values is not finite the cell is NA.
+ * Otherwise the cell's value is the "resample" section's value at the point (sx, sy) by MHS_RS_NEAR, MHS_RS_BILINEAR or
+ * MHS_RS_CUBIC: the same NA rules, the same cubic -> bilinear fallback, the same edge rule.  So a warped cell equals
+ * mhs_extract_points at (sx, sy), by definition, and a window of T gives the whole-grid result's cells bit for bit.
+ *
+ * Only the interpolating methods are supported; an aggregate method is refused by name.  A much coarser target is made by
+ * mhs_resample(..., MHS_RS_MEAN) in the source system first, then a warp.
+ *
+ * Every argument is checked before the first device call (MHS_ERR_INVALID, the message names the argument): NULL pointers, a
+ * step that is not a power of two in 1 .. 1024, node counts that differ from the two formulas above (the kernel reads nodes
+ * a + 1 and b + 1: a short lattice never reaches it), a window outside T, a method that is not interpolating, bad dtypes.
+ * The host form has no row bands: the source rows a target row band reads are not a band, so mhs_warp sends the WHOLE stack
+ * up in one piece, as mhs_proximity and mhs_flowpath do.                                                                  */
+typedef struct mhs_warp_lattice {
+    int32_t step;                       /* K: a power of two, 1 .. 1024                                  */
+    int64_t n_node_rows, n_node_cols;   /* must equal ceil(T.nrow / K) + 1 and ceil(T.ncol / K) + 1     */
+    const double *sx, *sy;              /* n_node_rows x n_node_cols, row-major, dense                   */
+} mhs_warp_lattice;
+/* DEVICE planes and DEVICE lattice arrays (the struct itself is on the host): out_dev holds C planes, each (r1-r0) x out_ld
+ * row-major, out_plane_stride elements apart, of out_dtype (MHS_F64, or MHS_F32 = the float64 result rounded once).  All layers
+ * go through one launch.  Only enqueues on `stream`. */
+MHS_API int mhs_warp_dev(const mhs_grid *src_grid, const mhs_stack *src_stack, const mhs_grid *dst_grid, int64_t r0, int64_t r1,
+                         int64_t c0, int64_t c1, const mhs_warp_lattice *lat_dev, int method, void *out_dev, int64_t out_ld,
+                         int64_t out_plane_stride, int out_dtype, void *stream);
+/* same, HOST planes, HOST lattice arrays and HOST output (C planes of (r1-r0) x (c1-c0), dense): the whole stack and the lattice
+ * go up in one piece, the window comes down; the same kernel, so the same bits.  Blocks until done. */
+MHS_API int mhs_warp(const mhs_grid *src_grid, const mhs_stack *src_stack, const mhs_grid *dst_grid, int64_t r0, int64_t r1,
+                     int64_t c0, int64_t c1, const mhs_warp_lattice *lat, int method, void *out_host, int out_dtype);
 
 /* ---------------------------------------------------------------- proximity --
  * Distance-to-feature covariates: distance to the coast, to open water, to the channel network, and what follows from knowing
@@ -1324,6 +1372,16 @@ MHS_API int mhs_tiff_write_f32_host(const char *path, const mhs_grid *g, const f
                                     int compression);
 MHS_API int mhs_tiff_write_f32_dev(const char *path, const mhs_grid *g, const double *plane_dev, int64_t ld,
                                    double nodata, int compression, void *stream);
+/* the same two writers for a grid in the coordinate system EPSG:`epsg`.  4326 writes the bytes of the writers above.
+ * 32601 .. 32660 and 32701 .. 32760 (WGS 84 / UTM north and south) write GTModelType = 1 (projected), GTRasterType = 1 and
+ * ProjectedCSTypeGeoKey (3072) = epsg.  Any other code is refused (MHS_ERR_INVALID). */
+MHS_API int mhs_tiff_write_f32_host_crs(const char *path, const mhs_grid *g, const float *data, double nodata,
+                                        int compression, int epsg);
+MHS_API int mhs_tiff_write_f32_dev_crs(const char *path, const mhs_grid *g, const double *plane_dev, int64_t ld,
+                                       double nodata, int compression, void *stream, int epsg);
+/* the EPSG code of the first image directory's GeoKeyDirectory (tag 34735): ProjectedCSTypeGeoKey (3072) if present, else
+ * GeographicTypeGeoKey (2048); *epsg = 0 when the file has neither.  Needs no GPU. */
+MHS_API int mhs_tiff_epsg_read(const char *path, int32_t *epsg);
 /* ESRI world file (.tfw): six numbers -- xres, rot, rot, -yres, x centre and y centre of the NW cell */
 MHS_API int mhs_tfw_read(const char *path, double *six);
 

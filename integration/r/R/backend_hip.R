@@ -295,6 +295,30 @@ mhs_extract <- function(x, xy, method = "simple") {
   out
 }
 
+# ---- rasters into another coordinate system: the README's "projection" ---------------------------------------------------------
+# x: a SpatRaster; y: the SpatRaster whose grid (in ANOTHER coordinate system) the result takes; lattice: list(step, sx, sy) made by
+# the caller -- step a power of two, sx and sy matrices of (ceil(nrow(y) / step) + 1) x (ceil(ncol(y) / step) + 1) nodes, node
+# [a + 1, b + 1] the coordinates IN x's SYSTEM of y's grid point (xmin(y) + b step xres(y), ymax(y) - a step yres(y)), e.g. by
+# terra::project(cbind(X, Y), from = terra::crs(y), to = terra::crs(x)); NA where the transform has no value.  The library
+# interpolates the lattice at y's cell centres and takes x there by "near", "bilinear" or "cubic" (section "warp" of
+# machisplin_hip.h; the rules are mhs_resample's).  How far the lattice is from the exact transform is the caller's to check: halve
+# step until the midpoints of the lattice cells agree with PROJ to the tolerance wanted (the Python side's project.lattice_from
+# does this; an R restatement is out of scope, as for sun_tables).  A much coarser y: mhs_resample(x, ., "mean") first.
+mhs_warp <- function(x, y, lattice, method = "bilinear") {
+  m <- match(method, c("near", "bilinear", "cubic"))
+  if (length(method) != 1L || is.na(m)) stop("mhs_warp: method must be near, bilinear or cubic (aggregate with mhs_resample in x's system first)")
+  step <- as.integer(lattice$step)
+  nodes <- c(ceiling(terra::nrow(y) / step) + 1, ceiling(terra::ncol(y) / step) + 1)
+  sx <- as.matrix(lattice$sx); sy <- as.matrix(lattice$sy)
+  if (!all(dim(sx) == nodes) || !all(dim(sy) == nodes)) stop("mhs_warp: lattice$sx and lattice$sy must be ", nodes[1], " x ", nodes[2], " matrices")
+  v <- terra::values(x); storage.mode(v) <- "double"
+  out <- .Call("mhsr_warp", .mhs_geom(x), v, NA_real_, .mhs_geom(y), step, as.double(t(sx)), as.double(t(sy)), as.integer(m - 1L))
+  r <- terra::rast(y[[1]], nlyrs = terra::nlyr(x))
+  r <- terra::setValues(r, out)
+  names(r) <- names(x)
+  r
+}
+
 # ---- distance-to-feature covariates: what terra::distance and terra::gridDist are used for ---------------------------------
 # x: a SpatRaster with square cells.  A cell is a feature where layer `layer` is NA (where = "na": the sea of a land-only DEM),
 # not NA ("valid"), or "lt" "le" "gt" "ge" "eq" "ne" `threshold`.  v: any of "d2" (squared distance in cells, exact), "index"

@@ -446,6 +446,28 @@ SEXP mhsr_extract(SEXP geom, SEXP planes, SEXP nodata, SEXP xy, SEXP method) {
     return out;
 }
 
+/* Every layer on the grid geom_dst of ANOTHER coordinate system (machisplin_hip.h "warp") through a control lattice the caller has
+ * made (R has PROJ through terra): step a power of two, sx and sy the source coordinates of the target-grid points
+ * (xmin + b step xres, ymax - a step yres), ROW-MAJOR vectors of (ceil(nrow / step) + 1) x (ceil(ncol / step) + 1) nodes (NA_real_
+ * where the transform has no value: those cells come out NA).  method: 0 near, 1 bilinear, 2 cubic.  An ncell(dst) x C matrix in
+ * terra cell order.  Runs on the HOST entry point mhs_warp: the whole stack goes up in one piece. */
+SEXP mhsr_warp(SEXP geom_src, SEXP planes, SEXP nodata, SEXP geom_dst, SEXP step, SEXP sx, SEXP sy, SEXP method) {
+    mhs_grid gs = grid_from(geom_src), gd = grid_from(geom_dst);
+    mhs_stack st = planes_from(planes, nodata, &gs, "mhsr_warp");
+    if (!(gd.nrow > 0 && gd.ncol > 0 && (double)gd.nrow * (double)gd.ncol <= 2147483647.0)) Rf_error("mhsr_warp: bad target dimension");
+    int K = Rf_asInteger(step);
+    if (K < 1 || K > 1024 || (K & (K - 1)) != 0) Rf_error("mhsr_warp: step must be a power of two in 1 .. 1024");
+    int64_t nr = (gd.nrow + K - 1) / K + 1, nc = (gd.ncol + K - 1) / K + 1;
+    if (!Rf_isReal(sx) || !Rf_isReal(sy) || (int64_t)Rf_xlength(sx) != nr * nc || (int64_t)Rf_xlength(sy) != nr * nc)
+        Rf_error("mhsr_warp: sx and sy must be numeric with (ceil(nrow / step) + 1) x (ceil(ncol / step) + 1) = %d x %d nodes", (int)nr, (int)nc);
+    mhs_warp_lattice lat = { K, nr, nc, REAL(sx), REAL(sy) };
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(gd.nrow * gd.ncol), st.n_layers));
+    int rc = mhs_warp(&gs, &st, &gd, 0, gd.nrow, 0, gd.ncol, &lat, Rf_asInteger(method), REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* Distance to the nearest feature cell (machisplin_hip.h "proximity"): what terra::distance and terra::gridDist are used for.
  * planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, unit) with layer and value_layer 0-based
  * (value_layer is read only for the value product) and where 0 na, 1 valid, 2 lt, 3 le, 4 gt, 5 ge, 6 eq, 7 ne; products: bit

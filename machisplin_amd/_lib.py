@@ -93,6 +93,11 @@ class HydroInfo(C.Structure):
                 ("solves_flat", C.c_int64), ("solves_acc", C.c_int64), ("ms_fill", C.c_double), ("ms_flat", C.c_double), ("ms_acc", C.c_double)]
 
 
+class WarpLattice(C.Structure):
+    """struct mhs_warp_lattice"""
+    _fields_ = [("step", C.c_int32), ("n_node_rows", C.c_int64), ("n_node_cols", C.c_int64), ("sx", C.c_void_p), ("sy", C.c_void_p)]
+
+
 class ProximityOut(C.Structure):
     """struct mhs_proximity_out"""
     _fields_ = [("d2", C.c_void_p), ("index", C.c_void_p), ("dist", C.c_void_p), ("dir_x", C.c_void_p), ("dir_y", C.c_void_p),
@@ -230,6 +235,9 @@ SIGNATURES = {
     "mhs_resample": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.c_int, _vp, C.c_int]),
     "mhs_extract_points_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp, _vp]),
     "mhs_extract_points": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), _vp, _i64, C.c_int, _vp]),
+    "mhs_warp_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.POINTER(WarpLattice), C.c_int, _vp,
+                               _i64, _i64, C.c_int, _vp]),
+    "mhs_warp": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.POINTER(WarpLattice), C.c_int, _vp, C.c_int]),
     "mhs_proximity_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
                                     C.POINTER(ProximityOut), C.c_int, _i64, _vp, C.POINTER(ProximityInfo)]),
     "mhs_proximity": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
@@ -253,6 +261,9 @@ SIGNATURES = {
     "mhs_tiff_read_dev": (C.c_int, [C.c_char_p, C.c_int, _vp, _i64, _vp]),
     "mhs_tiff_write_f32_host": (C.c_int, [C.c_char_p, C.POINTER(Grid), _vp, C.c_double, C.c_int]),
     "mhs_tiff_write_f32_dev": (C.c_int, [C.c_char_p, C.POINTER(Grid), _vp, _i64, C.c_double, C.c_int, _vp]),
+    "mhs_tiff_write_f32_host_crs": (C.c_int, [C.c_char_p, C.POINTER(Grid), _vp, C.c_double, C.c_int, C.c_int]),
+    "mhs_tiff_write_f32_dev_crs": (C.c_int, [C.c_char_p, C.POINTER(Grid), _vp, _i64, C.c_double, C.c_int, _vp, C.c_int]),
+    "mhs_tiff_epsg_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "mhs_tfw_read": (C.c_int, [C.c_char_p, _dp]),
     "mhs_tps_surface": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _vp]),
     "mhs_tps_tiles_dev": (C.c_int, [C.POINTER(Grid), _vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _i64, _vp]),

@@ -8,7 +8,7 @@
 // Reader: classic TIFF and BigTIFF, either byte order, strips or tiles, compression none / LZW /
 // deflate, predictor 1 / 2 / 3, one sample per pixel, 8/16/32/64-bit integer or float samples.
 // Writer: little-endian classic TIFF (BigTIFF above 4 GB), float32 strips, deflate or none, with
-// ModelPixelScale / ModelTiepoint / GeoKeyDirectory (EPSG:4326) / GDAL_NODATA tags.
+// ModelPixelScale / ModelTiepoint / GeoKeyDirectory (EPSG:4326, or WGS 84 / UTM through the _crs entries) / GDAL_NODATA tags.
 #include <zlib.h>
 #include <algorithm>
 #include <atomic>
@@ -33,6 +33,7 @@ struct Ifd {
     double nodata = NAN;
     bool has_scale = false, has_tie = false;
     double scale[3] = {0, 0, 0}, tie[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<double> geokeys;   // GeoKeyDirectory (34735) as written: a header of 4 shorts, then 4 per key
 };
 
 struct TiffFile {
@@ -151,6 +152,9 @@ static int open_tiff(const char *path, TiffFile *t) {
                 case 42113:
                     if (!entry_values(*t, type, count, vpos, nullptr, &a)) return MHS_ERR_INVALID;
                     break;
+                case 34735:                                        // a directory that cannot be read is no coordinate system
+                    if (!entry_values(*t, type, count, vpos, &v, nullptr)) v.clear();
+                    break;
                 default: continue;
             }
             switch (tag) {
@@ -169,6 +173,7 @@ static int open_tiff(const char *path, TiffFile *t) {
                 case 279: case 325: d.counts.assign(v.size(), 0); for (size_t i = 0; i < v.size(); ++i) d.counts[i] = (uint64_t)v[i]; break;
                 case 33550: if (v.size() >= 2) { d.has_scale = true; d.scale[0] = v[0]; d.scale[1] = v[1]; } break;
                 case 33922: if (v.size() >= 6) { d.has_tie = true; for (int i = 0; i < 6; ++i) d.tie[i] = v[i]; } break;
+                case 34735: d.geokeys = v; break;
                 case 42113: d.nodata = atof(a.c_str()); break;
             }
         }
@@ -398,7 +403,9 @@ struct TagW { uint16_t tag, type; uint64_t count; std::vector<uint8_t> data; };
 template <typename T>
 static void put(std::vector<uint8_t> &b, T v) { const uint8_t *p = (const uint8_t *)&v; b.insert(b.end(), p, p + sizeof(T)); }
 
-static int write_f32_tiff(const char *path, const mhs_grid &g, const float *data, double nodata, int compression) {
+static bool epsg_is_utm(int epsg) { return (epsg >= 32601 && epsg <= 32660) || (epsg >= 32701 && epsg <= 32760); }
+
+static int write_f32_tiff(const char *path, const mhs_grid &g, const float *data, double nodata, int compression, int epsg = 4326) {
     const int64_t W = g.ncol, H = g.nrow;
     const int64_t rps = std::max<int64_t>(1, std::min<int64_t>(H, (1 << 20) / std::max<int64_t>(1, W * 4)));  // ~1 MB strips
     const int64_t nstrips = (H + rps - 1) / rps;
@@ -470,7 +477,9 @@ static int write_f32_tiff(const char *path, const mhs_grid &g, const float *data
     add_double(33922, {0.0, 0.0, 0.0, g.xmin, g.ymax, 0.0});
     // GeoKeyDirectory: version 1.1.0, 3 keys: GTModelType = 2 (geographic), GTRasterType = 1 (PixelIsArea),
     // GeographicType = 4326 (WGS 84; the reference hard-codes +proj=longlat +datum=WGS84, V73:164,775)
-    add_short(34735, {1, 1, 0, 3, 1024, 0, 1, 2, 1025, 0, 1, 1, 2048, 0, 1, 4326});
+    // a WGS 84 / UTM grid: GTModelType = 1 (projected), ProjectedCSType = the code
+    if (epsg == 4326) add_short(34735, {1, 1, 0, 3, 1024, 0, 1, 2, 1025, 0, 1, 1, 2048, 0, 1, 4326});
+    else add_short(34735, {1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, (uint16_t)epsg});
     if (!std::isnan(nodata)) {
         char buf[64];
         snprintf(buf, sizeof(buf), "%.17g", nodata);
@@ -590,14 +599,16 @@ static int mhs_tiff_read_dev_impl(const char *path, int ifd, void *out_dev, int6
     return rc;
 }
 
-static int mhs_tiff_write_f32_host_impl(const char *path, const mhs_grid *g, const float *data, double nodata, int compression) {
+static int mhs_tiff_write_f32_host_impl(const char *path, const mhs_grid *g, const float *data, double nodata, int compression, int epsg = 4326) {
     MHS_REQUIRE(path && g && data && g->nrow > 0 && g->ncol > 0, "bad arguments");
     MHS_REQUIRE(compression == 1 || compression == 8, "compression must be 1 (none) or 8 (deflate)");
-    return write_f32_tiff(path, *g, data, nodata, compression);
+    MHS_REQUIRE(epsg == 4326 || epsg_is_utm(epsg), "epsg must be 4326, 32601 .. 32660 or 32701 .. 32760");
+    return write_f32_tiff(path, *g, data, nodata, compression, epsg);
 }
 
 static int mhs_tiff_write_f32_dev_impl(const char *path, const mhs_grid *g, const double *plane_dev, int64_t ld, double nodata,
-                           int compression, void *stream) {
+                           int compression, void *stream, int epsg = 4326) {
+    MHS_REQUIRE(epsg == 4326 || epsg_is_utm(epsg), "epsg must be 4326, 32601 .. 32660 or 32701 .. 32760");
     if (int rc = require_ready()) return rc;
     MHS_REQUIRE(path && g && plane_dev && g->nrow > 0 && g->ncol > 0 && ld >= g->ncol, "bad arguments");
     MHS_REQUIRE(compression == 1 || compression == 8, "compression must be 1 (none) or 8 (deflate)");
@@ -613,9 +624,30 @@ static int mhs_tiff_write_f32_dev_impl(const char *path, const mhs_grid *g, cons
     int rc = MHS_OK;
     if (hipMemcpyAsync(host, tmp.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) { set_error("HIP error while downloading the plane"); rc = MHS_ERR_HIP; }
-    if (!rc) rc = write_f32_tiff(path, *g, host, nodata, compression);
+    if (!rc) rc = write_f32_tiff(path, *g, host, nodata, compression, epsg);
     (void)hipHostFree(host);
     return rc;
+}
+
+// the code of key 3072 (ProjectedCSType), else of key 2048 (GeographicType), else 0; only keys stored in the directory itself
+// (TIFFTagLocation 0, count 1) carry a code
+static int mhs_tiff_epsg_read_impl(const char *path, int32_t *epsg) {
+    MHS_REQUIRE(path && epsg, "bad arguments");
+    TiffFile t;
+    if (int rc = open_tiff(path, &t)) return rc;
+    const std::vector<double> &k = t.ifds[0].geokeys;
+    int32_t proj = 0, geog = 0;
+    if (k.size() >= 4) {
+        const size_t n_keys = std::min((size_t)k[3], (k.size() - 4) / 4);
+        for (size_t i = 0; i < n_keys; ++i) {
+            const double *e = &k[4 + 4 * i];
+            if (e[1] != 0.0 || e[2] != 1.0) continue;
+            if (e[0] == 3072.0) proj = (int32_t)e[3];
+            if (e[0] == 2048.0) geog = (int32_t)e[3];
+        }
+    }
+    *epsg = proj ? proj : geog;
+    return MHS_OK;
 }
 
 static int mhs_tfw_read_impl(const char *path, double *six) {
@@ -646,6 +678,16 @@ int mhs_tiff_write_f32_host(const char *path, const mhs_grid *g, const float *da
 int mhs_tiff_write_f32_dev(const char *path, const mhs_grid *g, const double *plane_dev, int64_t ld, double nodata,
                            int compression, void *stream) {
     return guard("mhs_tiff_write_f32_dev", [&] { return mhs_tiff_write_f32_dev_impl(path, g, plane_dev, ld, nodata, compression, stream); });
+}
+int mhs_tiff_write_f32_host_crs(const char *path, const mhs_grid *g, const float *data, double nodata, int compression, int epsg) {
+    return guard("mhs_tiff_write_f32_host_crs", [&] { return mhs_tiff_write_f32_host_impl(path, g, data, nodata, compression, epsg); });
+}
+int mhs_tiff_write_f32_dev_crs(const char *path, const mhs_grid *g, const double *plane_dev, int64_t ld, double nodata,
+                               int compression, void *stream, int epsg) {
+    return guard("mhs_tiff_write_f32_dev_crs", [&] { return mhs_tiff_write_f32_dev_impl(path, g, plane_dev, ld, nodata, compression, stream, epsg); });
+}
+int mhs_tiff_epsg_read(const char *path, int32_t *epsg) {
+    return guard("mhs_tiff_epsg_read", [&] { return mhs_tiff_epsg_read_impl(path, epsg); });
 }
 int mhs_tfw_read(const char *path, double *six) {
     return guard("mhs_tfw_read", [&] { return mhs_tfw_read_impl(path, six); });

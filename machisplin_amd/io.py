@@ -111,8 +111,18 @@ def read_aligned(paths, geom: Geometry | None = None, methods="bilinear", ifd: i
     return align(stacks, geom, methods)
 
 
-def write_geotiff(path: str, geom: Geometry, plane, nodata: float = float("nan"), compress: bool = True) -> None:
-    """terra::writeRaster(layer, "<name>.tif") (V73:1011,1020): FLT4S strips, deflate; NaN -> nodata if given."""
+def read_crs(path: str) -> int | None:
+    """The EPSG code a GeoTIFF's GeoKeyDirectory names (ProjectedCSTypeGeoKey 3072, else GeographicTypeGeoKey 2048), or None.
+    ``project.from_epsg`` makes a coordinate system of it."""
+    code = C.c_int32(0)
+    _lib.check(_lib.load().mhs_tiff_epsg_read(os.fsencode(path), C.byref(code)))
+    return int(code.value) or None
+
+
+def write_geotiff(path: str, geom: Geometry, plane, nodata: float = float("nan"), compress: bool = True, epsg: int = 4326) -> None:
+    """terra::writeRaster(layer, "<name>.tif") (V73:1011,1020): FLT4S strips, deflate; NaN -> nodata if given.  ``epsg``: the
+    grid's coordinate system, 4326 (lon/lat, as the reference writes) or a WGS 84 / UTM code 32601 .. 32660, 32701 .. 32760
+    (``project.utm(zone).epsg``); any other code is refused."""
     import torch
     g = geom.c_struct()
     comp = 8 if compress else 1
@@ -120,10 +130,10 @@ def write_geotiff(path: str, geom: Geometry, plane, nodata: float = float("nan")
         data = np.ascontiguousarray(plane, dtype=np.float32)
         if not math.isnan(nodata):
             data = np.where(np.isnan(data), np.float32(nodata), data)
-        _lib.check(_lib.load().mhs_tiff_write_f32_host(os.fsencode(path), C.byref(g), data.ctypes.data, float(nodata), comp))
+        _lib.check(_lib.load().mhs_tiff_write_f32_host_crs(os.fsencode(path), C.byref(g), data.ctypes.data, float(nodata), comp, int(epsg)))
         return
     if plane.dtype != torch.float64 or not plane.is_cuda or plane.dim() != 2 or plane.stride(1) != 1:
         raise ValueError("plane must be a 2-D float64 device tensor (or a numpy array)")
     st = torch.cuda.current_stream(plane.device).cuda_stream
-    _lib.check(_lib.lib().mhs_tiff_write_f32_dev(os.fsencode(path), C.byref(g), plane.data_ptr(), plane.stride(0),
-                                                 float(nodata), comp, st))
+    _lib.check(_lib.lib().mhs_tiff_write_f32_dev_crs(os.fsencode(path), C.byref(g), plane.data_ptr(), plane.stride(0),
+                                                     float(nodata), comp, st, int(epsg)))
