@@ -36,6 +36,7 @@ constexpr int LOG_TAB_N = 1 << LOG_TAB_BITS;
 // synchronisation -- per fit).  mhs_tps_fit uses lane 0; mhs_tps_surface fits its tiles on several lanes
 // from host threads.
 constexpr int FIT_PANEL_CUS = 32;      // compute units the 32-column route's trailing update stays off (a multiple of 8: the same ones in every XCD)
+constexpr int SVR_POOL_SLOTS = 64;    // counters of the ksvm row-tile kernel's tile pool (Context::svr_pool)
 struct FitLane {
     hipStream_t s = nullptr, s2 = nullptr;
     hipStream_t ms = nullptr, ms2 = nullptr;   // the same pair confined to the compute units mhs_fit_reserve_cus keeps free
@@ -54,6 +55,11 @@ struct Context {
     FitLane *batch = nullptr;             // the batched small fits' own lane: ONE plain stream + arena, no CU-masked streams (batch_lane)
     double2 *log_tab = nullptr;  // device, LOG_TAB_N entries
     double *exp_tab = nullptr;   // device, 4096 entries 2^(j/4096) (svr_kernel)
+    // tile counters of the resident ksvm row-tile launches, one per launch in flight (ensemble.hip: svr_pool_take); made on first use
+    unsigned long long *svr_pool = nullptr;
+    hipEvent_t svr_pool_ev[SVR_POOL_SLOTS] = {};
+    unsigned svr_pool_next = 0;
+    int svr_rt_blocks_per_cu[16] = {};    // by P: resident blocks of svr_rt_resident_kernel<P> per compute unit (0 = not asked yet)
     double *points_arena = nullptr;       // grow-only device scratch of mhs_residual_points
     size_t points_arena_cap = 0;          // in doubles
     // grow-only device scratch of mhs_mosaic_feather_dev (sums, counts, seam boxes), one per mosaic lane: lane 0 = the calling

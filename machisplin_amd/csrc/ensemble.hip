@@ -211,9 +211,18 @@ __device__ __forceinline__ void rt_exp_table_stage(double *tab2, const double *_
         tab2[i] = __hiloint2double((int)(((unsigned)__double2hiint(e) & 0x000fffffu) - ((unsigned)j << 8)), __double2loint(e));
     }
 }
-__device__ __forceinline__ double table_exp_neg_acc_rt(double u, const double *tab2, double acc) {   // acc + exp(-700 u)
-    const double MAGIC = 0x1.8p52 + 1023.0 * EXP_TAB_N, NK = -EXP_RANGE * EXP_SCALE;
-    const double t = fma(u, NK, MAGIC);
+// magic and c1 are RT_EXP_MAGIC and RT_EXP_C1 in vector registers (rt_exp_consts): each is the second constant of an fma whose
+// first already takes the instruction's one scalar operand.  Left to the compiler, inside the resident kernel's tile loop they
+// live in scalar registers and are copied over in every trip of the support-vector loop, two more instructions per 145.
+constexpr double RT_EXP_MAGIC = 0x1.8p52 + 1023.0 * EXP_TAB_N, RT_EXP_C1 = 1.0 / EXP_SCALE;
+__device__ __forceinline__ void rt_exp_consts(double &magic, double &c1) {
+    magic = RT_EXP_MAGIC; c1 = RT_EXP_C1;
+    asm("" : "+v"(magic));
+    asm("" : "+v"(c1));
+}
+__device__ __forceinline__ double table_exp_neg_acc_rt(double u, const double *tab2, double acc, double magic, double c1) {   // acc + exp(-700 u)
+    const double MAGIC = RT_EXP_MAGIC, NK = -EXP_RANGE * EXP_SCALE;
+    const double t = fma(u, NK, magic);
     const double kd = t - MAGIC;
     const unsigned k = (unsigned)__double2loint(t);
     unsigned off;
@@ -221,8 +230,8 @@ __device__ __forceinline__ double table_exp_neg_acc_rt(double u, const double *t
     const double r = fma(u, NK, -kd);
     const double mj = *(const double *)((const char *)tab2 + off);
     const double sj = __hiloint2double((int)((k << 8) + (unsigned)__double2hiint(mj)), __double2loint(mj));
-    const double C1 = 1.0 / EXP_SCALE, C2 = 0.5 / (EXP_SCALE * EXP_SCALE);
-    double q = fma(r, C2, C1);
+    const double C2 = 0.5 / (EXP_SCALE * EXP_SCALE);
+    double q = fma(r, C2, c1);
     q = fma(q, r, 1.0);
     return fma(sj, q, acc);
 }
@@ -308,28 +317,20 @@ __global__ __launch_bounds__(256) void svr_kernel(const double *__restrict__ svp
 // TAB2 chooses the exponential: table_exp_neg_acc_rt and its 64 KB table (the same bits as svr_kernel's form:
 // tests/test_ksvm_rowtile_exp_gpu.py), or table_exp_neg_acc and the 32 KB table.  NW is the block's waves; launch_svr sets
 // both (svr_rt_tab2, svr_rt_waves).  A wave has its own tile and its own slice of aw; the only block-wide barrier is the
-// one behind the table's staging.
-template <int P, int R, int NW, bool TAB2>
-__global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restrict__ svp, int nsv, int stride,
-                                                         int npos, const double *__restrict__ xcs,
-                                                         const double *__restrict__ gtab, double sigma, double b,
-                                                         double amax, double y_center, double y_scale, StackDev s, PredGeom g,
-                                                         int tiles_per_row, double weight, int accumulate, double *__restrict__ out) {
+// one behind the table's staging.  svr_rt_kernel gives every wave one tile; svr_rt_resident_kernel lets a wave pull tile
+// after tile.
+//
+// exp() for a cell's back-scaling, as a CALL.  Inlined into the resident kernel's tile loop, its eleven polynomial constants
+// are hoisted out of that loop into vector registers for the whole kernel (141 VGPRs at P = 5; held to 128 the compiler
+// spills them, 44 bytes of scratch); the callee keeps them to itself.  The same function, the same bits.
+__device__ __attribute__((noinline)) double svr_rt_exp_call(double z) { return exp(z); }
+// One tile: the 64 R cells of row `row` from column `tcol` on, R cells per lane.  aw is the wave's own 1 KB of LDS.
+template <int P, int R, bool TAB2, bool EXPCALL>
+__device__ __forceinline__ void svr_rt_tile(const double *__restrict__ svp, int nsv, int stride, int npos,
+                                            const double *__restrict__ xcs, const double *etab, double *aw, double sigma, double b,
+                                            double amax, double y_center, double y_scale, const StackDev &s, const PredGeom &g,
+                                            int row, int tcol, int lane, double weight, int accumulate, double *__restrict__ out) {
     constexpr int CH = 128;
-    __shared__ double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
-    __shared__ double aw[NW][CH];
-    if constexpr (TAB2) rt_exp_table_stage(etab, gtab, threadIdx.x, 64 * NW);
-    else
-        for (int i = threadIdx.x; i < EXP_TAB_N; i += 64 * NW) {   // mantissa bits of 2^(j/4096)
-            const double e = gtab[i];
-            etab[i] = __hiloint2double(__double2hiint(e) & 0x000fffff, __double2loint(e));
-        }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t ntiles = (int64_t)g.nr * tiles_per_row;
-    const int64_t tile = (int64_t)blockIdx.x * NW + wave;
-    if (tile >= ntiles) return;
-    const int row = (int)(tile / tiles_per_row), tcol = (int)(tile - (int64_t)row * tiles_per_row) * (64 * R);
     double x[R][P], q[R], acc[R], accn[R];
     bool na[R], ok[R];
     int col[R];
@@ -365,6 +366,8 @@ __global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restric
     // its 42 vector instructions per support vector on them, 14.0 -> 13.1 per (cell, SV))
     const bool fold = __builtin_amdgcn_readfirstlane((int)(qhi - qlo <= 0.5)) != 0;   // false too when every cell of the wave is NA (qhi = -1, qlo = 2e300)
     const double S = fold ? qhi : 0.0;
+    double magic = 0.0, c1 = 0.0;
+    if constexpr (TAB2) rt_exp_consts(magic, c1);
     auto sum_range = [&](int v0, int v1, double (&a)[R], auto folded) {
         constexpr bool FOLD = decltype(folded)::value;
         auto pair = [&](const double *sp, const double ap) {
@@ -374,7 +377,7 @@ __global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restric
 #pragma unroll
                 for (int j = 0; j < P - 1; ++j) arg = fma(sp[j], x[c][j], arg);
                 arg = fmin(fmax(arg, 0.0), 1.0);
-                a[c] = TAB2 ? table_exp_neg_acc_rt(arg, etab, a[c]) : table_exp_neg_acc(arg, etab, a[c]);
+                a[c] = TAB2 ? table_exp_neg_acc_rt(arg, etab, a[c], magic, c1) : table_exp_neg_acc(arg, etab, a[c]);
             }
         };
         for (int vb = v0; vb < v1; vb += CH) {
@@ -382,11 +385,11 @@ __global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restric
             __builtin_amdgcn_wave_barrier();
             for (int e = lane; e < n; e += 64) {
                 const double *sp = svp + (int64_t)(vb + e) * stride;
-                aw[wave][e] = fma(sp[P - 1], xlat, sp[P]) + S;
+                aw[e] = fma(sp[P - 1], xlat, sp[P]) + S;
             }
             __builtin_amdgcn_wave_barrier();
             const double *sp = svp + (int64_t)vb * stride;
-            const double *ar = aw[wave];
+            const double *ar = aw;
             int e = 0;
             for (; e + 4 <= n; e += 4) {          // four support vectors per trip: one cursor bump, immediate LDS offsets
 #pragma unroll
@@ -406,10 +409,103 @@ __global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restric
 #pragma unroll
     for (int c = 0; c < R; ++c)
         if (ok[c]) {
-            const double back = fold ? exp(EXP_RANGE * (S - q[c])) : 1.0;
+            const double back = fold ? (EXPCALL ? svr_rt_exp_call(EXP_RANGE * (S - q[c])) : exp(EXP_RANGE * (S - q[c]))) : 1.0;
             const double pred = ((acc[c] - accn[c]) * back * amax - b) * y_scale + y_center;
             emit(out, (int64_t)row * g.ld_out + col[c], na[c] ? NAN : pred, weight, accumulate);
         }
+}
+
+// A tile by its index, for the resident kernel (exp() as a call).
+template <int P, int R, bool TAB2>
+__device__ __forceinline__ void svr_rt_run(int64_t tile, const double *__restrict__ svp, int nsv, int stride, int npos,
+                                           const double *__restrict__ xcs, const double *etab, double *aw, double sigma, double b,
+                                           double amax, double y_center, double y_scale, const StackDev &s, const PredGeom &g,
+                                           int tiles_per_row, int lane, double weight, int accumulate, double *__restrict__ out) {
+    const int row = (int)(tile / tiles_per_row), tcol = (int)(tile - (int64_t)row * tiles_per_row) * (64 * R);
+    svr_rt_tile<P, R, TAB2, true>(svp, nsv, stride, npos, xcs, etab, aw, sigma, b, amax, y_center, y_scale, s, g, row, tcol, lane, weight,
+                                  accumulate, out);
+}
+template <int NW, bool TAB2>
+__device__ __forceinline__ void svr_rt_stage(double *etab, const double *__restrict__ gtab) {
+    if constexpr (TAB2) rt_exp_table_stage(etab, gtab, threadIdx.x, 64 * NW);
+    else
+        for (int i = threadIdx.x; i < EXP_TAB_N; i += 64 * NW) {   // mantissa bits of 2^(j/4096)
+            const double e = gtab[i];
+            etab[i] = __hiloint2double(__double2hiint(e) & 0x000fffff, __double2loint(e));
+        }
+}
+
+// One tile per wave, three cells per lane everywhere: a block per NW tiles.
+template <int P, int R, int NW, bool TAB2>
+__global__ __launch_bounds__(64 * NW) void svr_rt_kernel(const double *__restrict__ svp, int nsv, int stride,
+                                                         int npos, const double *__restrict__ xcs,
+                                                         const double *__restrict__ gtab, double sigma, double b,
+                                                         double amax, double y_center, double y_scale, StackDev s, PredGeom g,
+                                                         int tiles_per_row, double weight, int accumulate, double *__restrict__ out) {
+    __shared__ double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
+    __shared__ double aw[NW][128];
+    svr_rt_stage<NW, TAB2>(etab, gtab);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t ntiles = (int64_t)g.nr * tiles_per_row;
+    const int64_t tile = (int64_t)blockIdx.x * NW + wave;
+    if (tile >= ntiles) return;
+    const int row = (int)(tile / tiles_per_row), tcol = (int)(tile - (int64_t)row * tiles_per_row) * (64 * R);
+    svr_rt_tile<P, R, TAB2, false>(svp, nsv, stride, npos, xcs, etab, aw[wave], sigma, b, amax, y_center, y_scale, s, g, row, tcol, lane,
+                                   weight, accumulate, out);
+}
+
+// RESIDENT WAVES.  The launch holds only as many blocks as the device keeps resident at once, and after the staging barrier
+// every wave pulls tile indices from *pool (one counter per launch: svr_pool_take) until the pool is empty.  A wave never
+// waits for a block-mate or for another block -- nothing can hang --, so a SIMD whose oldest wave ends early gets the next
+// tile at once instead of idling until the block's slowest wave is through.  A block that finds the pool empty (fewer tiles
+// than waves; a CU-masked stream that runs the blocks in turns) leaves at once.  Which wave takes which tile has no bearing
+// on the plane: a tile is the same cells, the same fold decision and the same order of additions whoever runs it.
+// The arguments that are no pointers travel as ONE struct behind the five pointers, and every tile reads them afresh from
+// the kernel-argument segment through a pointer the compiler cannot see through.  Held across the loop's back edge instead,
+// the ~50 scalar registers of arguments and what the compiler hoists out of the tile (the scaling constants) come on top
+// of the ~50 of the support-vector loop, and the overflow is parked in vector registers: 159 VGPRs at P = 5 against the
+// tile's own 124.  The pointers stay plain __restrict__ arguments: that is what lets the support-vector records come
+// through the scalar cache (read through a pointer that was itself loaded, they become vector loads of 32 registers).
+struct SvrRtScalars {
+    int nsv, stride, npos, tiles_per_row; double sigma, b, amax, y_center, y_scale;
+    StackDev s; PredGeom g; double weight; int accumulate;
+};
+constexpr int SVR_RT_SCALARS_AT = 5 * sizeof(void *);     // byte offset of `sc` among the resident kernel's arguments: FIVE pointers ahead of it
+static_assert(alignof(SvrRtScalars) <= 8, "svr_rt_resident_kernel: `sc` does not follow the pointers without padding");
+// the kernel rebuilds g and s field by field from the argument segment: a field added to either must be added there
+static_assert(sizeof(PredGeom) == 64 && sizeof(StackDev) == 48 && sizeof(SvrRtScalars) == 184,
+              "svr_rt_resident_kernel copies PredGeom / StackDev field by field: update the copies and these sizes together");
+inline void svr_rt_field_counts(const PredGeom &g, const StackDev &s) {      // never called: fails to compile when a field count changes
+    const auto &[g0, g1, g2, g3, g4, g5, g6, g7, g8] = g;
+    const auto &[s0, s1, s2, s3, s4, s5, s6, s7] = s;
+    (void)g0; (void)g1; (void)g2; (void)g3; (void)g4; (void)g5; (void)g6; (void)g7; (void)g8;
+    (void)s0; (void)s1; (void)s2; (void)s3; (void)s4; (void)s5; (void)s6; (void)s7;
+}
+template <int P, int R, int NW, bool TAB2, int WPS>
+__global__ __launch_bounds__(64 * NW, WPS) void svr_rt_resident_kernel(const double *__restrict__ svp, const double *__restrict__ xcs,
+                                                                  const double *__restrict__ gtab, double *__restrict__ out,
+                                                                  unsigned long long *__restrict__ pool, SvrRtScalars sc) {
+    __shared__ double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
+    __shared__ double aw[NW][128];
+    svr_rt_stage<NW, TAB2>(etab, gtab);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    typedef const __attribute__((address_space(4))) char *KBytes;
+    typedef const __attribute__((address_space(4))) SvrRtScalars *KScalars;
+    for (;;) {
+        KScalars k = (KScalars)((KBytes)__builtin_amdgcn_kernarg_segment_ptr() + SVR_RT_SCALARS_AT);
+        asm volatile("" : "+s"(k));
+        unsigned long long t = 0;
+        if (lane == 0) t = atomicAdd(pool, 1ull);         // relaxed, device scope: the index is all the waves share
+        const int64_t tile = (int64_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
+                                       (unsigned)__builtin_amdgcn_readfirstlane((int)t));
+        const PredGeom g = {k->g.xmin, k->g.ymax, k->g.xres, k->g.yres, k->g.r0, k->g.c0, k->g.nr, k->g.nc, k->g.ld_out};
+        if (tile >= (int64_t)g.nr * k->tiles_per_row) return;
+        const StackDev s = {k->s.data, k->s.C, k->s.dtype, k->s.plane_stride, k->s.ld, k->s.nodata, k->s.has_nodata, k->s.all_from_planes};
+        svr_rt_run<P, R, TAB2>(tile, svp, k->nsv, k->stride, k->npos, xcs, etab, aw[wave], k->sigma, k->b, k->amax,
+                               k->y_center, k->y_scale, s, g, k->tiles_per_row, lane, k->weight, k->accumulate, out);
+    }
 }
 
 // ---------------------------------------------------------------------- trees --
@@ -1241,32 +1337,83 @@ static void launch_nnet(const mhs_model *m, const StackDev &s, const PredGeom &g
                         double *out, hipStream_t st, unsigned blocks) {
     hipLaunchKernelGGL((nnet_kernel<P>), dim3(blocks), dim3(256), 0, st, m->dpar, m->n0, m->s0, m->s1, s, g, w, acc, out);
 }
-// The form of svr_rt_kernel by P.  P <= 5 (100 / 112 / 124 VGPRs at P = 3 / 4 / 5 in the built object: four waves per
-// SIMD): table_exp_neg_acc_rt with its 64 KB table in blocks of 8 waves, two per CU; one block of 16 instead is 23 % slower
-// at P = 5.  Larger P keep table_exp_neg_acc, the 32 KB table and blocks of 4: at three waves per SIMD the 64 KB table
-// leaves room for ONE block of 12 waves per CU, and P = 7 lost 7 % of cfg5's step with it (profiles/ksvm_exp_insertion.txt).
-// P = 6 and P = 8 .. 12 were not measured in either form.
-constexpr bool svr_rt_tab2(int P) { return P <= 5; }
-constexpr int svr_rt_waves(int P) { return svr_rt_tab2(P) ? 8 : 4; }
+// The form of the row-tile kernel by P (figures: profiles/ksvm_resident_waves.txt, profiles/ksvm_exp_insertion.txt).
+// P <= 5: table_exp_neg_acc_rt with its 64 KB table and RESIDENT waves that pull their tiles (svr_rt_resident_kernel), in ONE
+// block of 16 waves per CU -- 126 / 116 / 128 VGPRs at P = 3 / 4 / 5 in the built object, no scratch, four waves per SIMD.
+// With one tile per wave a CU took a new block only when the block's slowest wave was through, and one block of 16 was 23 %
+// slower than two of 8; with resident waves no wave waits for a block-mate, the block's shape is free, and one block per CU
+// stages the table once instead of twice: a cfg3 step takes 230.1 ms with the one-tile form in 2 x 8 and 224.3 resident in 1 x 16
+// (resident in 2 x 8: 4.4 ms more than in 1 x 16).  Short tiles at row ends were measured on top and not kept (-0.7 ms, within noise).
+// Larger P keep the one-tile kernel with table_exp_neg_acc, the 32 KB table and blocks of 4 waves, as before.  P = 7 resident
+// with the 64 KB table in one block of 12 was TIMED at cfg5 (3 087 -> 2 898 ms per step) but its planes were never checked
+// on a device, so it is not used; P = 6 and P = 8 .. 12 were measured in no form.
+constexpr bool svr_rt_tab2(int P) { return P <= 5; }       // and with it resident waves
+constexpr int svr_rt_waves_per_simd(int P) { return P <= 5 ? 4 : 3; }   // what the resident form is compiled for (its register budget)
+constexpr int svr_rt_waves(int P) { return svr_rt_tab2(P) ? 16 : 4; }
+
+// The tile counter of one resident launch.  A slot's ring holds SVR_POOL_SLOTS counters; a launch takes the next one, zeroes
+// it on its OWN stream ahead of the kernel and records the slot's event behind the kernel.  The launch that takes the same
+// counter SVR_POOL_SLOTS launches later first makes its stream wait for that event (a device-side wait; for an event that
+// has fired or was never recorded, nothing), so no two launches in flight -- on whatever streams of the slot -- ever count
+// in the same word, and the host never waits.  svr_pool_mu is held from the take to the record: host threads that launch
+// on one slot pass through one at a time.
+static std::mutex svr_pool_mu[MAX_SLOTS];
+static int svr_pool_take(Context &c, hipStream_t st, int *idx, unsigned long long **counter) {
+    if (!c.svr_pool) {      // the events first: the ring counts as made only when all of it is
+        for (hipEvent_t &e : c.svr_pool_ev)
+            if (!e) MHS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        MHS_HIP(hipMalloc((void **)&c.svr_pool, sizeof(unsigned long long) * SVR_POOL_SLOTS));
+    }
+    *idx = (int)(c.svr_pool_next++ % SVR_POOL_SLOTS);
+    *counter = c.svr_pool + *idx;
+    MHS_HIP(hipStreamWaitEvent(st, c.svr_pool_ev[*idx], 0));
+    MHS_HIP(hipMemsetAsync(*counter, 0, sizeof(unsigned long long), st));
+    return MHS_OK;
+}
+
 template <int P>
-static void launch_svr(const mhs_model *m, const StackDev &s, const PredGeom &g, double w, int acc,
-                       double *out, hipStream_t st, int64_t total) {
+static int launch_svr(const mhs_model *m, const StackDev &s, const PredGeom &g, double w, int acc,
+                      double *out, hipStream_t st, int64_t total) {
     constexpr int R = 3;      // cells per lane (2: 83.5, 3: 81.0, 4: 82.4 ms on 8000^2 cells x 3000 SVs)
     // grid mode with long rows: a wave = 192 cells of one row, the LAT term of the exponent once per wave (svr_rt_kernel)
     const int tpr = (g.nc + 64 * R - 1) / (64 * R);
     if (!s.all_from_planes && P == s.C + 2 && P >= 3 && !getenv("MHS_SVR_NO_ROWTILE") && (double)g.nc >= 0.93 * (double)tpr * (64 * R)) {
         const int64_t ntiles = (int64_t)g.nr * tpr;
         constexpr int NW = svr_rt_waves(P);
-        hipLaunchKernelGGL((svr_rt_kernel<P, R, NW, svr_rt_tab2(P)>), dim3((unsigned)((ntiles + NW - 1) / NW)), dim3(64 * NW), 0, st,
-                           m->dpar, m->n0, m->n1, m->n2, m->dpar + (size_t)m->n0 * m->n1, ctx().exp_tab, m->s1, m->s0, m->s4,
-                           m->s2, m->s3, s, g, tpr, w, acc, out);
-        return;
+        const int64_t covering = (ntiles + NW - 1) / NW;       // blocks whose waves cover the tiles one each
+        if constexpr (svr_rt_tab2(P)) {
+            auto kern = svr_rt_resident_kernel<P, R, NW, true, svr_rt_waves_per_simd(P)>;
+            Context &c = ctx();
+            std::lock_guard<std::mutex> lk(svr_pool_mu[current_slot()]);
+            int &per_cu = c.svr_rt_blocks_per_cu[P];            // blocks of this form a compute unit holds; the slot's own, under its mutex
+            if (per_cu == 0) {
+                int n = 0;
+                MHS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kern, 64 * NW, 0));
+                per_cu = std::max(1, n);
+            }
+            const int64_t resident = (int64_t)(c.n_cu > 0 ? c.n_cu : 256) * per_cu;
+            int idx = 0;
+            unsigned long long *counter = nullptr;
+            if (int rc = svr_pool_take(c, st, &idx, &counter)) return rc;
+            const SvrRtScalars sc = {m->n0, m->n1, m->n2, tpr, m->s1, m->s0, m->s4, m->s2, m->s3, s, g, w, acc};
+            hipLaunchKernelGGL(kern, dim3((unsigned)std::min(resident, covering)), dim3(64 * NW), 0, st,
+                               m->dpar, m->dpar + (size_t)m->n0 * m->n1, c.exp_tab, out, counter, sc);
+            MHS_HIP(hipEventRecord(c.svr_pool_ev[idx], st));
+            return MHS_OK;
+        }
+        else {
+            hipLaunchKernelGGL((svr_rt_kernel<P, R, NW, false>), dim3((unsigned)covering), dim3(64 * NW), 0, st,
+                               m->dpar, m->n0, m->n1, m->n2, m->dpar + (size_t)m->n0 * m->n1, ctx().exp_tab, m->s1, m->s0, m->s4,
+                               m->s2, m->s3, s, g, tpr, w, acc, out);
+            return MHS_OK;
+        }
     }
     const int64_t half = (total + R - 1) / R;
     hipLaunchKernelGGL((svr_kernel<P, R>), dim3((unsigned)((half + 255) / 256)), dim3(256), 0, st,
                        m->dpar, m->n0, m->n1, m->n2, m->dpar + (size_t)m->n0 * m->n1, ctx().exp_tab, m->s1, m->s0, m->s4,
                        m->s2, m->s3,
                        s, g, w, acc, out);
+    return MHS_OK;
 }
 
 #define MHS_DISPATCH_P(P_, CALL)                                                     \
@@ -1580,7 +1727,7 @@ static int launch_model(const mhs_model *m, const StackDev &s, const PredGeom &g
                                weight, accumulate, out);
             break;
         case K_SVR: {
-#define CALL_SVR(P) launch_svr<P>(m, s, g, weight, accumulate, out, st, total)
+#define CALL_SVR(P) if (int rc = launch_svr<P>(m, s, g, weight, accumulate, out, st, total)) return rc
             MHS_DISPATCH_P(m->p, CALL_SVR)
 #undef CALL_SVR
             break;

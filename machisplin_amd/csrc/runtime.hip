@@ -312,6 +312,8 @@ static void shutdown_slot(int slot) {
     c.mosaic_arena_cap[0] = c.mosaic_arena_cap[1] = 0;
     if (c.points_arena) (void)hipFree(c.points_arena);
     if (c.exp_tab) (void)hipFree(c.exp_tab);
+    if (c.svr_pool) (void)hipFree(c.svr_pool);
+    for (hipEvent_t pe : c.svr_pool_ev) if (pe) (void)hipEventDestroy(pe);
     if (c.upload) { (void)hipStreamSynchronize(c.upload); (void)hipStreamDestroy(c.upload); }
     for (hipStream_t ps : {c.pipe_h2d, c.pipe_comp, c.pipe_d2h})
         if (ps) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
