@@ -981,6 +981,88 @@ MHS_API int mhs_warp_dev(const mhs_grid *src_grid, const mhs_stack *src_stack, c
 MHS_API int mhs_warp(const mhs_grid *src_grid, const mhs_stack *src_stack, const mhs_grid *dst_grid, int64_t r0, int64_t r1,
                      int64_t c0, int64_t c1, const mhs_warp_lattice *lat, int method, void *out_host, int out_dtype);
 
+/* -------------------------------------------------------------------- focal --
+ * Window statistics of one layer at ANY radius -- terra::focal for sums, moments, min and max: the multi-scale covariates (TPI and DEV over
+ * kilometres, landscape-scale sd, the smoothed "effective terrain") that "terrain"'s relief, a window in LDS, stops short of at
+ * MHS_TERRAIN_MAX_RADIUS.  The reference has no such step.  THE RULES (this text is the specification; csrc/focal_rule.h holds
+ * them as code).  A statistic costs O(1) per cell in the radius for a square window and O(R) for a circular one.
+ *
+ * INPUT.  Layer `layer` of an mhs_stack (int16, float32, float64), converted exactly to double; NA = NaN or the stack's nodata;
+ * cells outside the raster count as NA; NA cells are skipped (na.rm): "terrain"'s rules.  With zc = z - offset (one rounded
+ * subtraction; `offset` is an argument, any finite double) the library sums three planes: a = zc, b = zc * zc, and the valid
+ * flag, 0 at NA cells (a = b = +0.0 there).  The count is summed in integers and is exact.
+ * RADII.  n_radii in 1 .. MHS_FOCAL_MAX_RADII radii, each in 1 .. max(nrow, ncol).  The row prefixes (below) do not depend on the
+ * radius and are made once per call; radius k's planes equal the single-radius call's bit for bit.
+ * SHAPES.  MHS_FOCAL_SQUARE: rows r - R .. r + R and columns c - R .. c + R, cut to the raster.  MHS_FOCAL_CIRCLE: the offsets
+ * with dr^2 + dc^2 <= R^2, relief's window: row r + dr takes the columns c - w(dr) .. c + w(dr) cut to the raster, w(dr) the
+ * largest dc with dr^2 + dc^2 <= R^2.
+ *
+ * THE ORDER OF THE SUMS -- a pure function of the plane, the offset and the radius, whatever the window, the host bands or the
+ * number of radii.  B = MHS_FOCAL_BLOCK.  The BLOCKED PREFIX of a sequence x[0 .. n):
+ *      p[i]  = x[i] if i is a multiple of B, else p[i - 1] + x[i]          sequential inside the aligned block of B elements
+ *      T[k]  = p[last element of block k]                                  the block totals
+ *      O[0]  = 0.0,  O[k] = O[k - 1] + T[k - 1]                             their sequential running sum
+ *      P[i]  = O[i / B] + p[i]
+ * and the sum of x[lo .. hi] is  P[hi] - P[lo - 1],  with P[-1] = 0.0.  numpy: cumsum over the array reshaped to (-1, B), cumsum
+ * over the totals shifted by one, one addition.
+ *   1. every ROW of the raster, from column 0, gets the blocked prefixes of a, b and the flag;  W[r][c; w] = the sum of the row's
+ *      columns max(c - w, 0) .. min(c + w, ncol - 1).
+ *   2. SQUARE: every COLUMN of W[.][c; R], from row 0, gets the blocked prefix down the rows; the window's sum is that of rows
+ *      max(r - R, 0) .. min(r + R, nrow - 1).
+ *      CIRCLE: S = 0.0, then S = S + W[r + dr][c; w(dr)] for dr = -R .. R in that order, rows outside the raster left out.
+ * STATISTICS from n (count), S1 (of a), S2 (of b), the smallest and largest valid value of the window and the centre e; bit k of
+ * `stats` selects plane k, the planes of a radius come in ascending bit order, radius after radius (plane index = k_radius *
+ * popcount(stats) + position):
+ *      0 count       n                                  4 min          5 max          6 range = max - min
+ *      1 sum         S1 + n * offset                    7 minus_mean   e - mean
+ *      2 mean        offset + S1 / n                    8 above_min    e - min        9 below_max = max - e
+ *      3 sd          sqrt(max(0, (S2 - S1 * S1 / n) / (n - 1))),  NA where n < 2     10 dev = (e - mean) / sd,  NA where sd is NA or 0
+ *    n = 0 gives count 0 and NA elsewhere.  An NA centre gives NA in every plane; with fill_na != 0 the planes that do not use the
+ *    centre (count, sum, mean, sd, min, max, range) are made there too.  NA is NaN.  A float32 output is the float64 value rounded
+ *    once.
+ * MIN AND MAX (square windows) are exact whatever the order they are found in, so there is no rule about their value, only a way to
+ * find them in O(1) per cell: a separable running minimum, rows then columns, on aligned blocks of B elements -- the minimum from
+ * the block's start to i, from i to the block's end, and a doubling table over the blocks' minima (csrc/focal_rule.h,
+ * focal_range_min); a window that lies strictly inside one block reads its fewer than B elements.  The maximum is minus the
+ * minimum of -z.  MHS_FOCAL_CIRCLE gives the sum family only (bits 0, 1, 2, 3, 7, 10): asking it for bits 4, 5, 6, 8 or 9 is
+ * MHS_ERR_INVALID, and the message names mhs_relief for R <= MHS_TERRAIN_MAX_RADIUS and the square window beyond.
+ *
+ * THE BOUND on a window sum against the exact sum of the same rounded terms (u = 2^-53).  A term of a blocked prefix passes
+ * through at most B - 1 additions inside its block, one per later block in the offsets and the final one: depth
+ * d(n) = B + ceil(n / B).  So |P^[i] - P[i]| <= g(d) A, g(d) = d u / (1 - d u), A = the sum of |x| up to i, and a row-window sum,
+ * the difference of two prefixes, is off by at most (2 g(d(ncol)) + u) A_row.  The column prefixes add the computed W's: the row
+ * errors of the rows inside the window stay, those above it cancel, and the column prefix adds (2 g(d(nrow)) + u) times the sum
+ * of |W|.  With A = the sum of |z - offset| (for S2: of (z - offset)^2) over the raster's rows 0 .. r + R:
+ *      square:  |S^ - S| <= 2.02 u (d(ncol) + d(nrow) + 1) A          circle:  |S^ - S| <= 2.02 u (d(ncol) + R + 1) A
+ * (the circle adds 2 R + 1 row sums in sequence: depth 2 R + 1 in place of the column prefix's 2 d).  The offset is what keeps
+ * this small where it matters: for elevations of mean 2 000 and sd 5, A with offset = the mean is 400 times smaller than without,
+ * and S2 - S1 * S1 / n no longer cancels eleven of its digits.  A `window` call must pass the SAME offset as the whole-grid call.
+ *
+ * SCRATCH, from stream-ordered memory, given back behind the last kernel: 20 bytes per cell of the rows a call reads (the row
+ * prefixes: two doubles and an int32) and, for a square window, 24 bytes per cell of those rows inside the window's columns (the
+ * in-block column prefixes: two doubles and an int64), plus 48 bytes per column and block of B rows.  The min / max family adds 32
+ * and 48 bytes per cell to the two (the running minima of z and -z from both ends of a block; the row-window minima and theirs)
+ * and the doubling tables, 1 / 64 of a plane per level.  A square window reads the rows 0 .. r1 + R (the column prefix starts at
+ * row 0), a circle the rows r0 - R .. r1 + R.
+ *
+ * Every argument is checked before the first device call; MHS_ERR_INVALID names the bad one (the window, the layer, n_radii, the
+ * radius with its limit, the shape, the mask, the offset, out, ld, plane_stride).                                          */
+#define MHS_FOCAL_BLOCK 64        /* B: elements of an aligned block of the blocked prefix */
+#define MHS_FOCAL_MAX_RADII 8
+#define MHS_FOCAL_SQUARE 0
+#define MHS_FOCAL_CIRCLE 1
+/* DEVICE planes: out_dev holds n_radii * popcount(stats) planes, each (r1-r0) x ld row-major, plane_stride elements apart, of
+ * out_dtype MHS_F64 or MHS_F32.  Only enqueues on `stream`. */
+MHS_API int mhs_focal_dev(const mhs_grid *g, const mhs_stack *stack, int layer, const int *radii, int n_radii, int shape,
+                          unsigned stats, int fill_na, double offset, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void *out_dev,
+                          int out_dtype, int64_t ld, int64_t plane_stride, void *stream);
+/* same, HOST planes in, HOST planes out ((r1-r0) x (c1-c0), one behind the other): row bands of the window go up with the rows
+ * above and below that they read (R rows below; above, R rows for a circle and, for a square window, R + 1 rows and the rest of
+ * that row's block of B rows: the column offsets of that block are carried from band to band on the device), through the same kernels; MHS_HOST_BANDS as for mhs_terrain.  Blocks
+ * until done. */
+MHS_API int mhs_focal(const mhs_grid *g, const mhs_stack *stack, int layer, const int *radii, int n_radii, int shape, unsigned stats,
+                      int fill_na, double offset, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void *out_host, int out_dtype);
+
 /* ---------------------------------------------------------------- proximity --
  * Distance-to-feature covariates: distance to the coast, to open water, to the channel network, and what follows from knowing
  * WHICH cell is nearest (the direction to it, another layer's value there, the height above the nearest stream).  The

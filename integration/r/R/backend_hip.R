@@ -319,6 +319,35 @@ mhs_warp <- function(x, y, lattice, method = "bilinear") {
   r
 }
 
+# ---- terra::focal at any radius (machisplin_hip.h "focal"): the multi-scale covariates -- TPI and DEV over kilometres, the sd of
+# elevation, the smoothed terrain -- that mhs_terrain's relief, limited to 45 cells, stops short of -------------------------------
+# x: a SpatRaster (layer `layer` is used); radius: 1 .. 8 radii in cells, each up to max(nrow, ncol); stats: any of .mhs_focal_stats;
+# shape "square" (every statistic) or "circle" (count, sum, mean, sd, minus_mean, dev); fill.na: make the statistics that do not
+# use the centre at NA cells too; offset: what the values are centred by before they are squared and summed (default: the layer's
+# rounded mean).  Returns a SpatRaster with one layer per radius and statistic, named <stat><radius>.
+.mhs_focal_stats <- c("count", "sum", "mean", "sd", "min", "max", "range", "minus_mean", "above_min", "below_max", "dev")
+mhs_focal <- function(x, radius, stats = "mean", layer = 1L, shape = "square", fill.na = FALSE, offset = NULL) {
+  bad <- setdiff(stats, .mhs_focal_stats)
+  if (length(bad)) stop("mhs_focal: unknown statistic ", paste(bad, collapse = ", "))
+  s <- match(shape, c("square", "circle"))
+  if (length(shape) != 1L || is.na(s)) stop("mhs_focal: shape must be square or circle")
+  if (s == 2L && any(stats %in% c("min", "max", "range", "above_min", "below_max")))
+    stop("mhs_focal: a circle gives the sum family only; mhs_terrain has above_min and below_max in a circle for radius <= 45, shape = \"square\" beyond")
+  v <- terra::values(x[[layer]])
+  if (is.null(offset)) offset <- round(mean(v, na.rm = TRUE))
+  if (!is.finite(offset)) offset <- 0
+  st <- intersect(.mhs_focal_stats, stats)                   # ascending bit order: the order of the columns that come back
+  m <- .Call("mhsr_focal", .mhs_geom(x), as.numeric(v), NA_real_, c(0, s - 1, as.numeric(isTRUE(fill.na)), as.numeric(offset)),
+             as.integer(radius), as.integer(sum(2^(match(st, .mhs_focal_stats) - 1))))
+  cols <- as.vector(outer(seq_along(st), (seq_along(radius) - 1L) * length(st), "+"))
+  names.all <- as.vector(outer(st, as.integer(radius), paste0))
+  want <- as.vector(outer(stats, as.integer(radius), paste0))
+  out <- terra::rast(x[[layer]], nlyrs = length(want))
+  terra::values(out) <- m[, cols[match(want, names.all)], drop = FALSE]
+  names(out) <- want
+  out
+}
+
 # ---- distance-to-feature covariates: what terra::distance and terra::gridDist are used for ---------------------------------
 # x: a SpatRaster with square cells.  A cell is a feature where layer `layer` is NA (where = "na": the sea of a land-only DEM),
 # not NA ("valid"), or "lt" "le" "gt" "ge" "eq" "ne" `threshold`.  v: any of "d2" (squared distance in cells, exact), "index"

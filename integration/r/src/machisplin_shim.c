@@ -468,6 +468,29 @@ SEXP mhsr_warp(SEXP geom_src, SEXP planes, SEXP nodata, SEXP geom_dst, SEXP step
     return out;
 }
 
+/* Window statistics of one layer at any radius (machisplin_hip.h "focal"): terra::focal for sums, moments, min and max.  planes,
+ * nodata: as for mhsr_resample; opts: c(layer, shape, fill_na, offset) with layer 0-based, shape 0 square / 1 circle and offset the
+ * constant the values are centred by (NA_real_: 0); radii: 1 .. 8 integers; stats: bit mask (1 count, 2 sum, 4 mean, 8 sd, 16 min,
+ * 32 max, 64 range, 128 minus_mean, 256 above_min, 512 below_max, 1024 dev).  An ncell x (length(radii) * statistics) matrix in terra
+ * cell order, radius after radius, the statistics in ascending bit order.  Runs on the HOST entry point mhs_focal (row bands). */
+SEXP mhsr_focal(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP radii, SEXP stats) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_focal");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 4) Rf_error("mhsr_focal: opts must be c(layer, shape, fill_na, offset)");
+    const double *o = REAL(opts);
+    if (TYPEOF(radii) != INTSXP || Rf_length(radii) < 1 || Rf_length(radii) > MHS_FOCAL_MAX_RADII)
+        Rf_error("mhsr_focal: radii must be 1 .. %d integers", MHS_FOCAL_MAX_RADII);
+    int mask = Rf_asInteger(stats), n = mask_planes(mask), nrad = Rf_length(radii);
+    if (mask == NA_INTEGER || mask < 1 || mask > 2047) Rf_error("mhsr_focal: stats must be a bit mask of 1 count ... 1024 dev");
+    if ((double)g.nrow * (double)g.ncol > 2147483647.0) Rf_error("mhsr_focal: bad dimension");
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)(g.nrow * g.ncol), n * nrad));
+    int rc = mhs_focal(&g, &st, (int)o[0], INTEGER(radii), nrad, (int)o[1], (unsigned)mask, o[2] != 0.0, ISNAN(o[3]) ? 0.0 : o[3], 0, g.nrow, 0, g.ncol,
+                       REAL(out), MHS_F64);
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* Distance to the nearest feature cell (machisplin_hip.h "proximity"): what terra::distance and terra::gridDist are used for.
  * planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, unit) with layer and value_layer 0-based
  * (value_layer is read only for the value product) and where 0 na, 1 valid, 2 lt, 3 le, 4 gt, 5 ge, 6 eq, 7 ne; products: bit

@@ -238,6 +238,10 @@ SIGNATURES = {
     "mhs_warp_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.POINTER(WarpLattice), C.c_int, _vp,
                                _i64, _i64, C.c_int, _vp]),
     "mhs_warp": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.POINTER(Grid), _i64, _i64, _i64, _i64, C.POINTER(WarpLattice), C.c_int, _vp, C.c_int]),
+    "mhs_focal_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_double, _i64, _i64, _i64, _i64,
+                                _vp, C.c_int, _i64, _i64, _vp]),
+    "mhs_focal": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_double, _i64, _i64, _i64, _i64, _vp,
+                            C.c_int]),
     "mhs_proximity_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
                                     C.POINTER(ProximityOut), C.c_int, _i64, _vp, C.POINTER(ProximityInfo)]),
     "mhs_proximity": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,

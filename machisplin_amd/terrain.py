@@ -31,6 +31,7 @@ DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covar
 STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
 FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
+FOCAL_SPEC = {"focal_mean": "mean", "focal_sd": "sd", "tpi_scale": "minus_mean", "dev": "dev"}      # covariates(): spec name -> the statistic of focal
 SOLAR = ("svf", "direct", "sun_hours", "horizon")                   # the products of mhs_solar, in its order; horizon is 16 planes
 # the sixteen ray directions of section "solar", clockwise from north: (rows south, columns east)
 SOLAR_DIRECTIONS = ((-1, 0), (-2, 1), (-1, 1), (-1, 2), (0, 1), (1, 2), (1, 1), (2, 1),
@@ -406,6 +407,10 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       a name of :data:`VARS`                      that 3 x 3 variable (all of them in one pass)
       (a name of :data:`STATS`, radius)           that relief statistic in a window of ``radius`` cells
       ("geomorphon", search[, flat_deg])          the geomorphon code (1 .. 10)
+      ("focal_mean" | "focal_sd" | "tpi_scale" | "dev", radius)
+                                                  mean, sample sd, e - mean and (e - mean) / sd of the SQUARE window of ``radius``
+                                                  cells, any radius up to max(nrow, ncol) (:func:`focal.focal`; one call per
+                                                  distinct radius makes all of its layers)
       "twi"                                       the topographic wetness index (:func:`hydro`, its defaults)
       "log_flowacc"                               log of the flow accumulation, taken by torch on the float64 plane
       "twi_mfd", "log_flowacc_mfd"                the same two with multiple flow direction (:func:`hydro_mfd`, its defaults)
@@ -475,6 +480,16 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
         sv = tuple(dict.fromkeys(e[0] for e in spec if len(e) > 1 and e[0] in sun_names and int(e[1]) == L))
         got = solar(dem_stack, L, sv, sun, layer, lonlat, lat, z_factor, out_dtype=torch.float32)
         by_name.update({(n, L): p for n, p in zip(sv, got)})
+    for e in spec:
+        if e[0] in FOCAL_SPEC and len(e) != 2:
+            raise ValueError(f"{e[0]!r} takes one argument, the radius in cells")
+    if any(e[0] in FOCAL_SPEC for e in spec):
+        from . import focal as _focal
+        off = _focal.default_offset(dem_stack, layer)
+        for R in dict.fromkeys(int(e[1]) for e in spec if e[0] in FOCAL_SPEC):
+            fv = tuple(dict.fromkeys(FOCAL_SPEC[e[0]] for e in spec if e[0] in FOCAL_SPEC and int(e[1]) == R))
+            got = _focal.focal(dem_stack, R, fv, layer, "square", out_dtype=torch.float32, offset=off)
+            by_name.update({(n, R): p for n, p in zip(fv, got)})
     from . import proximity as _prox
     for e in dict.fromkeys(e for e in spec if e[0] in DIST_SPEC):
         by_name[e] = _prox.proximity(dem_stack, layer, DIST_SPEC[e[0]], float(e[1]) if len(e) > 1 else None, "dist", out_dtype=torch.float32)[0]
@@ -484,6 +499,9 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             names.append(e[0] + (f"{float(e[1]):g}" if len(e) > 1 else ""))
         elif len(e) > 1 and e[0] in sun_names:
             planes[1 + k] = by_name[(e[0], int(e[1]))]
+            names.append(f"{e[0]}{int(e[1])}")
+        elif e[0] in FOCAL_SPEC:
+            planes[1 + k] = by_name[(FOCAL_SPEC[e[0]], int(e[1]))]
             names.append(f"{e[0]}{int(e[1])}")
         elif len(e) == 1:
             planes[1 + k] = by_name[e[0]]
