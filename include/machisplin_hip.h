@@ -1129,6 +1129,72 @@ MHS_API int mhs_proximity_dev(const mhs_grid *g, const mhs_stack *stack, int lay
 MHS_API int mhs_proximity(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int value_layer,
                           double unit, const mhs_proximity_out *out, int out_dtype, mhs_proximity_info *info);
 
+/* ------------------------------------------------------------------ patches --
+ * Which cells of a mask belong together: the connected patches of the feature cells, their sizes, and the size filter that
+ * GDAL and SAGA call a sieve.  "proximity" treats every feature cell alike -- a void of three cells on a mountain is as much
+ * "coast" as the ocean; a `keep` plane from here, handed to mhs_proximity* as the feature layer, measures to the patches that
+ * count.  The reference has no such step; its users go to terra::patches (raster::clump) and a size filter.  THE RULE (this
+ * text is the specification; csrc/patches_rule.h holds it as code).
+ *
+ * Grid of nrow x ncol cells, cell number = row * ncol + col.  A call always treats the WHOLE plane -- there is no window,
+ * connectivity is not local.  Nothing is known outside the grid: there are no features there, and no wrap-around.
+ *
+ * FEATURES.  As for "proximity": the value of layer `layer`, converted exactly to double, satisfies `where`, one of the eight
+ * MHS_PROX_* predicates against `threshold`, with their NA semantics.
+ * NEIGHBOURS.  Two feature cells are neighbours under connectivity 4 (N, S, E, W) or 8 (plus the four diagonals).  Any other
+ * value is refused.
+ * PATCHES.  A patch is a connected component of the feature cells under that relation.
+ *
+ * PRODUCTS; any subset, not none.  On a non-feature cell label is -1 and every other product is 0.  On a feature cell:
+ *   label   int32   the smallest cell number in the cell's patch
+ *   id      int32   the dense numbering 1 .. K of the patches in increasing order of label -- the numbering a row-major scan
+ *                   gives (terra::patches, scipy.ndimage.label)
+ *   size    int32   the number of cells in the patch
+ *   edge    uint8   1 where the patch has a cell in the first or last row or column of the grid
+ *   keep    uint8   1 where the patch passes the FILTER: min_size <= size <= max_size, and edge_rule -- MHS_PATCH_EDGE_ANY: no
+ *                   condition; MHS_PATCH_EDGE_TOUCHING: edge = 1; MHS_PATCH_EDGE_INTERIOR: edge = 0.  1 <= min_size <= max_size;
+ *                   max_size = INT64_MAX (anything >= nrow * ncol) is "no limit".
+ * Everything is an integer: every plane equals a restatement bit for bit, and a repeated call gives the same bytes.
+ *
+ * INFO: the number of feature cells, of patches, of patches that pass the filter and of their cells, the largest patch's
+ * size (0 without a feature), and the bytes of device scratch.  The counts are made whenever info is given.
+ *
+ * OUT OF SCOPE: patches of equal value (terra::patches(values = TRUE)); zonal statistics of another layer per patch (float
+ * sums need a fixed order); wrap-around at the date line; more than 2^31 - 1 cells.
+ *
+ * LIMITS, checked with every other argument before the first device call (MHS_ERR_INVALID, the message names the argument):
+ * nrow * ncol <= INT32_MAX (label is an int32).
+ *
+ * The algorithm (csrc/patches.hip) is a block-based union-find on the label plane, every phase its own launch:
+ * tiles of 32 x 64 cells joined in LDS, the tile borders merged by lock-free atomicMin links from the larger root to the
+ * smaller, a flatten, integer counts per root, a blocked prefix sum over the roots for the ids, one pass for the products.
+ * Every word of the label plane holds -1 or a cell number <= its own index at every moment, so no find loop can cycle.
+ * Scratch: at most 12 bytes per cell of stream-ordered device memory for the length of the call (the label plane 4 -- none
+ * when label is requested with ld = ncol, it is then written in place --, the count table 4, the id table 4; each only when
+ * a product needs it), plus 4 bytes per 2 048 cells, one counter block and 256-byte alignments; MHS_ERR_ALLOC if there is none. */
+enum { MHS_PATCH_EDGE_ANY = 0, MHS_PATCH_EDGE_TOUCHING, MHS_PATCH_EDGE_INTERIOR };
+typedef struct mhs_patches_out {   /* the planes to make; any may be NULL, not all */
+    int32_t *label, *id, *size;
+    uint8_t *edge, *keep;
+} mhs_patches_out;
+typedef struct mhs_patches_info {
+    int64_t n_features;       /* cells that satisfy `where` */
+    int64_t n_patches;        /* K */
+    int64_t n_kept_patches;   /* patches that pass the filter */
+    int64_t n_kept_cells;     /* ... and their cells: the cells at which keep is 1 */
+    int64_t max_size;         /* the largest patch's size; 0 without a feature */
+    int64_t scratch_bytes;    /* the call's block of device scratch */
+} mhs_patches_info;
+/* DEVICE planes: stack->data covers the whole grid; every plane of `out` is nrow x ld row-major on the device.  Only enqueues
+ * on `stream` -- unless info is given: then the stream is synchronised once, behind the last kernel, to read the counts. */
+MHS_API int mhs_patches_dev(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int connectivity,
+                            int64_t min_size, int64_t max_size, int edge_rule, const mhs_patches_out *out, int64_t ld, void *stream,
+                            mhs_patches_info *info);
+/* same, HOST planes: stack->data and the planes of `out` (nrow x ncol dense) on the host -- what the R shim hands over.  The
+ * whole plane goes up in one piece and the requested planes come down; no row bands.  Blocks until done. */
+MHS_API int mhs_patches(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int connectivity,
+                        int64_t min_size, int64_t max_size, int edge_rule, const mhs_patches_out *out, mhs_patches_info *info);
+
 /* --------------------------------------------------------------- flow paths --
  * Drainage covariates ALONG the flow: height above and distance to the first channel cell that a cell's own water meets (HAND,
  * SAGA's vertical / horizontal distance to channel network), and the basin a cell drains to.  "proximity" takes the stream cell

@@ -385,6 +385,44 @@ mhs_proximity <- function(x, where = "na", threshold = NA_real_, v = "dist", lay
   r
 }
 
+# ---- connected patches of a mask: what terra::patches and a size filter (a sieve) are used for ------------------------------
+# x: a SpatRaster.  A cell is a feature by `where` and `threshold` as for mhs_proximity (default "valid": the cells that are not
+# NA).  Two feature cells are neighbours under directions = 4 or 8 (terra::patches' name for it).  v: any of "label" (the cell
+# number of the patch's first cell, NA off the features), "id" (1 .. K in that order: terra::patches' numbering; 0 off the
+# features), "size", "edge" (1 where the patch touches the raster's edge) and "keep" (1 where min.size <= size <= max.size and
+# the patch meets edge = "any", "touching" or "interior").  mhs_proximity(r[["keep"]], where = "ne", threshold = 0) then measures
+# to the patches that were kept.  Section "patches" of machisplin_hip.h states the rule; patches of equal value, zonal
+# statistics and wrap-around at the date line are out of scope.
+.mhs_patches_products <- c("label", "id", "size", "edge", "keep")
+.mhs_patches_edge <- c("any", "touching", "interior")
+mhs_patches <- function(x, where = "valid", threshold = NA_real_, directions = 8L, v = "id", min.size = 1, max.size = Inf, edge = "any",
+                        layer = 1L) {
+  w <- match(where, .mhs_proximity_where)
+  if (length(where) != 1L || is.na(w)) stop("mhs_patches: where must be one of ", paste(.mhs_proximity_where, collapse = ", "))
+  if (w > 2L && is.na(threshold)) stop("mhs_patches: where = \"", where, "\" needs a threshold")
+  if (length(directions) != 1L || !(directions %in% c(4, 8))) stop("mhs_patches: directions must be 4 or 8")
+  bad <- setdiff(v, .mhs_patches_products)
+  if (length(bad) || !length(v)) stop("mhs_patches: v must name some of ", paste(.mhs_patches_products, collapse = ", "))
+  if (is.na(min.size) || min.size < 1 || min.size != floor(min.size)) stop("mhs_patches: min.size must be a whole number >= 1")
+  if (is.na(max.size) || max.size < min.size) stop("mhs_patches: max.size must not be below min.size")
+  e <- match(edge, .mhs_patches_edge)
+  if (length(edge) != 1L || is.na(e)) stop("mhs_patches: edge must be one of ", paste(.mhs_patches_edge, collapse = ", "))
+  v <- unique(v)
+  pv <- match(v, .mhs_patches_products)
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  out <- .Call("mhsr_patches", .mhs_geom(x), vals, NA_real_,
+               c(layer - 1, w - 1, if (w > 2L) threshold else 0, directions, min.size, max.size, e - 1),
+               as.integer(sum(2^(pv - 1))))
+  layers <- lapply(seq_along(v), function(j) {
+    r <- terra::setValues(terra::rast(x[[1]]), out[[pv[j]]])
+    names(r) <- v[j]
+    r
+  })
+  r <- do.call(c, layers)
+  attr(r, "info") <- stats::setNames(out[[6]], c("n_features", "n_patches", "n_kept_patches", "n_kept_cells", "max_size"))
+  r
+}
+
 # ---- flow-path covariates: HAND, SAGA's vertical / horizontal distance to channel network, catchment labels ------------------
 # flowdir: the one-layer SpatRaster of D8 directions that the hydrology call makes (0 .. 7 = E, SE, S, SW, W, NW, N, NE, -1 the
 # water leaves, NA).  x: a SpatRaster on the same grid whose layer `layer` defines the targets -- `where` as for mhs_proximity,

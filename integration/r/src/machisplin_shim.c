@@ -535,6 +535,59 @@ SEXP mhsr_proximity(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP product
     return out;
 }
 
+/* Connected patches of the feature cells (machisplin_hip.h "patches"): what terra::patches and a size filter (a sieve) are used
+ * for.  planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, connectivity, min_size, max_size, edge_rule) with
+ * layer 0-based, where 0 .. 7 as for mhsr_proximity, connectivity 4 or 8, max_size NA or Inf = no limit, edge_rule 0 any,
+ * 1 touching, 2 interior; products: bit mask (1 label, 2 id, 4 size, 8 edge, 16 keep).  Returns list(label, id, size, edge, keep,
+ * info) in terra cell order, NULL where a plane was not asked for, all integer vectors: label the terra cell NUMBER (1-based) of
+ * the patch's first cell, NA_integer_ at a non-feature cell, the others 0 there; info = c(n_features, n_patches, n_kept_patches,
+ * n_kept_cells, max_size).  Runs on the HOST entry point: the whole plane goes up, there are no row bands. */
+SEXP mhsr_patches(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP products) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_patches");
+    int mask = Rf_asInteger(products);
+    if (mask == NA_INTEGER || mask < 1 || mask > 31) Rf_error("mhsr_patches: products must be a bit mask of 1 label, 2 id, 4 size, 8 edge, 16 keep");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 7)
+        Rf_error("mhsr_patches: opts must be c(layer, where, threshold, connectivity, min_size, max_size, edge_rule)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_patches: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 7.0)) Rf_error("mhsr_patches: where must be 0 .. 7");
+    if (!(o[3] == 4.0 || o[3] == 8.0)) Rf_error("mhsr_patches: connectivity must be 4 or 8");
+    if (!(o[4] >= 1.0 && o[4] <= 2147483647.0)) Rf_error("mhsr_patches: min_size must be a whole number of cells >= 1");
+    if (!(o[6] >= 0.0 && o[6] <= 2.0)) Rf_error("mhsr_patches: edge_rule must be 0 any, 1 touching or 2 interior");
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_patches: bad grid dimension");
+    int64_t max_size = (ISNAN(o[5]) || o[5] >= 2147483647.0) ? INT64_MAX : o[5] < 1.0 ? 0 : (int64_t)o[5];       /* below min_size: the library refuses */
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 6));
+    SEXP plane[5] = { R_NilValue, R_NilValue, R_NilValue, R_NilValue, R_NilValue };
+    uint8_t *byte[5] = { NULL, NULL, NULL, NULL, NULL };
+    int n_protect = 1;
+    for (int k = 0; k < 5; ++k)
+        if (mask & (1 << k)) {
+            plane[k] = PROTECT(Rf_allocVector(INTSXP, n)); ++n_protect;
+            if (k >= 3) byte[k] = (uint8_t *)R_alloc((size_t)n, 1);                            /* edge and keep come down as bytes */
+        }
+    mhs_patches_out po = { (mask & 1) ? (int32_t *)INTEGER(plane[0]) : NULL, (mask & 2) ? (int32_t *)INTEGER(plane[1]) : NULL,
+                           (mask & 4) ? (int32_t *)INTEGER(plane[2]) : NULL, byte[3], byte[4] };
+    mhs_patches_info info = { 0 };
+    int rc = mhs_patches(&g, &st, (int)o[0], (int)o[1], o[2], (int)o[3], (int64_t)o[4], max_size, (int)o[6], &po, &info);
+    if (rc == MHS_OK) {
+        if (mask & 1)
+            for (R_xlen_t k = 0; k < n; ++k) INTEGER(plane[0])[k] = INTEGER(plane[0])[k] < 0 ? NA_INTEGER : INTEGER(plane[0])[k] + 1;
+        for (int j = 3; j < 5; ++j)
+            if (byte[j])
+                for (R_xlen_t k = 0; k < n; ++k) INTEGER(plane[j])[k] = byte[j][k];
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 5)); ++n_protect;
+        REAL(inf)[0] = (double)info.n_features; REAL(inf)[1] = (double)info.n_patches; REAL(inf)[2] = (double)info.n_kept_patches;
+        REAL(inf)[3] = (double)info.n_kept_cells; REAL(inf)[4] = (double)info.max_size;
+        for (int k = 0; k < 5; ++k) SET_VECTOR_ELT(out, k, plane[k]);
+        SET_VECTOR_ELT(out, 5, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* Along the D8 flow paths (machisplin_hip.h "flow paths"): height above and distance to the first target cell a cell's own water
  * meets, catchment labels.  flowdir: the integer vector mhsr_hydro returns (0 .. 7, -1 the water leaves, NA_integer_ at NA
  * cells), one per cell; planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, flags, dx, dy) with

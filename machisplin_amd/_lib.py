@@ -109,6 +109,17 @@ class ProximityInfo(C.Structure):
     _fields_ = [("n_features", C.c_int64), ("max_d2", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class PatchesOut(C.Structure):
+    """struct mhs_patches_out"""
+    _fields_ = [("label", C.c_void_p), ("id", C.c_void_p), ("size", C.c_void_p), ("edge", C.c_void_p), ("keep", C.c_void_p)]
+
+
+class PatchesInfo(C.Structure):
+    """struct mhs_patches_info"""
+    _fields_ = [("n_features", C.c_int64), ("n_patches", C.c_int64), ("n_kept_patches", C.c_int64), ("n_kept_cells", C.c_int64),
+                ("max_size", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 class FlowpathOut(C.Structure):
     """struct mhs_flowpath_out"""
     _fields_ = [("index", C.c_void_p), ("steps", C.c_void_p), ("dist", C.c_void_p), ("value", C.c_void_p), ("drop", C.c_void_p)]
@@ -246,6 +257,10 @@ SIGNATURES = {
                                     C.POINTER(ProximityOut), C.c_int, _i64, _vp, C.POINTER(ProximityInfo)]),
     "mhs_proximity": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
                                 C.POINTER(ProximityOut), C.c_int, C.POINTER(ProximityInfo)]),
+    "mhs_patches_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, _i64, _i64, C.c_int,
+                                  C.POINTER(PatchesOut), _i64, _vp, C.POINTER(PatchesInfo)]),
+    "mhs_patches": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, _i64, _i64, C.c_int,
+                              C.POINTER(PatchesOut), C.POINTER(PatchesInfo)]),
     "mhs_flowpath_dev": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.POINTER(FlowpathOut), C.c_int, _i64, _vp, C.POINTER(FlowpathInfo)]),
     "mhs_flowpath": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,

@@ -29,6 +29,7 @@ HYDRO_MFD = ("filled", "flowacc", "twi")                            # the planes
 HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True)}      # the same, made by hydro_mfd at its defaults
 DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covariates(): spec name -> the predicate of proximity
 STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
+PATCH_DIST_SPEC = {"dist_na_edge": ("na", 0), "dist_na_min": ("na", 1), "dist_le_min": ("le", 2)}      # covariates(): spec name -> the predicate of patches, its arguments
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
 FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
 FOCAL_SPEC = {"focal_mean": "mean", "focal_sd": "sd", "tpi_scale": "minus_mean", "dev": "dev"}      # covariates(): spec name -> the statistic of focal
@@ -420,6 +421,11 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       "dist_na"                                   distance to the nearest NA cell of the DEM -- the sea, for a land-only DEM
                                                   (:func:`proximity.proximity`, in the geometry's cell width; square cells)
       ("dist_le" | "dist_ge", t)                  distance to the nearest cell whose elevation is <= t / >= t
+      "dist_na_edge"                              distance to the nearest NA cell whose 8-connected patch of NA cells touches
+                                                  the raster's edge (:func:`patches.sieve`, then proximity on that mask): the
+                                                  sea without the voids and masked lakes inland
+      ("dist_na_min", n)                          distance to the nearest NA cell in a patch of at least ``n`` NA cells
+      ("dist_le_min", t, n)                       distance to the nearest cell <= t in a patch of at least ``n`` such cells
       ("dist_stream", A)                          distance to the nearest cell whose D8 ``flowacc`` is >= A (the one
                                                   :func:`hydro` call that makes ``twi`` / ``log_flowacc`` serves these too)
       ("above_stream", A)                         the DEM minus the DEM at that nearest stream cell, in elevation units:
@@ -454,10 +460,16 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             raise ValueError(f"{e[0]!r} takes one argument, the flow accumulation from which a cell is a stream")
         if e[0] in DIST_SPEC and len(e) != (1 if e[0] == "dist_na" else 2):
             raise ValueError(f"{e[0]!r} takes {'no argument' if e[0] == 'dist_na' else 'one threshold'}")
+        if e[0] in PATCH_DIST_SPEC:
+            n_args = PATCH_DIST_SPEC[e[0]][1]
+            if len(e) != 1 + n_args or (n_args and (int(e[-1]) != e[-1] or int(e[-1]) < 1)):
+                raise ValueError(f"{e[0]!r} takes " + ("no argument", "one argument, the smallest patch in cells (a whole number >= 1)",
+                                                       "a threshold and the smallest patch in cells (a whole number >= 1)")[n_args])
     stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
     flow_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in FLOW_SPEC))
     flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec)
-    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC and e[0] != FLOW_OUTLET]
+    tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC and e[0] != FLOW_OUTLET
+          and e[0] not in PATCH_DIST_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
@@ -493,8 +505,23 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     from . import proximity as _prox
     for e in dict.fromkeys(e for e in spec if e[0] in DIST_SPEC):
         by_name[e] = _prox.proximity(dem_stack, layer, DIST_SPEC[e[0]], float(e[1]) if len(e) > 1 else None, "dist", out_dtype=torch.float32)[0]
+    patch_specs = list(dict.fromkeys(e for e in spec if e[0] in PATCH_DIST_SPEC))
+    if patch_specs:
+        from . import patches as _patches
+        g = dem_stack.geom
+        if abs(g.xres - g.yres) > 1e-9 * max(abs(g.xres), abs(g.yres)):
+            raise ValueError(f"{patch_specs[0][0]!r}: the cells are not square (xres {g.xres}, yres {g.yres}); bring the raster onto a square "
+                             "grid with resample.resample")
+        for e in patch_specs:
+            where, n_args = PATCH_DIST_SPEC[e[0]]
+            keep = _patches.sieve(dem_stack, layer, where, float(e[1]) if n_args == 2 else None, 8, min_size=int(e[-1]) if n_args else 1,
+                                  edge="any" if n_args else "touching")
+            by_name[e] = _prox.proximity(keep, products="dist", unit=g.xres, out_dtype=torch.float32)[0]
     for k, e in enumerate(spec):
-        if e[0] in DIST_SPEC or e[0] in STREAM_SPEC or e[0] in FLOW_SPEC:
+        if e[0] in PATCH_DIST_SPEC:
+            planes[1 + k] = by_name[e]
+            names.append(e[0] if len(e) == 1 else f"{e[0]}{int(e[1])}" if len(e) == 2 else f"dist_le{float(e[1]):g}_min{int(e[2])}")
+        elif e[0] in DIST_SPEC or e[0] in STREAM_SPEC or e[0] in FLOW_SPEC:
             planes[1 + k] = by_name[e if e[0] in DIST_SPEC else (e[0], float(e[1]))]
             names.append(e[0] + (f"{float(e[1]):g}" if len(e) > 1 else ""))
         elif len(e) > 1 and e[0] in sun_names:
