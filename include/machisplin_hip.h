@@ -1159,8 +1159,8 @@ MHS_API int mhs_proximity(const mhs_grid *g, const mhs_stack *stack, int layer, 
  * INFO: the number of feature cells, of patches, of patches that pass the filter and of their cells, the largest patch's
  * size (0 without a feature), and the bytes of device scratch.  The counts are made whenever info is given.
  *
- * OUT OF SCOPE: patches of equal value (terra::patches(values = TRUE)); zonal statistics of another layer per patch (float
- * sums need a fixed order); wrap-around at the date line; more than 2^31 - 1 cells.
+ * OUT OF SCOPE: patches of equal value (terra::patches(values = TRUE)); wrap-around at the date line; more than 2^31 - 1 cells.
+ * The statistics of another layer per patch are section "zonal" below: a label or id plane from here is a zone plane.
  *
  * LIMITS, checked with every other argument before the first device call (MHS_ERR_INVALID, the message names the argument):
  * nrow * ncol <= INT32_MAX (label is an int32).
@@ -1194,6 +1194,121 @@ MHS_API int mhs_patches_dev(const mhs_grid *g, const mhs_stack *stack, int layer
  * whole plane goes up in one piece and the requested planes come down; no row bands.  Blocks until done. */
 MHS_API int mhs_patches(const mhs_grid *g, const mhs_stack *stack, int layer, int where, double threshold, int connectivity,
                         int64_t min_size, int64_t max_size, int edge_rule, const mhs_patches_out *out, mhs_patches_info *info);
+
+/* -------------------------------------------------------------------- zonal --
+ * The statistics of one layer inside each ZONE of an integer zone plane, and those statistics put back on the cells: what
+ * terra::zonal is used for -- basin mean elevation, a cell's height relative to its basin, the mean elevation of a lake or a
+ * plateau patch.  Zone planes are made by "patches" (label, id), by "flow paths" (index with MHS_FLOWPATH_OUTLET: drainage
+ * basins), or are a land-cover or administrative raster.  The reference has no such step.  THE RULE (this text is the
+ * specification; csrc/zonal_rule.h holds it as code).  Every accumulator is an EXACT INTEGER, so no result depends on the order
+ * in which the cells are added: every table and plane equals a numpy and Python-int restatement bit for bit, and a repeated
+ * call gives the same bytes.
+ *
+ * INPUT.  Layer `layer` of an mhs_stack (float64, float32 or int16, converted exactly to double; NA = NaN or the stack's
+ * nodata), and an int32 ZONE PLANE `zones` of the same nrow x ncol with the row stride ld_zones; nrow * ncol <= 2^31 - 1.  A
+ * call always treats the whole plane.  A cell BELONGS to zone z when 0 <= z < n_zones.  A negative zone is "no zone" (label -1
+ * off the features, an unreached cell of "flow paths").  A zone >= n_zones is MHS_ERR_INVALID naming n_zones: a device flag
+ * finds it before any table or plane is written, and nothing is written.  n_zones = 0: the library measures max(zone) + 1
+ * itself.  A cell CONTRIBUTES its value when it belongs to a zone and the value is not NA and finite; +-Inf is counted in the
+ * info (n_nonfinite, over the cells with a zone) and otherwise treated as NA.
+ *
+ * QUANTISATION.  Statistics are taken of q = rint(v / quantum), round half to even, quantum a power of two in 2^-1022 .. 2^1023.
+ * Every valid finite value of the LAYER (with a zone or not) must satisfy |v| <= 2^30 * quantum, so |q| <= 2^30; a given
+ * quantum that does not is MHS_ERR_INVALID naming quantum.  quantum = 0: the library takes the smallest power of two (not
+ * below 2^-1022) with max|v| <= 2^30 * quantum over the layer's valid finite cells -- a device max-reduction, read back by the
+ * host; it is 1 for an int16 layer (not measured) and for a layer without a nonzero value.  The info returns the quantum used
+ * and n_inexact, the number of contributing cells with q * quantum != v.  When n_inexact is 0 the statistics are those of the
+ * input itself: every int16 plane, and float32 planes whose values stay within a factor of about 2^7 of the largest magnitude
+ * (there every ulp is at least the quantum).  v / quantum and q * quantum are exact scalings.
+ *
+ * ACCUMULATORS per zone: cells (every cell of the zone, NA-valued ones included) and n (the contributing cells), uint32;
+ * S1 = sum q, int64 (at most 2^31 * 2^30); S2 = sum q^2 as TWO uint64 words, L = the sum of the low 32 bits of each q^2 and H =
+ * the sum of the bits above them, S2 = H * 2^32 + L as a 128-bit integer (neither word can overflow; the words are combined,
+ * never carried); qmin, qmax, int32.
+ *
+ * STATISTICS, bit k of a mask; every line fixes the operations, each rounded once:
+ *      0 count       n                                           6 range        max - min
+ *      1 sum         (double)S1 * quantum                        7 minus_mean   q * quantum - mean
+ *      2 mean        ((double)S1 / (double)n) * quantum          8 above_min    q * quantum - min
+ *      3 sd          sqrt(D(n * S2 - S1 * S1) / ((double)n * (double)(n - 1))) * quantum;  NA where n < 2
+ *      4 min         qmin * quantum                              9 below_max    max - q * quantum
+ *      5 max         qmax * quantum                             10 dev          minus_mean / sd;  NA where sd is NA or 0
+ *     11 cells       cells
+ *   n * S2 - S1 * S1 is an exact integer, non-negative and at most 123 bits wide; D(x) = (double)(uint64)(x >> 64) * 2^64 +
+ *   (double)(uint64)x.  Nothing cancels in sd, so no offset is needed.  n = 0 gives count 0 and NA elsewhere.  Bits 7 .. 10
+ *   exist only as planes and are NA at a cell that does not contribute.  NA is NaN.  A float32 output is the float64 value
+ *   rounded once.
+ *   SUM AND MEAN AGAINST FLOAT ARITHMETIC.  With n_inexact = 0, S1 * quantum is the exact sum of the zone's values rounded
+ *   once: |sum - exact| <= u |exact|, u = 2^-53, and mean carries two more roundings: |mean - exact / n| <= 3.01 u |exact / n|.
+ *   A float64 summation of the same values in any order is itself within (n - 1) u / (1 - (n - 1) u) of the sum of their
+ *   magnitudes.
+ *
+ * OUTPUTS; each is optional, a call must ask for at least one of table, planes, info.
+ *   TABLE, float64 (count and cells int64); a non-NULL array selects its statistic; every array holds `capacity` rows.
+ *     DENSE (zone = NULL): row z is zone z, n_zones rows; n_zones > capacity is MHS_ERR_INVALID naming capacity.
+ *     PRESENT (zone != NULL; needs info): only the zones with cells > 0, in increasing zone number, their numbers in `zone`,
+ *     K = info->n_present rows; K > capacity is MHS_ERR_INVALID naming capacity (capacity = min(n_zones, nrow * ncol) always
+ *     suffices).  This is the form for cell-number labels, where n_zones = nrow * ncol.
+ *   PLANES, plane[k] for bit k, nrow x ld[k], of dtype MHS_F32 or MHS_F64 (count and cells: int32).  A cell receives its own
+ *     zone's statistic (bits 0 .. 6, 11) or its own value against it (7 .. 10); a cell without a zone gets NA (0 for count and
+ *     cells).
+ *   INFO: n_zones, n_present (zones with cells > 0), n_cells_in_zones, n_contributing, n_nonfinite, n_inexact, quantum,
+ *     scratch_bytes.
+ *
+ * flags: MHS_ZONAL_NO_STRIP flushes the accumulate kernel's LDS table after every tile (a diagnostic: the results are the same).
+ *
+ * LIMITS, checked with every other argument before the first device call (MHS_ERR_INVALID, the message names the argument):
+ * nrow * ncol <= INT32_MAX, 0 <= n_zones <= INT32_MAX, quantum 0 or a power of two, the layer in range, ld_zones >= ncol, each
+ * requested plane's ld >= ncol, the planes' dtype, capacity >= 0, no unknown bit in flags, some output.
+ *
+ * OUT OF SCOPE: median and mode per zone; zones given as floats; more than 2^31 - 1 cells; weights (the area of a cell on a
+ * lon/lat grid).
+ *
+ * The algorithm (csrc/zonal.hip), every phase its own launch, a kernel boundary the only ordering: (1) range and
+ * zone check: max|v|, max(zone), the +-Inf count -- skipped when quantum and n_zones are given and info is NULL; (2) accumulate:
+ * a workgroup of four waves per strip of 8 tiles of 32 x 64 cells, a wave per row at a time; the work is done per RUN of equal
+ * zone along the row by a segmented wave scan, and the run's last lane adds the run's totals to a table of 256 slots in LDS
+ * keyed by zone (one compare-and-swap claims a key, at most 4 probes, integer LDS atomics), or straight to the global table when
+ * it finds no slot; the occupied slots are flushed at the strip's end, one global integer atomic per accumulator; (3) finalise, a
+ * lane per zone slot; (4) the present zones: flags, a blocked prefix sum, a compaction; (5) planes, a lane per cell.
+ * SCRATCH, stream-ordered memory given back behind the last kernel: one block of at most 40 bytes per zone slot for the integer
+ * accumulators (only those a requested statistic needs) plus 8 per float64 statistic that a plane or a present table reads,
+ * 4 bytes per 2 048 zone slots and 256-byte alignments; and a counter block of 256 bytes.  MHS_ERR_ALLOC if there is none. */
+#define MHS_ZONAL_N_STATS 12
+#define MHS_ZONAL_NO_STRIP 1
+typedef struct mhs_zonal_table {
+    int64_t capacity;          /* rows that every array below holds */
+    int32_t *zone;             /* NULL: dense.  Else the present form: the zone number of each row */
+    int64_t *count;            /* bit 0 */
+    double *sum, *mean, *sd, *min, *max, *range;   /* bits 1 .. 6 */
+    int64_t *cells;            /* bit 11 */
+} mhs_zonal_table;
+typedef struct mhs_zonal_planes {
+    void *plane[MHS_ZONAL_N_STATS];      /* by bit; NULL: not wanted */
+    int64_t ld[MHS_ZONAL_N_STATS];       /* the row stride of each, in elements */
+    int dtype;                           /* MHS_F64 or MHS_F32; planes 0 and 11 are int32 */
+} mhs_zonal_planes;
+typedef struct mhs_zonal_info {
+    int64_t n_zones;           /* as given, or max(zone) + 1 */
+    int64_t n_present;         /* zones with cells > 0 */
+    int64_t n_cells_in_zones;
+    int64_t n_contributing;
+    int64_t n_nonfinite;       /* cells with a zone whose value is +-Inf */
+    int64_t n_inexact;         /* contributing cells with q * quantum != v */
+    double quantum;            /* the quantum used */
+    int64_t scratch_bytes;     /* the call's device scratch */
+} mhs_zonal_info;
+/* DEVICE planes: stack->data and zones cover the whole grid; the table's arrays and the planes are on the device.  The stream
+ * is synchronised once behind phase 1 where that runs (the host reads max|v| and max(zone)), and once behind the last kernel
+ * when info is given or phase 1 was skipped (the device flag is read). */
+MHS_API int mhs_zonal_dev(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t ld_zones, int64_t n_zones,
+                          double quantum, int flags, const mhs_zonal_table *table, const mhs_zonal_planes *planes, void *stream,
+                          mhs_zonal_info *info);
+/* same, HOST planes: stack->data, zones (nrow x ncol dense), the table's arrays and the planes (nrow x ncol dense; ld is not
+ * looked at) on the host -- what the R shim hands over.  The layer and the zone plane go up in one piece, the table's rows and
+ * the planes come down.  Blocks until done. */
+MHS_API int mhs_zonal(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t n_zones, double quantum, int flags,
+                      const mhs_zonal_table *table, const mhs_zonal_planes *planes, mhs_zonal_info *info);
 
 /* --------------------------------------------------------------- flow paths --
  * Drainage covariates ALONG the flow: height above and distance to the first channel cell that a cell's own water meets (HAND,

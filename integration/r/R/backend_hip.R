@@ -391,8 +391,8 @@ mhs_proximity <- function(x, where = "na", threshold = NA_real_, v = "dist", lay
 # number of the patch's first cell, NA off the features), "id" (1 .. K in that order: terra::patches' numbering; 0 off the
 # features), "size", "edge" (1 where the patch touches the raster's edge) and "keep" (1 where min.size <= size <= max.size and
 # the patch meets edge = "any", "touching" or "interior").  mhs_proximity(r[["keep"]], where = "ne", threshold = 0) then measures
-# to the patches that were kept.  Section "patches" of machisplin_hip.h states the rule; patches of equal value, zonal
-# statistics and wrap-around at the date line are out of scope.
+# to the patches that were kept.  Section "patches" of machisplin_hip.h states the rule; patches of equal value and wrap-around
+# at the date line are out of scope; the statistics of another layer per patch are mhs_zonal below.
 .mhs_patches_products <- c("label", "id", "size", "edge", "keep")
 .mhs_patches_edge <- c("any", "touching", "interior")
 mhs_patches <- function(x, where = "valid", threshold = NA_real_, directions = 8L, v = "id", min.size = 1, max.size = Inf, edge = "any",
@@ -421,6 +421,52 @@ mhs_patches <- function(x, where = "valid", threshold = NA_real_, directions = 8
   r <- do.call(c, layers)
   attr(r, "info") <- stats::setNames(out[[6]], c("n_features", "n_patches", "n_kept_patches", "n_kept_cells", "max_size"))
   r
+}
+
+# ---- zonal statistics: what terra::zonal is used for, and the statistics put back on the cells --------------------------------
+# x: a SpatRaster whose layer `layer` holds the values.  z: a one-layer SpatRaster of whole zone numbers >= 0 on the same grid --
+# mhs_patches(v = "id") (its 0 off the features is then a zone of its own: subtract 1 or mask it), the "index" layer of
+# mhs_flowpath(where = "outlet"), a land-cover raster; NA or a negative number = no zone.  stats: the table's statistics, any of
+# count sum mean sd min max range cells (NULL: no table); planes: the statistics wanted on the cells, any of those and
+# minus_mean above_min below_max dev.  present = TRUE gives only the zones that have a cell (the form for cell-number labels).
+# n.zones = NULL and quantum = NULL leave both to the library.  Returns list(table = a data.frame with the column zone, planes = a
+# SpatRaster or NULL, info).  Section "zonal" of machisplin_hip.h states the rule: the values are quantised to whole multiples of
+# `quantum`, a power of two, and every sum is an exact integer; info[["n_inexact"]] = 0 says the statistics are those of the
+# input itself.  Median and mode, zones given as fractions and cell-area weights are out of scope.
+.mhs_zonal_stats <- c("count", "sum", "mean", "sd", "min", "max", "range", "minus_mean", "above_min", "below_max", "dev", "cells")
+.mhs_zonal_table <- c("count", "sum", "mean", "sd", "min", "max", "range", "cells")
+mhs_zonal <- function(x, z, stats = "mean", planes = NULL, present = TRUE, n.zones = NULL, quantum = NULL, layer = 1L) {
+  if (length(setdiff(stats, .mhs_zonal_table))) stop("mhs_zonal: stats must name some of ", paste(.mhs_zonal_table, collapse = ", "))
+  if (length(setdiff(planes, .mhs_zonal_stats))) stop("mhs_zonal: planes must name some of ", paste(.mhs_zonal_stats, collapse = ", "))
+  if (!length(stats) && !length(planes)) stop("mhs_zonal: no output: stats and planes are both empty")
+  if (terra::ncell(z) != terra::ncell(x) || terra::ncol(z) != terra::ncol(x)) stop("mhs_zonal: shape mismatch: z is not on the grid of x")
+  if (!is.null(n.zones) && (is.na(n.zones) || n.zones < 1 || n.zones > 2147483647)) stop("mhs_zonal: n.zones must be in 1 .. 2^31 - 1")
+  if (!is.null(quantum) && (is.na(quantum) || quantum <= 0 || log2(quantum) != floor(log2(quantum)))) stop("mhs_zonal: quantum must be a power of two")
+  stats <- unique(stats); planes <- unique(planes)
+  zv <- terra::values(z[[1]])[, 1]
+  if (any(zv != floor(zv), na.rm = TRUE)) stop("mhs_zonal: zones given as fractions are out of scope")
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  bits <- function(v) as.integer(sum(2^(match(v, .mhs_zonal_stats) - 1)))
+  out <- .Call("mhsr_zonal", .mhs_geom(x), vals, NA_real_, as.integer(zv),
+               c(layer - 1, if (is.null(n.zones)) 0 else n.zones, if (is.null(quantum)) 0 else quantum, as.numeric(isTRUE(present))),
+               bits(stats), bits(planes))
+  table <- NULL
+  if (length(stats)) {
+    cols <- stats::setNames(out[[1]][1L + match(stats, .mhs_zonal_table)], stats)
+    zone <- if (isTRUE(present)) out[[1]][[1]] else seq_along(cols[[1]]) - 1L
+    table <- data.frame(zone = zone, cols)
+  }
+  r <- NULL
+  if (length(planes)) {
+    layers <- lapply(planes, function(p) {
+      l <- terra::setValues(terra::rast(x[[1]]), out[[2]][[match(p, .mhs_zonal_stats)]])
+      names(l) <- p
+      l
+    })
+    r <- do.call(c, layers)
+  }
+  list(table = table, planes = r,
+       info = stats::setNames(out[[3]], c("n_zones", "n_present", "n_cells_in_zones", "n_contributing", "n_nonfinite", "n_inexact", "quantum")))
 }
 
 # ---- flow-path covariates: HAND, SAGA's vertical / horizontal distance to channel network, catchment labels ------------------

@@ -588,6 +588,95 @@ SEXP mhsr_patches(SEXP geom, SEXP planes, SEXP nodata, SEXP opts, SEXP products)
     return out;
 }
 
+/* Zonal statistics (machisplin_hip.h "zonal"): what terra::zonal is used for, and the statistics put back on the cells.  planes,
+ * nodata: as for mhsr_resample; zones: an integer vector of one zone number per cell in terra cell order, NA_integer_ or a
+ * negative number = no zone; opts: c(layer, n_zones, quantum, present) with layer 0-based, n_zones 0 = max(zone) + 1, quantum 0 =
+ * the library's choice, present 1 = only the zones that have a cell; stats: bit mask of the table's statistics (1 count, 2 sum,
+ * 4 mean, 8 sd, 16 min, 32 max, 64 range, 2048 cells), 0 for no table; planes_mask: bit mask of the planes (those and 128
+ * minus_mean, 256 above_min, 512 below_max, 1024 dev), 0 for none.  Returns list(table, planes, info): table = list(zone, count,
+ * sum, mean, sd, min, max, range, cells), numeric vectors of one row per zone (zone: integer, NULL for a dense table), NULL where
+ * not asked for; planes = a list of 12 by bit number, numeric (count and cells integer), NULL where not asked for; info =
+ * c(n_zones, n_present, n_cells_in_zones, n_contributing, n_nonfinite, n_inexact, quantum).  Runs on the HOST entry point: the
+ * layer and the zone plane go up whole.  A dense table whose n_zones is to be measured costs a first call for the info. */
+SEXP mhsr_zonal(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP opts, SEXP stats, SEXP planes_mask) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_zonal");
+    int ts = Rf_asInteger(stats), ps = Rf_asInteger(planes_mask);
+    if (ts == NA_INTEGER || ts < 0 || (ts & ~0x87f)) Rf_error("mhsr_zonal: stats must be a bit mask of 1 count, 2 sum, 4 mean, 8 sd, 16 min, 32 max, 64 range, 2048 cells");
+    if (ps == NA_INTEGER || ps < 0 || ps > 4095) Rf_error("mhsr_zonal: planes_mask must be a bit mask of the twelve statistics (1 count ... 2048 cells)");
+    if (!ts && !ps) Rf_error("mhsr_zonal: no output: stats and planes_mask are both 0");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 4) Rf_error("mhsr_zonal: opts must be c(layer, n_zones, quantum, present)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_zonal: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 2147483647.0)) Rf_error("mhsr_zonal: n_zones must be 0 (measure it) or in 1 .. 2^31 - 1");
+    if (!(o[2] >= 0.0)) Rf_error("mhsr_zonal: quantum must be 0 (the library's choice) or a power of two");
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_zonal: bad grid dimension");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    if (TYPEOF(zones) != INTSXP || Rf_xlength(zones) != n) Rf_error("mhsr_zonal: zones must be an integer vector of one zone per cell");
+    const int present = o[3] != 0.0;
+    int64_t n_zones = (int64_t)o[1];
+    double quantum = o[2];
+    mhs_zonal_info info = { 0 };
+    if (ts && !present && n_zones == 0) {                          /* the library measures n_zones before the dense table is sized */
+        chk(mhs_zonal(&g, &st, (int)o[0], (const int32_t *)INTEGER(zones), 0, quantum, 0, NULL, NULL, &info));
+        n_zones = info.n_zones;
+        quantum = info.quantum;
+    }
+    R_xlen_t rows = !ts ? 0 : !present ? (R_xlen_t)n_zones : (n_zones && n_zones < n) ? (R_xlen_t)n_zones : n;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SEXP tab = PROTECT(Rf_allocVector(VECSXP, 9)), pl = PROTECT(Rf_allocVector(VECSXP, 12));
+    int n_protect = 3;
+    for (int k = 0; k < 9; ++k) SET_VECTOR_ELT(tab, k, R_NilValue);
+    for (int k = 0; k < 12; ++k) SET_VECTOR_ELT(pl, k, R_NilValue);
+    /* the library's arrays hold `rows` rows in transient storage; the R vectors are made once the number of rows is known */
+    mhs_zonal_table zt = { (int64_t)rows, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    double **slot[6] = { &zt.sum, &zt.mean, &zt.sd, &zt.min, &zt.max, &zt.range };
+    if (ts && rows > 0) {
+        if (present) zt.zone = (int32_t *)R_alloc((size_t)rows, sizeof(int32_t));
+        if (ts & 1) zt.count = (int64_t *)R_alloc((size_t)rows, sizeof(int64_t));
+        if (ts & 2048) zt.cells = (int64_t *)R_alloc((size_t)rows, sizeof(int64_t));
+        for (int k = 1; k < 7; ++k)
+            if (ts & (1 << k)) *slot[k - 1] = (double *)R_alloc((size_t)rows, sizeof(double));
+    }
+    mhs_zonal_planes zp = { { NULL }, { 0 }, MHS_F64 };
+    for (int k = 0; k < 12; ++k)
+        if (ps & (1 << k)) {
+            const int is_int = k == 0 || k == 11;
+            SET_VECTOR_ELT(pl, k, Rf_allocVector(is_int ? INTSXP : REALSXP, n));
+            zp.plane[k] = is_int ? (void *)INTEGER(VECTOR_ELT(pl, k)) : (void *)REAL(VECTOR_ELT(pl, k));
+            zp.ld[k] = g.ncol;
+        }
+    const int with_table = ts && rows > 0;
+    int rc = MHS_OK;
+    if (with_table || ps) rc = mhs_zonal(&g, &st, (int)o[0], (const int32_t *)INTEGER(zones), n_zones, quantum, 0, with_table ? &zt : NULL, ps ? &zp : NULL, &info);
+    if (rc == MHS_OK) {
+        const R_xlen_t k_rows = !with_table ? 0 : present ? (R_xlen_t)info.n_present : rows;
+        if (ts) {
+            if (present) {
+                SET_VECTOR_ELT(tab, 0, Rf_allocVector(INTSXP, k_rows));
+                for (R_xlen_t k = 0; k < k_rows; ++k) INTEGER(VECTOR_ELT(tab, 0))[k] = zt.zone[k];
+            }
+            for (int j = 0; j < 8; ++j) {                          /* count, sum .. range, cells: bits 0 .. 6 and 11 */
+                if (!(ts & (1 << (j == 7 ? 11 : j)))) continue;
+                SET_VECTOR_ELT(tab, 1 + j, Rf_allocVector(REALSXP, k_rows));
+                double *dst = REAL(VECTOR_ELT(tab, 1 + j));
+                for (R_xlen_t k = 0; k < k_rows; ++k)
+                    dst[k] = j == 0 ? (double)zt.count[k] : j == 7 ? (double)zt.cells[k] : (*slot[j - 1])[k];
+            }
+        }
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 7)); ++n_protect;
+        REAL(inf)[0] = (double)info.n_zones; REAL(inf)[1] = (double)info.n_present; REAL(inf)[2] = (double)info.n_cells_in_zones;
+        REAL(inf)[3] = (double)info.n_contributing; REAL(inf)[4] = (double)info.n_nonfinite; REAL(inf)[5] = (double)info.n_inexact;
+        REAL(inf)[6] = info.quantum;
+        SET_VECTOR_ELT(out, 0, tab);
+        SET_VECTOR_ELT(out, 1, pl);
+        SET_VECTOR_ELT(out, 2, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* Along the D8 flow paths (machisplin_hip.h "flow paths"): height above and distance to the first target cell a cell's own water
  * meets, catchment labels.  flowdir: the integer vector mhsr_hydro returns (0 .. 7, -1 the water leaves, NA_integer_ at NA
  * cells), one per cell; planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, flags, dx, dy) with

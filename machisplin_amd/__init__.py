@@ -22,6 +22,7 @@ from . import flowpath                    # flowpath.flowpath: likewise
 from . import project                     # project.project, project.warp: rasters into another coordinate system
 from . import focal                       # focal.focal: window statistics at any radius
 from . import patches                     # patches.patches, patches.sieve: connected patches of a mask and the size filter
+from . import zonal                       # zonal.zonal: a layer's statistics per zone of an integer zone plane
 from .mess import Mess
 from .terrain import relief, geomorphon, hydro, hydro_mfd, covariates, solar, sun_tables, SunTables      # the 3 x 3 variables: terrain.terrain (the module keeps its name)
 from .cv import fit_layer, fit_nnet_folds, fit_ksvm_folds, kfold
@@ -32,4 +33,4 @@ __all__ = ["MhsError", "init", "Geometry", "RasterStack", "Tps", "interpolate", 
            "ensemble_predict", "models", "tiles", "mltps", "mltps_predict",
            "tps_residual_surface", "tps_residual_surface_se", "nnet_fit_many", "ksvm_fit_many", "sigest", "fit_layer",
            "fit_nnet_folds", "fit_ksvm_folds", "kfold", "varimp", "mess", "Mess", "terrain", "relief", "geomorphon", "hydro", "hydro_mfd", "covariates", "solar", "sun_tables",
-           "SunTables", "resample", "extract", "align", "proximity", "flowpath", "project", "focal", "patches", "_lib"]
+           "SunTables", "resample", "extract", "align", "proximity", "flowpath", "project", "focal", "patches", "zonal", "_lib"]

@@ -120,6 +120,23 @@ class PatchesInfo(C.Structure):
                 ("max_size", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class ZonalTable(C.Structure):
+    """struct mhs_zonal_table"""
+    _fields_ = [("capacity", C.c_int64), ("zone", C.c_void_p), ("count", C.c_void_p), ("sum", C.c_void_p), ("mean", C.c_void_p), ("sd", C.c_void_p),
+                ("min", C.c_void_p), ("max", C.c_void_p), ("range", C.c_void_p), ("cells", C.c_void_p)]
+
+
+class ZonalPlanes(C.Structure):
+    """struct mhs_zonal_planes"""
+    _fields_ = [("plane", C.c_void_p * 12), ("ld", C.c_int64 * 12), ("dtype", C.c_int)]
+
+
+class ZonalInfo(C.Structure):
+    """struct mhs_zonal_info"""
+    _fields_ = [("n_zones", C.c_int64), ("n_present", C.c_int64), ("n_cells_in_zones", C.c_int64), ("n_contributing", C.c_int64),
+                ("n_nonfinite", C.c_int64), ("n_inexact", C.c_int64), ("quantum", C.c_double), ("scratch_bytes", C.c_int64)]
+
+
 class FlowpathOut(C.Structure):
     """struct mhs_flowpath_out"""
     _fields_ = [("index", C.c_void_p), ("steps", C.c_void_p), ("dist", C.c_void_p), ("value", C.c_void_p), ("drop", C.c_void_p)]
@@ -261,6 +278,10 @@ SIGNATURES = {
                                   C.POINTER(PatchesOut), _i64, _vp, C.POINTER(PatchesInfo)]),
     "mhs_patches": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, _i64, _i64, C.c_int,
                               C.POINTER(PatchesOut), C.POINTER(PatchesInfo)]),
+    "mhs_zonal_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _i64, C.c_double, C.c_int, C.POINTER(ZonalTable),
+                                C.POINTER(ZonalPlanes), _vp, C.POINTER(ZonalInfo)]),
+    "mhs_zonal": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, C.c_double, C.c_int, C.POINTER(ZonalTable),
+                            C.POINTER(ZonalPlanes), C.POINTER(ZonalInfo)]),
     "mhs_flowpath_dev": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.POINTER(FlowpathOut), C.c_int, _i64, _vp, C.POINTER(FlowpathInfo)]),
     "mhs_flowpath": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,

@@ -7,8 +7,8 @@ integer, so every plane equals a numpy restatement bit for bit.  All work on the
 (csrc/patches.hip, a block-based union-find); this module only marshals arguments.  A ``keep`` plane goes straight into
 :func:`proximity.proximity`, which takes a 2-D integer tensor of feature flags.
 
-Out of scope: patches of equal value (``terra::patches(values=TRUE)``), zonal statistics of another layer per patch (float
-sums need a fixed order), wrap-around at the date line, more than 2^31 - 1 cells.
+Out of scope: patches of equal value (``terra::patches(values=TRUE)``), wrap-around at the date line, more than 2^31 - 1
+cells.  The statistics of another layer per patch are :func:`zonal.zonal`: a ``label`` or ``id`` plane is a zone plane.
 """
 from __future__ import annotations
 

@@ -30,6 +30,7 @@ HYDRO_MFD_SPEC = {"twi_mfd": ("twi", False), "log_flowacc_mfd": ("flowacc", True
 DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covariates(): spec name -> the predicate of proximity
 STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
 PATCH_DIST_SPEC = {"dist_na_edge": ("na", 0), "dist_na_min": ("na", 1), "dist_le_min": ("le", 2)}      # covariates(): spec name -> the predicate of patches, its arguments
+BASIN_SPEC = {"basin_mean": "mean", "basin_minus_mean": "minus_mean", "basin_dev": "dev"}      # covariates(): spec name -> the plane of zonal
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
 FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
 FOCAL_SPEC = {"focal_mean": "mean", "focal_sd": "sd", "tpi_scale": "minus_mean", "dev": "dev"}      # covariates(): spec name -> the statistic of focal
@@ -402,6 +403,18 @@ def _flow_layers(dem_stack, demf, flowdir, flowacc, thresholds, spec, layer):
     return out
 
 
+def _basin_layers(dem_stack, flowdir, wanted, layer):
+    """the "basin_mean", "basin_minus_mean" and "basin_dev" layers of :func:`covariates`: the outlet labels of the D8 forest are
+    the zones (a cell number per basin, -1 at NA cells), and one zonal call makes the planes; keyed by the spec's name"""
+    import torch
+    from . import flowpath as _flow
+    from . import zonal as _zonal
+    g = dem_stack.geom
+    basin = _flow.flowpath(flowdir, dem_stack, layer, "outlet", None, "index")[0]
+    _, planes, _ = _zonal.zonal(dem_stack, basin, layer, stats=(), planes=wanted, n_zones=g.nrow * g.ncol, table=None, out_dtype=torch.float32)
+    return {name: planes[plane] for name, plane in BASIN_SPEC.items() if plane in planes}
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
@@ -437,6 +450,12 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
       "flowdist_outlet"                           the length of the flow path to its root, where the water leaves the raster
                                                   (these three share the ``hydro`` call too, need metric cells and raise
                                                   ValueError for ``lonlat=True``; one flowpath call per distinct A)
+      "basin_mean", "basin_minus_mean", "basin_dev"
+                                                  the elevation against the cell's DRAINAGE BASIN, the cells that drain to the same
+                                                  root of the D8 forest: the basin's mean elevation, the cell's elevation minus it,
+                                                  and that over the basin's sample sd (the ``hydro`` call is shared again; one
+                                                  :func:`flowpath.flowpath` call labels the basins, one :func:`zonal.zonal` call
+                                                  makes all three)
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -456,6 +475,8 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                        else "no argument"))
             if lonlat:
                 raise ValueError(f"{e[0]!r} follows flow paths in metric cells: lonlat=True is out of scope (resample.resample onto a metric grid)")
+        if e[0] in BASIN_SPEC and len(e) != 1:
+            raise ValueError(f"{e[0]!r} takes no argument")
         if e[0] in STREAM_SPEC and len(e) != 2:
             raise ValueError(f"{e[0]!r} takes one argument, the flow accumulation from which a cell is a stream")
         if e[0] in DIST_SPEC and len(e) != (1 if e[0] == "dist_na" else 2):
@@ -467,9 +488,10 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                        "a threshold and the smallest patch in cells (a whole number >= 1)")[n_args])
     stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
     flow_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in FLOW_SPEC))
-    flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec)
+    basins = tuple(dict.fromkeys(BASIN_SPEC[e[0]] for e in spec if e[0] in BASIN_SPEC))
+    flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec) or bool(basins)
     tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC and e[0] != FLOW_OUTLET
-          and e[0] not in PATCH_DIST_SPEC]
+          and e[0] not in PATCH_DIST_SPEC and e[0] not in BASIN_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
@@ -484,6 +506,8 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                 by_name.update(_stream_layers(dem_stack, demf, hp["flowacc"], stream_a, spec))
             if flows and call is hydro:
                 by_name.update(_flow_layers(dem_stack, demf, hp["flowdir"], hp.get("flowacc"), flow_a, spec, layer))
+            if basins and call is hydro:
+                by_name.update(_basin_layers(dem_stack, hp["flowdir"], basins, layer))
             for n in hv:
                 product, log = table[n]
                 by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
