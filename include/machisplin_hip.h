@@ -1310,6 +1310,103 @@ MHS_API int mhs_zonal_dev(const mhs_grid *g, const mhs_stack *stack, int layer, 
 MHS_API int mhs_zonal(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t n_zones, double quantum, int flags,
                       const mhs_zonal_table *table, const mhs_zonal_planes *planes, mhs_zonal_info *info);
 
+/* ---------------------------------------------------------------- rasterize --
+ * Points, lines and polygons burned onto the grid: what terra::rasterize is used for -- the administrative units or catchments
+ * that become a zone plane of "zonal", the digitised coastline, rivers and lakes that "proximity" measures to, the stations'
+ * density per cell.  The reference has no such step.  THE RULE (this text is the specification; csrc/rasterize_rule.h holds it
+ * as code).  The library is built without contraction, so every line is a fixed sequence of float64 operations, each rounded
+ * once; every product is an integer or a gather, equals a numpy restatement exactly, and a repeated call gives the same bytes.
+ *
+ * GRID.  x_c(c) = xmin + (c + 0.5) * xres, y_r(r) = ymax - (r + 0.5) * yres, yedge(r) = ymax - r * yres,
+ * col(x) = floor((x - xmin) / xres), row(y) = floor((ymax - y) / yres).
+ *
+ * SEGMENT.  Always in canonical orientation: (xa, ya) is the endpoint with the smaller y.  t = (xb - xa) / (yb - ya) and
+ * X(y) = xa + (y - ya) * t, with X(yb) = xb, and X clamped to the segment's own x range min(xa, xb) .. max(xa, xb): a feature's
+ * cover then lies inside the bounding box of its vertices whatever the rounding of t.  Two polygons that share an edge in
+ * opposite directions compute identical bits on it: no gap and no overlap between them.
+ *
+ * POLYGONS (centre rule, even-odd over ALL rings of the feature: holes and multi-part features need no special case).  An edge
+ * crosses row r when (y0 <= y_r) != (y1 <= y_r); it toggles the cells with x_c(c) < X(y_r); a cell is covered when it was
+ * toggled an odd number of times.  Horizontal edges never cross.
+ * LINES (every cell the segment passes through; 4-connected).  A horizontal segment burns row(ya) from col(min x) to col(max x).
+ * Any other, for each row r in row(yb) .. row(ya): ylo = max(ya, yedge(r + 1)), yhi = min(yb, yedge(r)); if ylo > yhi the row is
+ * skipped, else the columns col(min(X(ylo), X(yhi))) .. col(max(X(ylo), X(yhi))) are burned.  Rows and columns are clipped to
+ * the grid.  The value at a shared row edge is computed identically for the row above and the row below: the chain cannot break.
+ * POINTS.  Cell (row(y), col(x)); the east edge belongs to the last column and the south edge to the last row (terra's
+ * colFromX / rowFromY).  A point outside the grid is counted in info->n_outside and burns nothing.
+ * touches != 0, polygons only: the centre rule OR the line rule applied to every ring.
+ *
+ * WHICH FEATURE WINS.  Feature i carries a unique int32 key made on the host, and a cell keeps the LARGEST key that covers it
+ * (integer atomicMax into a key plane that starts at -1), so the result does not depend on the order of execution:
+ *   MHS_RASTERIZE_LAST   i                        MHS_RASTERIZE_MAX   the rank of values[i], ties by index
+ *   MHS_RASTERIZE_FIRST  n - 1 - i                MHS_RASTERIZE_MIN   n - 1 - that rank
+ *
+ * PRODUCTS, each optional, at least one: index (int32: the winning feature, -1 for none -- a ready zone plane for "zonal"),
+ * count (int32: the number of features that cover the cell -- a feature counts once however many of its rings and segments
+ * meet the cell --, for points the number of points in it; integer atomicAdd), value (MHS_F32 or MHS_F64: values[index], NaN
+ * for none; a float32 is the float64 rounded once).
+ * INFO: n_features, n_parts, n_vertices, n_edges (segments: n_vertices - n_parts; 0 for points), n_items (the (edge, row) items
+ * processed: a polygon edge's crossings of grid rows, a line segment's rows inside the grid, both with touches; for points
+ * n_vertices), n_batches, n_burned (cells with index >= 0), n_outside (points outside the grid), scratch_bytes.
+ *
+ * GEOMETRY arrives as HOST arrays in both entries (vector data is born in files; the library copies it to the device on the
+ * call's stream): coords, n_vertices x 2 (x, y) in the grid's coordinate system; part_offsets, n_parts + 1 vertex numbers -- a
+ * part is a ring of a polygon, a polyline of a line, a run of points; feature_offsets, n_features + 1 part numbers; values,
+ * n_features float64 or NULL.
+ *
+ * REFUSALS (MHS_ERR_INVALID), every one before the first device call, the message names the argument: a non-finite
+ * coordinate; offsets that do not start at 0, decrease, or do not end at the array lengths; a ring of fewer than 4 vertices or
+ * one whose last vertex is not its first; a line part of fewer than 2 vertices; nrow * ncol > 2^31 - 1; cell sizes that are not
+ * positive and finite; no product; values missing when value, MHS_RASTERIZE_MIN or _MAX needs them, or not finite with _MIN or
+ * _MAX; a negative scratch_budget; an unknown kind, rule or value dtype; an ld smaller than ncol.
+ *
+ * OUT OF SCOPE: partial-coverage fractions (cover = TRUE); float sums of overlapping features' values; Shapefile, GeoPackage
+ * and WKT readers; reprojection of geometries along curved edges (vertices only); line width and buffers; polygon validity
+ * repair; more than 2^31 - 1 cells, vertices or features.
+ *
+ * The algorithm (csrc/rasterize.hip), every phase its own launch, a kernel boundary the only ordering: (1) a lane
+ * per edge counts its items, then a blocked exclusive prefix sum; (2) a lane per (edge, row) item finds its edge by bisection in
+ * the prefix sums and toggles bit c* of the feature's row in a per-feature BIT PLANE (atomicXor), or ORs a line span into the
+ * plane's second layer (atomicOr); (3) a wave per (feature, box row) runs a suffix-XOR scan over the row's words, ORs the line
+ * layer, and sends every covered cell's key to the key plane (atomicMax) and 1 to the count plane (atomicAdd); points go
+ * straight to the two planes; (4) one pass makes index and value from the key plane.  The host plans BATCHES of consecutive
+ * features whose bit planes fit scratch_budget bytes (0: 256 MiB); a feature larger than the budget gets a batch of its own;
+ * the planes are identical whatever the budget.  SCRATCH, stream-ordered memory given back behind the last kernel: the
+ * geometry (20 bytes per vertex), 12 bytes per vertex for the prefix sums (20 with touches), 52 bytes per feature, the key
+ * plane (4 bytes per cell) and the largest batch's bit planes.  MHS_ERR_ALLOC if there is none. */
+#define MHS_RASTERIZE_POINT 0
+#define MHS_RASTERIZE_LINE 1
+#define MHS_RASTERIZE_POLYGON 2
+#define MHS_RASTERIZE_LAST 0
+#define MHS_RASTERIZE_FIRST 1
+#define MHS_RASTERIZE_MAX 2
+#define MHS_RASTERIZE_MIN 3
+typedef struct mhs_features {
+    int kind;                          /* MHS_RASTERIZE_POINT, _LINE or _POLYGON */
+    int64_t n_vertices, n_parts, n_features;
+    const double *coords;              /* n_vertices x 2: x, y */
+    const int64_t *part_offsets;       /* n_parts + 1 */
+    const int64_t *feature_offsets;    /* n_features + 1 */
+    const double *values;              /* n_features, or NULL */
+} mhs_features;
+typedef struct mhs_rasterize_out {
+    int32_t *index;                    /* NULL: not wanted */
+    int32_t *count;
+    void *value;
+    int64_t ld_index, ld_count, ld_value;      /* the row stride of each, in elements */
+    int value_dtype;                   /* MHS_F64 or MHS_F32 */
+} mhs_rasterize_out;
+typedef struct mhs_rasterize_info {
+    int64_t n_features, n_parts, n_vertices, n_edges, n_items, n_batches, n_burned, n_outside, scratch_bytes;
+} mhs_rasterize_info;
+/* DEVICE planes: out's planes are on the device, the geometry on the host.  The stream is synchronised behind the prefix sums
+ * (the host reads the batches' item ranges) and behind the last kernel. */
+MHS_API int mhs_rasterize_dev(const mhs_grid *g, const mhs_features *features, int rule, int touches, const mhs_rasterize_out *out,
+                              int64_t scratch_budget, void *stream, mhs_rasterize_info *info);
+/* same, HOST planes (nrow x ncol dense; ld is not looked at) -- what the R shim hands over.  Blocks until done. */
+MHS_API int mhs_rasterize(const mhs_grid *g, const mhs_features *features, int rule, int touches, const mhs_rasterize_out *out,
+                          int64_t scratch_budget, mhs_rasterize_info *info);
+
 /* --------------------------------------------------------------- flow paths --
  * Drainage covariates ALONG the flow: height above and distance to the first channel cell that a cell's own water meets (HAND,
  * SAGA's vertical / horizontal distance to channel network), and the basin a cell drains to.  "proximity" takes the stream cell

@@ -469,6 +469,47 @@ mhs_zonal <- function(x, z, stats = "mean", planes = NULL, present = TRUE, n.zon
        info = stats::setNames(out[[3]], c("n_zones", "n_present", "n_cells_in_zones", "n_contributing", "n_nonfinite", "n_inexact", "quantum")))
 }
 
+# ---- rasterize: points, lines and polygons burned onto the grid (what terra::rasterize is used for) --------------------------
+# x: a SpatRaster that gives the grid.  coords: a numeric matrix of two columns (x, y) in the grid's coordinate system;
+# part.offsets: 0-based vertex numbers that cut it into parts (a ring of a polygon, a polyline, a run of points), one more than
+# there are parts; feature.offsets: 0-based part numbers that group the parts into features, one more than there are features --
+# with terra, g <- terra::geom(v) gives coords = g[, c("x", "y")], the parts from the runs of (geom, part, hole) and the features
+# from the runs of geom.  values: one number per feature (a field of the vector), or NULL.  v: the layers wanted, any of "index"
+# (the winning feature, 1-based as a row of the vector; NA for none -- minus 1 it is a zone plane for mhs_zonal), "count" (the
+# number of features on the cell; for points the number of points in it) and "value" (values[index]; NA for none -- what
+# mhs_proximity(where = "valid") takes).  rule: which feature wins where several cover a cell, "last" or "first" in the vector's
+# order, "max" or "min" of values.  touches = TRUE adds every cell that a polygon's ring passes through to the centre rule.
+# Section "rasterize" of machisplin_hip.h states the rule; partial-coverage fractions, sums of overlapping values, line width and
+# buffers, and validity repair are out of scope.
+.mhs_rasterize_kinds <- c("point", "line", "polygon")
+.mhs_rasterize_rules <- c("last", "first", "max", "min")
+.mhs_rasterize_products <- c("index", "count", "value")
+mhs_rasterize <- function(x, coords, part.offsets, feature.offsets, values = NULL, kind = "polygon", v = "index", rule = "last", touches = FALSE,
+                          scratch.budget = NULL) {
+  if (!kind %in% .mhs_rasterize_kinds) stop("mhs_rasterize: kind must be one of ", paste(.mhs_rasterize_kinds, collapse = ", "))
+  if (!rule %in% .mhs_rasterize_rules) stop("mhs_rasterize: rule must be one of ", paste(.mhs_rasterize_rules, collapse = ", "))
+  if (!length(v) || length(setdiff(v, .mhs_rasterize_products))) stop("mhs_rasterize: v must name some of ", paste(.mhs_rasterize_products, collapse = ", "))
+  if (is.null(values) && ("value" %in% v || rule %in% c("max", "min"))) stop("mhs_rasterize: values is missing: \"value\", \"max\" and \"min\" need it")
+  if (!is.null(scratch.budget) && (is.na(scratch.budget) || scratch.budget < 1)) stop("mhs_rasterize: scratch.budget must be a positive number of bytes")
+  v <- unique(v)
+  coords <- as.matrix(coords); storage.mode(coords) <- "double"
+  out <- .Call("mhsr_rasterize", .mhs_geom(x), coords, as.integer(part.offsets), as.integer(feature.offsets),
+               if (is.null(values)) NULL else as.numeric(values),
+               c(match(kind, .mhs_rasterize_kinds) - 1, match(rule, .mhs_rasterize_rules) - 1, as.numeric(isTRUE(touches)),
+                 if (is.null(scratch.budget)) 0 else scratch.budget),
+               as.integer(sum(2^(match(v, .mhs_rasterize_products) - 1))))
+  layers <- lapply(v, function(p) {
+    vals <- out[[match(p, .mhs_rasterize_products)]]
+    if (p == "index") vals <- ifelse(vals < 0L, NA_integer_, vals + 1L)
+    l <- terra::setValues(terra::rast(x[[1]]), vals)
+    names(l) <- p
+    l
+  })
+  r <- do.call(c, layers)
+  attr(r, "info") <- stats::setNames(out[[4]], c("n_features", "n_parts", "n_vertices", "n_edges", "n_items", "n_batches", "n_burned", "n_outside"))
+  r
+}
+
 # ---- flow-path covariates: HAND, SAGA's vertical / horizontal distance to channel network, catchment labels ------------------
 # flowdir: the one-layer SpatRaster of D8 directions that the hydrology call makes (0 .. 7 = E, SE, S, SW, W, NW, N, NE, -1 the
 # water leaves, NA).  x: a SpatRaster on the same grid whose layer `layer` defines the targets -- `where` as for mhs_proximity,

@@ -677,6 +677,57 @@ SEXP mhsr_zonal(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP opts, SEXP
     return out;
 }
 
+/* Vector features burned onto the grid (machisplin_hip.h "rasterize"): what terra::rasterize is used for.  coords: a V x 2 numeric
+ * matrix (x, y) in the grid's coordinate system; part_offsets: integer vector of P + 1 0-based vertex numbers (a part is a ring of
+ * a polygon, a polyline, a run of points); feature_offsets: integer vector of F + 1 0-based part numbers; values: numeric vector of
+ * one value per feature, or NULL; opts: c(kind, rule, touches, scratch_budget) with kind 0 point, 1 line, 2 polygon, rule 0 last,
+ * 1 first, 2 max, 3 min, scratch_budget 0 = the library's 256 MiB; products: bit mask of 1 index, 2 count, 4 value.  Returns
+ * list(index, count, value, info): index (integer, the winning feature 0-based, -1 for none) and count (integer) and value
+ * (numeric, NaN for none), one per cell in terra cell order, NULL where not asked for; info = c(n_features, n_parts, n_vertices,
+ * n_edges, n_items, n_batches, n_burned, n_outside).  Runs on the HOST entry point: the products come down whole. */
+SEXP mhsr_rasterize(SEXP geom, SEXP coords, SEXP part_offsets, SEXP feature_offsets, SEXP values, SEXP opts, SEXP products) {
+    mhs_grid g = grid_from(geom);
+    if (!Rf_isReal(coords) || !Rf_isMatrix(coords) || Rf_ncols(coords) != 2) Rf_error("mhsr_rasterize: coords must be a numeric matrix of two columns (x, y)");
+    if (TYPEOF(part_offsets) != INTSXP || Rf_xlength(part_offsets) < 1) Rf_error("mhsr_rasterize: part_offsets must be an integer vector of n_parts + 1 vertex numbers");
+    if (TYPEOF(feature_offsets) != INTSXP || Rf_xlength(feature_offsets) < 1) Rf_error("mhsr_rasterize: feature_offsets must be an integer vector of n_features + 1 part numbers");
+    const R_xlen_t nv = Rf_nrows(coords), np = Rf_xlength(part_offsets) - 1, nf = Rf_xlength(feature_offsets) - 1;
+    if (values != R_NilValue && (!Rf_isReal(values) || Rf_xlength(values) != nf)) Rf_error("mhsr_rasterize: values must be NULL or a numeric vector of one value per feature");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 4) Rf_error("mhsr_rasterize: opts must be c(kind, rule, touches, scratch_budget)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2.0)) Rf_error("mhsr_rasterize: kind must be 0 (point), 1 (line) or 2 (polygon)");
+    if (!(o[1] >= 0.0 && o[1] <= 3.0)) Rf_error("mhsr_rasterize: rule must be 0 (last), 1 (first), 2 (max) or 3 (min)");
+    if (!(o[3] >= 0.0 && o[3] <= 9007199254740992.0)) Rf_error("mhsr_rasterize: scratch_budget must be 0 (the library's choice) or a number of bytes");
+    int pm = Rf_asInteger(products);
+    if (pm == NA_INTEGER || pm < 1 || pm > 7) Rf_error("mhsr_rasterize: products must be a bit mask of 1 index, 2 count, 4 value, and not 0");
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_rasterize: bad grid dimension");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    /* R's matrix is column-major and its offsets are int: the library takes x, y pairs and int64 */
+    double *xy = (double *)R_alloc((size_t)(nv ? 2 * nv : 1), sizeof(double));
+    int64_t *po = (int64_t *)R_alloc((size_t)(np + 1), sizeof(int64_t)), *fo = (int64_t *)R_alloc((size_t)(nf + 1), sizeof(int64_t));
+    for (R_xlen_t v = 0; v < nv; ++v) { xy[2 * v] = REAL(coords)[v]; xy[2 * v + 1] = REAL(coords)[nv + v]; }
+    for (R_xlen_t i = 0; i <= np; ++i) po[i] = INTEGER(part_offsets)[i] == NA_INTEGER ? -1 : INTEGER(part_offsets)[i];
+    for (R_xlen_t i = 0; i <= nf; ++i) fo[i] = INTEGER(feature_offsets)[i] == NA_INTEGER ? -1 : INTEGER(feature_offsets)[i];
+    mhs_features ft = { (int)o[0], (int64_t)nv, (int64_t)np, (int64_t)nf, xy, po, fo, values == R_NilValue ? NULL : REAL(values) };
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 4));
+    for (int k = 0; k < 4; ++k) SET_VECTOR_ELT(out, k, R_NilValue);
+    if (pm & 1) SET_VECTOR_ELT(out, 0, Rf_allocVector(INTSXP, n));
+    if (pm & 2) SET_VECTOR_ELT(out, 1, Rf_allocVector(INTSXP, n));
+    if (pm & 4) SET_VECTOR_ELT(out, 2, Rf_allocVector(REALSXP, n));
+    mhs_rasterize_out ro = { (pm & 1) ? (int32_t *)INTEGER(VECTOR_ELT(out, 0)) : NULL, (pm & 2) ? (int32_t *)INTEGER(VECTOR_ELT(out, 1)) : NULL,
+                             (pm & 4) ? (void *)REAL(VECTOR_ELT(out, 2)) : NULL, g.ncol, g.ncol, g.ncol, MHS_F64 };
+    mhs_rasterize_info info = { 0 };
+    int rc = mhs_rasterize(&g, &ft, (int)o[1], o[2] != 0.0, &ro, (int64_t)o[3], &info);
+    if (rc == MHS_OK) {
+        SET_VECTOR_ELT(out, 3, Rf_allocVector(REALSXP, 8));
+        double *inf = REAL(VECTOR_ELT(out, 3));
+        inf[0] = (double)info.n_features; inf[1] = (double)info.n_parts; inf[2] = (double)info.n_vertices; inf[3] = (double)info.n_edges;
+        inf[4] = (double)info.n_items; inf[5] = (double)info.n_batches; inf[6] = (double)info.n_burned; inf[7] = (double)info.n_outside;
+    }
+    UNPROTECT(1);
+    chk(rc);
+    return out;
+}
+
 /* Along the D8 flow paths (machisplin_hip.h "flow paths"): height above and distance to the first target cell a cell's own water
  * meets, catchment labels.  flowdir: the integer vector mhsr_hydro returns (0 .. 7, -1 the water leaves, NA_integer_ at NA
  * cells), one per cell; planes, nodata: as for mhsr_resample; opts: c(layer, where, threshold, value_layer, flags, dx, dy) with

@@ -137,6 +137,24 @@ class ZonalInfo(C.Structure):
                 ("n_nonfinite", C.c_int64), ("n_inexact", C.c_int64), ("quantum", C.c_double), ("scratch_bytes", C.c_int64)]
 
 
+class Features(C.Structure):
+    """struct mhs_features"""
+    _fields_ = [("kind", C.c_int), ("n_vertices", C.c_int64), ("n_parts", C.c_int64), ("n_features", C.c_int64), ("coords", C.c_void_p),
+                ("part_offsets", C.c_void_p), ("feature_offsets", C.c_void_p), ("values", C.c_void_p)]
+
+
+class RasterizeOut(C.Structure):
+    """struct mhs_rasterize_out"""
+    _fields_ = [("index", C.c_void_p), ("count", C.c_void_p), ("value", C.c_void_p), ("ld_index", C.c_int64), ("ld_count", C.c_int64),
+                ("ld_value", C.c_int64), ("value_dtype", C.c_int)]
+
+
+class RasterizeInfo(C.Structure):
+    """struct mhs_rasterize_info"""
+    _fields_ = [("n_features", C.c_int64), ("n_parts", C.c_int64), ("n_vertices", C.c_int64), ("n_edges", C.c_int64), ("n_items", C.c_int64),
+                ("n_batches", C.c_int64), ("n_burned", C.c_int64), ("n_outside", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 class FlowpathOut(C.Structure):
     """struct mhs_flowpath_out"""
     _fields_ = [("index", C.c_void_p), ("steps", C.c_void_p), ("dist", C.c_void_p), ("value", C.c_void_p), ("drop", C.c_void_p)]
@@ -282,6 +300,9 @@ SIGNATURES = {
                                 C.POINTER(ZonalPlanes), _vp, C.POINTER(ZonalInfo)]),
     "mhs_zonal": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, C.c_double, C.c_int, C.POINTER(ZonalTable),
                             C.POINTER(ZonalPlanes), C.POINTER(ZonalInfo)]),
+    "mhs_rasterize_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Features), C.c_int, C.c_int, C.POINTER(RasterizeOut), _i64, _vp,
+                                    C.POINTER(RasterizeInfo)]),
+    "mhs_rasterize": (C.c_int, [C.POINTER(Grid), C.POINTER(Features), C.c_int, C.c_int, C.POINTER(RasterizeOut), _i64, C.POINTER(RasterizeInfo)]),
     "mhs_flowpath_dev": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
                                    C.c_double, C.POINTER(FlowpathOut), C.c_int, _i64, _vp, C.POINTER(FlowpathInfo)]),
     "mhs_flowpath": (C.c_int, [C.POINTER(Grid), _vp, _i64, C.POINTER(Stack), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,

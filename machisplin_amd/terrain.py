@@ -31,6 +31,8 @@ DIST_SPEC = {"dist_na": "na", "dist_le": "le", "dist_ge": "ge"}          # covar
 STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covariates(): spec name -> the product of proximity
 PATCH_DIST_SPEC = {"dist_na_edge": ("na", 0), "dist_na_min": ("na", 1), "dist_le_min": ("le", 2)}      # covariates(): spec name -> the predicate of patches, its arguments
 BASIN_SPEC = {"basin_mean": "mean", "basin_minus_mean": "minus_mean", "basin_dev": "dev"}      # covariates(): spec name -> the plane of zonal
+ZONE_SPEC = {"zone_mean": "mean", "zone_minus_mean": "minus_mean", "zone_dev": "dev"}      # covariates(): spec name -> the plane of zonal, zones from vector features
+DIST_FEATURES = "dist_features"                                         # covariates(): the distance to vector features
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
 FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
 FOCAL_SPEC = {"focal_mean": "mean", "focal_sd": "sd", "tpi_scale": "minus_mean", "dev": "dev"}      # covariates(): spec name -> the statistic of focal
@@ -415,6 +417,33 @@ def _basin_layers(dem_stack, flowdir, wanted, layer):
     return {name: planes[plane] for name, plane in BASIN_SPEC.items() if plane in planes}
 
 
+def _vector_layers(dem_stack, spec, layer):
+    """the ("dist_features", feats) and ("zone_mean" | "zone_minus_mean" | "zone_dev", feats) layers of :func:`covariates`: the
+    features are burned onto the DEM's grid (:func:`rasterize.rasterize`) -- with ``touches`` and as a value plane for the distance,
+    which one proximity call then measures to; as an index plane for the zones, which one zonal call per distinct ``feats`` makes
+    all three planes from; keyed (name, id(feats))"""
+    import torch
+    from . import proximity as _prox
+    from . import rasterize as _rast
+    from . import zonal as _zonal
+    from .vector import Features
+    g = dem_stack.geom
+    dev = dem_stack.planes.device
+    out = {}
+    for feats in {id(e[1]): e[1] for e in spec if e[0] == DIST_FEATURES}.values():
+        marked = Features(feats.kind, feats.coords, feats.part_offsets, feats.feature_offsets, np.zeros(feats.n_features))   # a NaN value would be no feature
+        burned, _ = _rast.rasterize(marked, g, ("value",), touches=True, device=dev)
+        out[(DIST_FEATURES, id(feats))] = _prox.proximity(RasterStack(g, burned["value"][None], float("nan")), 0, "valid", None, "dist",
+                                                          out_dtype=torch.float32)[0]
+    for feats in {id(e[1]): e[1] for e in spec if e[0] in ZONE_SPEC}.values():
+        wanted = tuple(dict.fromkeys(ZONE_SPEC[e[0]] for e in spec if e[0] in ZONE_SPEC and e[1] is feats))
+        zones, _ = _rast.rasterize(feats, g, ("index",), device=dev)
+        _, planes, _ = _zonal.zonal(dem_stack, zones["index"], layer, stats=(), planes=wanted, n_zones=max(feats.n_features, 1), table=None,
+                                    out_dtype=torch.float32)
+        out.update({(name, id(feats)): planes[plane] for name, plane in ZONE_SPEC.items() if plane in planes})
+    return out
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
@@ -456,6 +485,14 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                   and that over the basin's sample sd (the ``hydro`` call is shared again; one
                                                   :func:`flowpath.flowpath` call labels the basins, one :func:`zonal.zonal` call
                                                   makes all three)
+      ("dist_features", feats)                    distance to the nearest cell that the :class:`vector.Features` ``feats`` -- a
+                                                  digitised coastline, rivers, lakes, stations -- touch (:func:`rasterize.rasterize`
+                                                  with ``touches=True``, then proximity; square cells)
+      ("zone_mean" | "zone_minus_mean" | "zone_dev", feats)
+                                                  the elevation against the polygon of ``feats`` that holds the cell's centre --
+                                                  an administrative unit, a catchment: the zone's mean elevation, the cell's
+                                                  elevation minus it, and that over the zone's sample sd (one rasterize call and
+                                                  one :func:`zonal.zonal` call per distinct ``feats`` make all three; NaN outside)
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -477,6 +514,10 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                 raise ValueError(f"{e[0]!r} follows flow paths in metric cells: lonlat=True is out of scope (resample.resample onto a metric grid)")
         if e[0] in BASIN_SPEC and len(e) != 1:
             raise ValueError(f"{e[0]!r} takes no argument")
+        if e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
+            from .vector import Features
+            if len(e) != 2 or not isinstance(e[1], Features):
+                raise ValueError(f"{e[0]!r} takes one argument, a vector.Features in the DEM's coordinate system")
         if e[0] in STREAM_SPEC and len(e) != 2:
             raise ValueError(f"{e[0]!r} takes one argument, the flow accumulation from which a cell is a stream")
         if e[0] in DIST_SPEC and len(e) != (1 if e[0] == "dist_na" else 2):
@@ -541,8 +582,13 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             keep = _patches.sieve(dem_stack, layer, where, float(e[1]) if n_args == 2 else None, 8, min_size=int(e[-1]) if n_args else 1,
                                   edge="any" if n_args else "touching")
             by_name[e] = _prox.proximity(keep, products="dist", unit=g.xres, out_dtype=torch.float32)[0]
+    if any(e[0] in ZONE_SPEC or e[0] == DIST_FEATURES for e in spec):
+        by_name.update(_vector_layers(dem_stack, spec, layer))
     for k, e in enumerate(spec):
-        if e[0] in PATCH_DIST_SPEC:
+        if e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
+            planes[1 + k] = by_name[(e[0], id(e[1]))]
+            names.append(e[0])
+        elif e[0] in PATCH_DIST_SPEC:
             planes[1 + k] = by_name[e]
             names.append(e[0] if len(e) == 1 else f"{e[0]}{int(e[1])}" if len(e) == 2 else f"dist_le{float(e[1]):g}_min{int(e[2])}")
         elif e[0] in DIST_SPEC or e[0] in STREAM_SPEC or e[0] in FLOW_SPEC:
