@@ -37,17 +37,19 @@ def _improvements(x, zc, tot, m, minobs):
     return np.where(ok, imp, 0), ls
 
 
-def _best_split(X, z, segs, tot, minobs, acc):
+def _best_split(X, z, segs, tot, minobs, acc, scan=np.cumsum, var_tie_last=False, pos_tie_high=False):
     m = segs[0].size
     best = (acc(0), -1, 0, 0.0, acc(0))         # imp, var, nL, split, left sum
     if m < 2:
         return best
     for v, r in enumerate(segs):
         x = X[r, v]
-        zc = np.cumsum(z[r].astype(acc))
+        zc = scan(z[r].astype(acc))
         imp, ls = _improvements(x, zc, tot, m, minobs)
         k = int(np.argmax(imp))                 # the first of equal maxima: the lowest position
-        if imp[k] > best[0]:
+        if pos_tie_high:
+            k = imp.size - 1 - int(np.argmax(imp[::-1]))
+        if imp[k] > best[0] or (var_tie_last and imp[k] == best[0] and imp[k] > 0):
             best = (imp[k], v, k + 1, 0.5 * (x[k] + x[k + 1]), ls[k])
     return best
 
@@ -67,24 +69,30 @@ def candidate_improvement(X, z, tree, node, var, split, minobs=10, acc=np.float6
     return float(imp[nl - 1])
 
 
-def grow_tree(X, z, bag, orders, depth=25, minobs=10, shrinkage=0.01, acc=np.float64):
+def grow_tree(X, z, bag, orders, depth=25, minobs=10, shrinkage=0.01, acc=np.float64, scan=np.cumsum, var_tie_last=False,
+              pos_tie_high=False, node_tie_later=False):
     """One tree.  Returns a dict: the preorder arrays (split_var, split_val, left, right, missing), ``imp`` (the
     improvement of every internal node, preorder), ``pre`` (creation index -> preorder index), and per creation-order
-    node ``segs`` (its bag rows in every variable's order) and ``tot``."""
+    node ``segs`` (its bag rows in every variable's order) and ``tot``.  ``scan`` forms the running sums of z along a
+    sorted order in place of np.cumsum.  The last three arguments grow DELIBERATELY WRONG trees, for the tests that show
+    what an exact comparison catches (test_tree_ties_host.py): ``var_tie_last`` lets an equal improvement of a later
+    variable replace the best ('>=' for '>'), ``pos_tie_high`` takes the highest position among equal improvements of
+    one variable, ``node_tie_later`` splits the later of two terminal nodes with equal improvements."""
+    search = lambda s, t_: _best_split(X, z, s, t_, minobs, acc, scan, var_tie_last, pos_tie_high)
     n, p = X.shape
     inbag = np.zeros(n, dtype=bool)
     inbag[bag] = True
     segs0 = [o[inbag[o]] for o in orders]
-    tot0 = np.cumsum(z[segs0[0]].astype(acc))[-1]
+    tot0 = scan(z[segs0[0]].astype(acc))[-1]
     var, val, left, right, miss, imps = [-1], [tot0 / acc(segs0[0].size)], [-1], [-1], [-1], [0.0]
     segs, tot = [segs0], [tot0]
     term = [0]                                   # terminal list: creation indices
-    best = {0: _best_split(X, z, segs0, tot0, minobs, acc)}
+    best = {0: search(segs0, tot0)}
     empty = [np.zeros(0, dtype=np.int64)] * p
     for _ in range(depth):
         k, top = -1, acc(0)
         for slot, nd in enumerate(term):
-            if best[nd][0] > top:
+            if best[nd][0] > top or (node_tie_later and best[nd][0] == top and top > 0):
                 top, k = best[nd][0], slot
         if k < 0:
             break
@@ -103,8 +111,8 @@ def grow_tree(X, z, bag, orders, depth=25, minobs=10, shrinkage=0.01, acc=np.flo
         for s, t_, mean in ((sl, tl, tl / acc(nl)), (sr, tr, tr / acc(m - nl)), (empty, acc(0), parent_mean)):
             var.append(-1); val.append(mean); left.append(-1); right.append(-1); miss.append(-1); imps.append(0.0)
             segs.append(s); tot.append(t_)
-        best[nn] = _best_split(X, z, sl, tl, minobs, acc)
-        best[nn + 1] = _best_split(X, z, sr, tr, minobs, acc)
+        best[nn] = search(sl, tl)
+        best[nn + 1] = search(sr, tr)
         best[nn + 2] = (acc(0), -1, 0, 0.0, acc(0))
         term[k] = nn
         term += [nn + 1, nn + 2]

@@ -47,14 +47,14 @@ def draw_vars(seed, k, p, mtry):
     return out
 
 
-def _candidates(X, y, counts, rows, v, acc):
+def _candidates(X, y, counts, rows, v, acc, scan=np.cumsum):
     """The candidates of a node (``rows`` ascending) along variable v: (criteria, a, b, rows left) per candidate, in
-    position order, with sequential sums in ``acc``."""
+    position order, with sequential sums in ``acc`` (``scan``: what forms the running sums of c y in place of np.cumsum)."""
     o = np.argsort(X[rows, v], kind="stable")
     r = rows[o]
     x = X[r, v]
     c = counts[r]
-    wc = np.cumsum((c * y[r]).astype(acc))
+    wc = scan((c * y[r]).astype(acc))
     cc = np.cumsum(c)
     tot, m = wc[-1], acc(cc[-1])
     at = np.flatnonzero(x[:-1] < x[1:])
@@ -69,8 +69,12 @@ def split_value(a, b):
     return mid if mid < b else a
 
 
-def grow_tree(X, y, counts, seed, mtry, nodesize=5, acc=np.float64):
-    """One tree.  Returns the dict of tree-local arrays plus ``rows`` (the in-bag rows of every node)."""
+def grow_tree(X, y, counts, seed, mtry, nodesize=5, acc=np.float64, scan=np.cumsum, var_tie_last=False, pos_tie_high=False):
+    """One tree.  Returns the dict of tree-local arrays plus ``rows`` (the in-bag rows of every node).  ``scan`` forms the
+    running sums of c y along a sorted order in place of np.cumsum.  The last two arguments grow DELIBERATELY WRONG trees,
+    for the tests that show what an exact comparison catches (test_tree_ties_host.py): ``var_tie_last`` lets an equal
+    criterion of a later drawn variable replace the best ('>=' for '>'), ``pos_tie_high`` takes the highest position
+    among equal criteria of one variable."""
     counts = np.asarray(counts, dtype=np.int64)
     p = X.shape[1]
     rows = [np.flatnonzero(counts > 0)]
@@ -80,14 +84,16 @@ def grow_tree(X, y, counts, seed, mtry, nodesize=5, acc=np.float64):
         rk = rows[k]
         c = counts[rk]
         m = int(c.sum())
-        pred.append(float(np.cumsum((c * y[rk]).astype(acc))[-1] / acc(m)))
+        pred.append(float(scan((c * y[rk]).astype(acc))[-1] / acc(m)))
         if (k == 0 or m > nodesize) and rk.size >= 2:
             best = (acc(0), -1, 0.0, None)
             for v in draw_vars(seed, k, p, mtry):
-                crit, a, b, nl, r = _candidates(X, y, counts, rk, v, acc)
+                crit, a, b, nl, r = _candidates(X, y, counts, rk, v, acc, scan)
                 if crit.size:
                     j = int(np.argmax(crit))            # the first of equal maxima: the lowest position
-                    if crit[j] > best[0]:
+                    if pos_tie_high:
+                        j = crit.size - 1 - int(np.argmax(crit[::-1]))
+                    if crit[j] > best[0] or (var_tie_last and crit[j] == best[0] and crit[j] > 0):
                         best = (crit[j], v, split_value(a[j], b[j]), r[:nl[j]])
             if best[1] >= 0:
                 go_left = np.zeros(X.shape[0], dtype=bool)
