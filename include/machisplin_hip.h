@@ -1407,6 +1407,142 @@ MHS_API int mhs_rasterize_dev(const mhs_grid *g, const mhs_features *features, i
 MHS_API int mhs_rasterize(const mhs_grid *g, const mhs_features *features, int rule, int touches, const mhs_rasterize_out *out,
                           int64_t scratch_budget, mhs_rasterize_info *info);
 
+/* ------------------------------------------------------------------ classes --
+ * CATEGORICAL layers -- a land-cover raster (NLCD, CORINE, WorldCover, MODIS IGBP): what is INSIDE a zone, a coarser cell or a
+ * neighbourhood of it.  The members take numeric covariates only, so such a raster enters a stack as CLASS FRACTIONS: the share
+ * of forest, water or built-up land in the model cell, within R cells, or in the basin; and "zonal" and "resample" gain the
+ * mode they leave out.  What terra::crosstab, terra::aggregate(fun = "modal") and terra::focal per class are used for.  The
+ * reference has no such step.  THE RULE (this text is the specification; csrc/classes_rule.h holds it as code).  The one
+ * accumulator is a histogram of EXACT INTEGER counts, so no result depends on the order in which the cells are added: every
+ * table and plane equals a numpy restatement bit for bit, and a repeated call gives the same bytes.
+ *
+ * CLASS OF A CELL.  The value of layer `layer` of an mhs_stack (float64, float32 or int16) is converted exactly to double; it
+ * is NA when it is NaN or equals the stack's nodata ("focal"'s rule).  `classes` is a list of K DISTINCT integer CODES,
+ * 1 <= K <= MHS_CLASS_MAX = 256, each in 0 .. 65 535, in any order; the library sorts it ascending, and class index k refers
+ * to the sorted list (info->codes).  A valid cell has class index k when its value equals codes[k] exactly; every other valid
+ * cell -- non-integral, out of 0 .. 65 535, +-Inf, or not listed -- is OTHER.  classes = NULL with n_classes = 0: the library
+ * MEASURES the codes present in the layer: one pass ORs a 65 536-bit presence map, the host reads 8 KiB back; more than 256
+ * distinct codes is MHS_ERR_INVALID with the number found, none at all likewise; valid cells that are no integer in 0 .. 65 535
+ * are `other` and the info counts them.  An output whose size depends on K (the table's counts; frac without frac_of) cannot go
+ * with a measured list: measure first with an info-only call.
+ *
+ * PER UNIT (a zone, a target cell, a window) the integers are: cells (every cell of the unit, crosstab only), n (the valid
+ * cells, `other` included), other, count[k]; each is at most 2^31 - 1, and n = sum_k count[k] + other.
+ *
+ * DERIVED VALUES, each a fixed handful of IEEE operations on those integers (cls_finish of classes_rule.h, used by all three
+ * calls and by the check program):
+ *   frac[k]     (double)count[k] / (double)n;  NA where n = 0
+ *   mode        the code with the largest count; a tie goes to the SMALLER CODE (terra's modal breaks ties by first occurrence
+ *               in the data; this rule does not, because a first occurrence depends on an order of the cells); int32, -1 where
+ *               no listed class occurs
+ *   mode_frac   (double)count[mode] / (double)n;  NA where mode is -1
+ *   variety     the number of k with count[k] > 0 (int32)
+ *   simpson     (double)(n * n - sum_k count[k]^2 - other^2) / ((double)n * (double)n), the numerator an exact uint64 (at most
+ *               2^62);  NA where n = 0.  There is no Shannon index: a log would break bit equality.
+ *   NA is NaN.  A float32 output is the float64 value rounded once.
+ * frac_of names the n_frac_of codes whose frac is wanted, one output per code in the given order; NULL with 0: all K, in
+ * ascending code.  A frac_of code that is not in the list is MHS_ERR_INVALID.
+ *
+ * THE THREE UNITS.
+ *   CROSSTAB: the zones of an int32 zone plane, exactly as in "zonal": nrow x ncol with the row stride ld_zones, a cell belongs
+ *     to zone z when 0 <= z < n_zones, a negative zone is no zone, a zone >= n_zones is MHS_ERR_INVALID naming n_zones (a device
+ *     flag where the plane was not measured: such a cell touches no table and nothing is written), n_zones = 0 measures
+ *     max(zone) + 1.  n_zones * (K + 3) > 2^31 - 1 is MHS_ERR_INVALID.  TABLE, dense, row z is zone z, `capacity` rows in every
+ *     array (n_zones > capacity is MHS_ERR_INVALID naming capacity): counts (int32, capacity x K row-major), n, other, cells,
+ *     mode, variety (int32), mode_frac, simpson (float64), frac (float64, capacity x n_frac row-major).  PLANES put mode,
+ *     mode_frac, variety, simpson, n and frac back on the cells; -1 (int32) or NaN where the cell has no zone.  The "present"
+ *     table form of "zonal" is out of scope: renumber cell-number labels 0 .. Z - 1 first -- the label plane of "patches" by its id
+ *     plane minus 1; the index plane of "flow paths" (basins) NOT through "patches", which labels the connected pieces of a mask
+ *     and would merge basins that touch, but by a sort of the distinct labels (torch.unique, R's match against sort(unique())).
+ *   AGGREGATE: the target cells of another geometry in the same coordinate system.  The unit of target cell (r, c) is the
+ *     source cells whose centre lies in it: the footprint of "resample"'s aggregates (rs_foot_col / rs_foot_row of
+ *     resample_rule.h), unchanged; the footprints partition the source.  The grids are checked as "resample" checks them.  A
+ *     target cell with an empty footprint (outside the source; finer than the source) has n = 0: mode -1, variety 0, NA.
+ *     Products: mode, variety, n (int32), mode_frac, simpson, frac.
+ *   FOCAL: the window of `radius` cells (1 .. max(nrow, ncol)), MHS_FOCAL_SQUARE or MHS_FOCAL_CIRCLE with "focal"'s windows,
+ *     cells outside the raster and NA cells skipped.  Products: frac, mode, mode_frac, variety, n (no simpson).  Where the
+ *     centre is NA every product is NA (-1 for the int32 planes), as "focal" has it without fill_na.  Built by composition,
+ *     one class at a time: class k's 0 / 1 / NoData int16 indicator, "focal"'s own sum of it at offset 0 (exact whatever the
+ *     order of addition: sums of 0 / 1 values stay far below 2^53), and an update of the running best count and code (a strict
+ *     > over ascending codes gives the tie rule) and the variety; the window's n is "focal"'s count.  frac_of names a code
+ *     once.  Several radii in one call are out of scope.
+ *
+ * OUTPUTS: every pointer of the structs below is optional (NULL: not wanted); a call must ask for a table statistic, a plane or
+ * the info.  INFO: K, the codes in force (ascending), n_zones (crosstab; else 0), and over the WHOLE layer n_valid, n_na and
+ * n_other (valid cells that are `other` under the list in force), scratch_bytes.  A call with an info runs the census pass.
+ *
+ * Every refusal is MHS_ERR_INVALID with a message that names the argument and the limit; it comes before any device call, and
+ * nothing is written: K = 0 or K > 256, a code outside 0 .. 65 535, a code named twice, a frac_of code not in the list,
+ * n_zones * (K + 3) too large, a layer out of range, strides smaller than the grid, a bad dtype, no output, a radius or shape
+ * out of range, the grids that "resample" refuses.
+ *
+ * OUT OF SCOPE: a "mode" method inside mhs_resample; the present table form; several radii per focal call; codes outside
+ * 0 .. 65 535 or more than 256 classes; Shannon entropy; fractions weighted by cell area on lon/lat grids; warping categorical
+ * rasters ("warp" with the nearest cell, then this); a median per zone; more than 2^31 - 1 cells.
+ *
+ * The algorithm (csrc/classes.hip), every phase its own launch, a kernel boundary the only ordering.  Code to k:
+ * a direct table in LDS where max code - min code < 1 024, else a bisection in the sorted list in LDS; both give the same k.
+ * CROSSTAB: a workgroup of four waves per strip of 8 tiles of 32 x 64 cells, a wave per row at a time; the work is done per RUN
+ * of equal (zone, slot) along the row: one ballot gives the run heads, the run's length is the distance to the next head, and
+ * only the head adds it, to a table of 1 024 slots in LDS keyed by zone * (K + 3) + slot (one compare-and-swap claims a key, at
+ * most 4 probes) or straight to the global n_zones x (K + 3) uint32 table when it finds no slot; occupied slots are flushed at
+ * the strip's end; then a lane per zone finishes and a lane per cell writes the planes.  AGGREGATE: a workgroup owns a tile of
+ * target cells whose (K + 2)-word counters live in LDS (at most 64 KiB: floor(16 384 / (K + 2)) cells, at most 64 x 64; halved, rows
+ * first, while the target has fewer than 2 048 tiles, so that a small target still fills the device), reads
+ * the tile's source footprint row by row with the same run logic on (target column, slot), and finishes a lane per target cell:
+ * no global atomic, no scratch.  One target cell's footprint is read by one workgroup: a 1 x 1 target over a large source is
+ * slow -- use crosstab with one zone.  SCRATCH, stream-ordered memory given back behind the last kernel: the counter block and
+ * presence map (8 448 bytes); crosstab 4 (K + 3) bytes per zone and 28 more with planes; focal 30 bytes per cell, whatever K,
+ * beside "focal"'s own.  MHS_ERR_ALLOC if there is none. */
+#define MHS_CLASS_MAX 256
+typedef struct mhs_class_table {
+    int64_t capacity;          /* rows that every array below holds */
+    int32_t *counts;           /* capacity x K, row-major; needs a given class list */
+    int32_t *n, *other, *cells, *mode, *variety;
+    double *mode_frac, *simpson;
+    double *frac;              /* capacity x n_frac, row-major */
+} mhs_class_table;
+typedef struct mhs_class_planes {
+    int32_t *mode, *variety, *n;
+    void *mode_frac, *simpson; /* of dtype */
+    void *frac;                /* n_frac planes of dtype, frac_stride elements apart */
+    int64_t ld;                /* the row stride of every plane, in elements */
+    int64_t frac_stride;
+    int dtype;                 /* MHS_F64 or MHS_F32 */
+} mhs_class_planes;
+typedef struct mhs_class_info {
+    int32_t K;                 /* classes in force */
+    int32_t codes[MHS_CLASS_MAX];      /* ascending; the first K */
+    int64_t n_zones;           /* crosstab: as given, or max(zone) + 1 */
+    int64_t n_valid, n_na, n_other;    /* over the whole layer */
+    int64_t scratch_bytes;
+} mhs_class_info;
+/* DEVICE planes: stack->data and zones cover the whole grid; the table's arrays and the planes are on the device.  The stream
+ * is synchronised behind the census where that runs (classes or n_zones measured, or an info), and behind the last kernel
+ * when no info is given (the device flag is read). */
+MHS_API int mhs_class_crosstab_dev(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t ld_zones,
+                                   int64_t n_zones, const int32_t *classes, int n_classes, const int32_t *frac_of, int n_frac_of,
+                                   const mhs_class_table *table, const mhs_class_planes *planes, void *stream, mhs_class_info *info);
+/* same, HOST planes: stack->data, zones (nrow x ncol dense), the table's arrays (n_zones rows: n_zones must be given with a
+ * table) and the planes (nrow x ncol dense; ld and frac_stride are not looked at) on the host -- what the R shim hands over.
+ * Blocks until done. */
+MHS_API int mhs_class_crosstab(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t n_zones,
+                               const int32_t *classes, int n_classes, const int32_t *frac_of, int n_frac_of,
+                               const mhs_class_table *table, const mhs_class_planes *planes, mhs_class_info *info);
+/* DEVICE planes: src_stack covers src_grid; the planes cover dst_grid.  Only enqueues on `stream` unless the classes are
+ * measured or an info is given. */
+MHS_API int mhs_class_aggregate_dev(const mhs_grid *src_grid, const mhs_stack *src_stack, int layer, const mhs_grid *dst_grid,
+                                    const int32_t *classes, int n_classes, const int32_t *frac_of, int n_frac_of,
+                                    const mhs_class_planes *planes, void *stream, mhs_class_info *info);
+/* same, HOST planes (dst nrow x ncol dense).  Blocks until done. */
+MHS_API int mhs_class_aggregate(const mhs_grid *src_grid, const mhs_stack *src_stack, int layer, const mhs_grid *dst_grid,
+                                const int32_t *classes, int n_classes, const int32_t *frac_of, int n_frac_of,
+                                const mhs_class_planes *planes, mhs_class_info *info);
+/* DEVICE planes; shape is MHS_FOCAL_SQUARE or MHS_FOCAL_CIRCLE; planes->simpson must be NULL. */
+MHS_API int mhs_class_focal_dev(const mhs_grid *g, const mhs_stack *stack, int layer, int radius, int shape, const int32_t *classes,
+                                int n_classes, const int32_t *frac_of, int n_frac_of, const mhs_class_planes *planes, void *stream,
+                                mhs_class_info *info);
+
 /* --------------------------------------------------------------- flow paths --
  * Drainage covariates ALONG the flow: height above and distance to the first channel cell that a cell's own water meets (HAND,
  * SAGA's vertical / horizontal distance to channel network), and the basin a cell drains to.  "proximity" takes the stream cell

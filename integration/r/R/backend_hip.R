@@ -469,6 +469,86 @@ mhs_zonal <- function(x, z, stats = "mean", planes = NULL, present = TRUE, n.zon
        info = stats::setNames(out[[3]], c("n_zones", "n_present", "n_cells_in_zones", "n_contributing", "n_nonfinite", "n_inexact", "quantum")))
 }
 
+# ---- categorical layers: class counts, fractions and mode per zone and per coarser cell -------------------------------------------
+# What terra::crosstab and terra::aggregate(fun = "modal") are used for, and how a land-cover raster enters a covariate stack: as
+# class fractions.  Section "classes" of machisplin_hip.h states the rule: a value is the class whose code it equals exactly, every
+# other valid value is `other`, every accumulator is an exact integer count, and a tie of the mode goes to the SMALLER code (terra's
+# modal takes the first occurrence).  classes: the class codes, whole numbers in 0 .. 65535, at most 256 (NULL: the codes present in
+# the layer); frac.of: the codes whose fraction is wanted (NULL: all).
+#
+# mhs_class_crosstab: x, z, n.zones as for mhs_zonal.  stats: any of counts n other cells mode mode_frac variety simpson frac (NULL: no
+# table); planes: any of mode mode_frac variety simpson n frac.  Returns list(table = a data.frame with the column zone -- counts and
+# frac as one column per code, counts_<code> and frac_<code> --, planes = a SpatRaster or NULL, info, codes).  The table is dense:
+# renumber cell-number labels first -- mhs_patches(v = "label") by its "id" layer minus 1; the "index" layer of mhs_flowpath (basins) by
+# match(v, sort(unique(v))) - 1, NOT through mhs_patches, which would merge basins that touch.
+.mhs_class_table <- c("counts", "n", "other", "cells", "mode", "mode_frac", "variety", "simpson", "frac")
+.mhs_class_planes <- c("mode", "mode_frac", "variety", "simpson", "n", "frac")
+.mhs_class_products <- c("mode", "variety", "n", "mode_frac", "simpson", "frac")
+.mhs_class_codes <- function(who, what, v) {
+  if (is.null(v)) return(NULL)
+  if (!length(v) || length(v) > 256L || anyNA(v) || any(v != floor(v)) || any(v < 0 | v > 65535)) stop(who, ": ", what, " must hold 1 .. 256 whole numbers in 0 .. 65535")
+  if (anyDuplicated(v)) stop(who, ": ", what, " names a code twice")
+  as.integer(v)
+}
+.mhs_class_layers <- function(template, lst, names.all, wanted, codes) {
+  layers <- lapply(wanted, function(p) {
+    v <- lst[[match(p, names.all)]]
+    l <- terra::setValues(terra::rast(template[[1]], nlyrs = if (is.matrix(v)) ncol(v) else 1L), v)
+    names(l) <- if (is.matrix(v)) paste0("frac_", codes) else p
+    l
+  })
+  do.call(c, layers)
+}
+mhs_class_crosstab <- function(x, z, classes = NULL, stats = "counts", planes = NULL, frac.of = NULL, n.zones = NULL, layer = 1L) {
+  who <- "mhs_class_crosstab"
+  if (length(setdiff(stats, .mhs_class_table))) stop(who, ": stats must name some of ", paste(.mhs_class_table, collapse = ", "))
+  if (length(setdiff(planes, .mhs_class_planes))) stop(who, ": planes must name some of ", paste(.mhs_class_planes, collapse = ", "))
+  if (!length(stats) && !length(planes)) stop(who, ": no output: stats and planes are both empty")
+  if (terra::ncell(z) != terra::ncell(x) || terra::ncol(z) != terra::ncol(x)) stop(who, ": shape mismatch: z is not on the grid of x")
+  if (!is.null(n.zones) && (is.na(n.zones) || n.zones < 1 || n.zones > 2147483647)) stop(who, ": n.zones must be in 1 .. 2^31 - 1")
+  classes <- .mhs_class_codes(who, "classes", classes); frac.of <- .mhs_class_codes(who, "frac.of", frac.of)
+  if (!is.null(classes) && length(setdiff(frac.of, classes))) stop(who, ": frac.of names a code that is not in classes")
+  stats <- unique(stats); planes <- unique(planes)
+  zv <- terra::values(z[[1]])[, 1]
+  if (any(zv != floor(zv), na.rm = TRUE)) stop(who, ": zones given as fractions are out of scope")
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  bits <- function(v, all) as.integer(sum(2^(match(v, all) - 1)))
+  out <- .Call("mhsr_class_crosstab", .mhs_geom(x), vals, NA_real_, as.integer(zv), c(layer - 1, if (is.null(n.zones)) 0 else n.zones),
+               classes, frac.of, bits(stats, .mhs_class_table), bits(planes, .mhs_class_planes))
+  codes <- out[[4]]
+  fcodes <- if (is.null(frac.of)) codes else frac.of
+  table <- NULL
+  if (length(stats)) {
+    cols <- lapply(stats, function(s) {
+      v <- out[[1]][[match(s, .mhs_class_table)]]
+      if (!is.matrix(v)) return(stats::setNames(data.frame(v), s))
+      stats::setNames(as.data.frame(t(v)), paste0(s, "_", if (s == "counts") codes else fcodes))       # a zone is a column of the shim's matrix
+    })
+    table <- do.call(cbind, c(list(data.frame(zone = seq_len(out[[3]][2]) - 1L)), cols))
+  }
+  list(table = table, planes = if (length(planes)) .mhs_class_layers(x, out[[2]], .mhs_class_planes, planes, fcodes) else NULL,
+       info = stats::setNames(out[[3]], c("K", "n_zones", "n_valid", "n_na", "n_other")), codes = codes)
+}
+# mhs_class_aggregate: every product of layer `layer` of x on the grid of y (one coordinate system), the unit of a cell of y being the
+# cells of x whose centre lies in it (mhs_resample's aggregates).  v: any of mode variety n mode_frac simpson frac.  A SpatRaster with
+# one layer per entry of v (frac: one per code, frac_<code>); attr(, "info") and attr(, "codes").  A cell of y that holds no centre of
+# a cell of x has n = 0, mode NA.
+mhs_class_aggregate <- function(x, y, classes = NULL, v = "mode", frac.of = NULL, layer = 1L) {
+  who <- "mhs_class_aggregate"
+  if (!length(v) || length(setdiff(v, .mhs_class_products))) stop(who, ": v must name some of ", paste(.mhs_class_products, collapse = ", "))
+  classes <- .mhs_class_codes(who, "classes", classes); frac.of <- .mhs_class_codes(who, "frac.of", frac.of)
+  if (!is.null(classes) && length(setdiff(frac.of, classes))) stop(who, ": frac.of names a code that is not in classes")
+  v <- unique(v)
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  out <- .Call("mhsr_class_aggregate", .mhs_geom(x), vals, NA_real_, .mhs_geom(y), c(layer - 1), classes, frac.of,
+               as.integer(sum(2^(match(v, .mhs_class_products) - 1))))
+  if ("mode" %in% v) out[[1]][[1]][out[[1]][[1]] < 0L] <- NA_integer_
+  r <- .mhs_class_layers(y, out[[1]], .mhs_class_products, v, if (is.null(frac.of)) out[[3]] else frac.of)
+  attr(r, "info") <- stats::setNames(out[[2]], c("K", "n_zones", "n_valid", "n_na", "n_other"))
+  attr(r, "codes") <- out[[3]]
+  r
+}
+
 # ---- rasterize: points, lines and polygons burned onto the grid (what terra::rasterize is used for) --------------------------
 # x: a SpatRaster that gives the grid.  coords: a numeric matrix of two columns (x, y) in the grid's coordinate system;
 # part.offsets: 0-based vertex numbers that cut it into parts (a ring of a polygon, a polyline, a run of points), one more than

@@ -8,6 +8,7 @@
 #include <R.h>
 #include <Rinternals.h>
 #include <stdint.h>
+#include <string.h>
 #include "machisplin_hip.h"
 
 static void chk(int rc) { if (rc != MHS_OK) Rf_error("machisplin_hip: %s", mhs_last_error()); }
@@ -673,6 +674,162 @@ SEXP mhsr_zonal(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP opts, SEXP
         SET_VECTOR_ELT(out, 2, inf);
     }
     UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
+/* the class list and frac_of of the two class entries: integer vectors, or NULL (classes: measure them; frac_of: all classes) */
+static int class_codes(SEXP v, const char *who, const char *what, const int32_t **out) {
+    *out = NULL;
+    if (v == R_NilValue) return 0;
+    if (TYPEOF(v) != INTSXP || Rf_xlength(v) < 1 || Rf_xlength(v) > MHS_CLASS_MAX) Rf_error("%s: %s must be NULL or an integer vector of 1 .. 256 codes", who, what);
+    *out = (const int32_t *)INTEGER(v);
+    return (int)Rf_xlength(v);
+}
+static SEXP class_info_vec(const mhs_class_info *info) {          /* c(K, n_zones, n_valid, n_na, n_other) */
+    SEXP inf = Rf_allocVector(REALSXP, 5);
+    REAL(inf)[0] = (double)info->K; REAL(inf)[1] = (double)info->n_zones; REAL(inf)[2] = (double)info->n_valid;
+    REAL(inf)[3] = (double)info->n_na; REAL(inf)[4] = (double)info->n_other;
+    return inf;
+}
+static SEXP class_codes_vec(const mhs_class_info *info) {
+    SEXP codes = Rf_allocVector(INTSXP, info->K);
+    for (int k = 0; k < info->K; ++k) INTEGER(codes)[k] = info->codes[k];
+    return codes;
+}
+
+/* Class counts, fractions and mode per zone (machisplin_hip.h "classes"): what terra::crosstab is used for, and mhs_zonal's missing
+ * mode.  planes, nodata, zones: as for mhsr_zonal; opts: c(layer, n_zones) with layer 0-based and n_zones 0 = max(zone) + 1;
+ * classes: integer vector of the class codes, NULL = the codes present in the layer; frac_of: integer vector of the codes whose
+ * frac is wanted, NULL = all; stats: bit mask of the table's statistics (1 counts, 2 n, 4 other, 8 cells, 16 mode, 32 mode_frac,
+ * 64 variety, 128 simpson, 256 frac), 0 for no table; planes_mask: bit mask of the planes (1 mode, 2 mode_frac, 4 variety,
+ * 8 simpson, 16 n, 32 frac), 0 for none.  Returns list(table, planes, info, codes): table = a list of 9 in that order, one entry per
+ * zone (counts: an integer matrix K x n_zones, frac: a numeric matrix n_frac x n_zones -- a zone is a COLUMN), NULL where not asked
+ * for; planes = a list of 6 in that order, one entry per cell in terra cell order (frac: a matrix ncell x n_frac); info = c(K,
+ * n_zones, n_valid, n_na, n_other); codes = the class codes in force, ascending.  Runs on the HOST entry point.  Measured classes
+ * or n_zones cost a first call for the info. */
+SEXP mhsr_class_crosstab(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP opts, SEXP classes, SEXP frac_of, SEXP stats, SEXP planes_mask) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_class_crosstab");
+    int ts = Rf_asInteger(stats), ps = Rf_asInteger(planes_mask);
+    if (ts == NA_INTEGER || ts < 0 || ts > 511) Rf_error("mhsr_class_crosstab: stats must be a bit mask of 1 counts, 2 n, 4 other, 8 cells, 16 mode, 32 mode_frac, 64 variety, 128 simpson, 256 frac");
+    if (ps == NA_INTEGER || ps < 0 || ps > 63) Rf_error("mhsr_class_crosstab: planes_mask must be a bit mask of 1 mode, 2 mode_frac, 4 variety, 8 simpson, 16 n, 32 frac");
+    if (!ts && !ps) Rf_error("mhsr_class_crosstab: no output: stats and planes_mask are both 0");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 2) Rf_error("mhsr_class_crosstab: opts must be c(layer, n_zones)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_class_crosstab: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 2147483647.0)) Rf_error("mhsr_class_crosstab: n_zones must be 0 (measure it) or in 1 .. 2^31 - 1");
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_class_crosstab: bad grid dimension");
+    R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    if (TYPEOF(zones) != INTSXP || Rf_xlength(zones) != n) Rf_error("mhsr_class_crosstab: zones must be an integer vector of one zone per cell");
+    const int32_t *cl, *fo;
+    int K = class_codes(classes, "mhsr_class_crosstab", "classes", &cl);
+    const int nf_given = class_codes(frac_of, "mhsr_class_crosstab", "frac_of", &fo);
+    int64_t n_zones = (int64_t)o[1];
+    mhs_class_info info;
+    int32_t measured[MHS_CLASS_MAX];
+    memset(&info, 0, sizeof(info));
+    if (K == 0 || n_zones == 0) {                                  /* the library measures the codes and n_zones before the outputs are sized */
+        chk(mhs_class_crosstab(&g, &st, (int)o[0], (const int32_t *)INTEGER(zones), n_zones, cl, K, NULL, 0, NULL, NULL, &info));
+        n_zones = info.n_zones;
+        K = info.K;
+        memcpy(measured, info.codes, sizeof(measured));
+        cl = measured;
+    }
+    const int nf = nf_given ? nf_given : K;
+    const R_xlen_t rows = (R_xlen_t)n_zones;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 4));
+    SEXP tab = PROTECT(Rf_allocVector(VECSXP, 9)), pl = PROTECT(Rf_allocVector(VECSXP, 6));
+    for (int k = 0; k < 9; ++k) SET_VECTOR_ELT(tab, k, R_NilValue);
+    for (int k = 0; k < 6; ++k) SET_VECTOR_ELT(pl, k, R_NilValue);
+    mhs_class_table ct;
+    mhs_class_planes cp;
+    memset(&ct, 0, sizeof(ct));
+    memset(&cp, 0, sizeof(cp));
+    ct.capacity = (int64_t)rows;
+    for (int k = 0; k < 9; ++k) {
+        if (!(ts & (1 << k))) continue;
+        const int is_int = k < 5 || k == 6;
+        SEXP v = k == 0 ? Rf_allocMatrix(INTSXP, K, (int)rows) : k == 8 ? Rf_allocMatrix(REALSXP, nf, (int)rows) : Rf_allocVector(is_int ? INTSXP : REALSXP, rows);
+        SET_VECTOR_ELT(tab, k, v);
+        void *p = is_int ? (void *)INTEGER(v) : (void *)REAL(v);
+        if (k == 0) ct.counts = p; else if (k == 1) ct.n = p; else if (k == 2) ct.other = p; else if (k == 3) ct.cells = p; else if (k == 4) ct.mode = p;
+        else if (k == 5) ct.mode_frac = p; else if (k == 6) ct.variety = p; else if (k == 7) ct.simpson = p; else ct.frac = p;
+    }
+    cp.dtype = MHS_F64;
+    for (int k = 0; k < 6; ++k) {
+        if (!(ps & (1 << k))) continue;
+        const int is_int = k == 0 || k == 2 || k == 4;
+        SEXP v = k == 5 ? Rf_allocMatrix(REALSXP, (int)n, nf) : Rf_allocVector(is_int ? INTSXP : REALSXP, n);
+        SET_VECTOR_ELT(pl, k, v);
+        void *p = is_int ? (void *)INTEGER(v) : (void *)REAL(v);
+        if (k == 0) cp.mode = p; else if (k == 1) cp.mode_frac = p; else if (k == 2) cp.variety = p; else if (k == 3) cp.simpson = p; else if (k == 4) cp.n = p;
+        else cp.frac = p;
+    }
+    const int with_table = ts && rows > 0;
+    int rc = MHS_OK;
+    if (with_table || ps) rc = mhs_class_crosstab(&g, &st, (int)o[0], (const int32_t *)INTEGER(zones), n_zones, cl, K, fo, nf_given, with_table ? &ct : NULL, ps ? &cp : NULL, &info);
+    if (rc == MHS_OK) {
+        SET_VECTOR_ELT(out, 0, tab);
+        SET_VECTOR_ELT(out, 1, pl);
+        SET_VECTOR_ELT(out, 2, class_info_vec(&info));
+        SET_VECTOR_ELT(out, 3, class_codes_vec(&info));
+    }
+    UNPROTECT(3);
+    chk(rc);
+    return out;
+}
+
+/* Class fractions and mode per cell of another grid (machisplin_hip.h "classes"): terra::aggregate(fun = "modal"), and class cover
+ * when land cover is finer than the model grid.  geom_src, planes, nodata, geom_dst: as for mhsr_resample; opts: c(layer), 0-based;
+ * classes, frac_of: as for mhsr_class_crosstab; products: bit mask of 1 mode, 2 variety, 4 n, 8 mode_frac, 16 simpson, 32 frac.
+ * Returns list(planes, info, codes): planes = a list of 6 in that order, one entry per cell of dst in terra cell order (frac: a
+ * matrix ncell x n_frac), NULL where not asked for.  Runs on the HOST entry point. */
+SEXP mhsr_class_aggregate(SEXP geom_src, SEXP planes, SEXP nodata, SEXP geom_dst, SEXP opts, SEXP classes, SEXP frac_of, SEXP products) {
+    mhs_grid gs = grid_from(geom_src), gd = grid_from(geom_dst);
+    mhs_stack st = planes_from(planes, nodata, &gs, "mhsr_class_aggregate");
+    const int pm = Rf_asInteger(products);
+    if (pm == NA_INTEGER || pm < 1 || pm > 63) Rf_error("mhsr_class_aggregate: products must be a bit mask of 1 mode, 2 variety, 4 n, 8 mode_frac, 16 simpson, 32 frac, and not 0");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 1) Rf_error("mhsr_class_aggregate: opts must be c(layer)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_class_aggregate: layer must be a 0-based layer number");
+    if (!(gd.nrow > 0 && gd.ncol > 0 && (double)gd.nrow * (double)gd.ncol <= 2147483647.0)) Rf_error("mhsr_class_aggregate: bad target dimension");
+    const R_xlen_t n = (R_xlen_t)gd.nrow * gd.ncol;
+    const int32_t *cl, *fo;
+    int K = class_codes(classes, "mhsr_class_aggregate", "classes", &cl);
+    const int nf_given = class_codes(frac_of, "mhsr_class_aggregate", "frac_of", &fo);
+    mhs_class_info info;
+    int32_t measured[MHS_CLASS_MAX];
+    memset(&info, 0, sizeof(info));
+    if (K == 0) {                                                  /* the library measures the codes before frac is sized */
+        chk(mhs_class_aggregate(&gs, &st, (int)o[0], &gd, NULL, 0, NULL, 0, NULL, &info));
+        K = info.K;
+        memcpy(measured, info.codes, sizeof(measured));
+        cl = measured;
+    }
+    const int nf = nf_given ? nf_given : K;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SEXP pl = PROTECT(Rf_allocVector(VECSXP, 6));
+    for (int k = 0; k < 6; ++k) SET_VECTOR_ELT(pl, k, R_NilValue);
+    mhs_class_planes cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.dtype = MHS_F64;
+    for (int k = 0; k < 6; ++k) {
+        if (!(pm & (1 << k))) continue;
+        const int is_int = k < 3;
+        SEXP v = k == 5 ? Rf_allocMatrix(REALSXP, (int)n, nf) : Rf_allocVector(is_int ? INTSXP : REALSXP, n);
+        SET_VECTOR_ELT(pl, k, v);
+        void *p = is_int ? (void *)INTEGER(v) : (void *)REAL(v);
+        if (k == 0) cp.mode = p; else if (k == 1) cp.variety = p; else if (k == 2) cp.n = p; else if (k == 3) cp.mode_frac = p; else if (k == 4) cp.simpson = p;
+        else cp.frac = p;
+    }
+    const int rc = mhs_class_aggregate(&gs, &st, (int)o[0], &gd, cl, K, fo, nf_given, &cp, &info);
+    if (rc == MHS_OK) {
+        SET_VECTOR_ELT(out, 0, pl);
+        SET_VECTOR_ELT(out, 1, class_info_vec(&info));
+        SET_VECTOR_ELT(out, 2, class_codes_vec(&info));
+    }
+    UNPROTECT(2);
     chk(rc);
     return out;
 }

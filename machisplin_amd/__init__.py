@@ -23,6 +23,7 @@ from . import project                     # project.project, project.warp: raste
 from . import focal                       # focal.focal: window statistics at any radius
 from . import patches                     # patches.patches, patches.sieve: connected patches of a mask and the size filter
 from . import zonal                       # zonal.zonal: a layer's statistics per zone of an integer zone plane
+from . import classes                     # classes.crosstab, classes.aggregate, classes.focal: categorical layers per zone, cell, window
 from . import vector                      # vector.Features, vector.read_geojson: points, lines and polygons as flat arrays
 from . import rasterize                   # rasterize.rasterize: vector features burned onto the grid
 from .mess import Mess
@@ -35,4 +36,4 @@ __all__ = ["MhsError", "init", "Geometry", "RasterStack", "Tps", "interpolate", 
            "ensemble_predict", "models", "tiles", "mltps", "mltps_predict",
            "tps_residual_surface", "tps_residual_surface_se", "nnet_fit_many", "ksvm_fit_many", "sigest", "fit_layer",
            "fit_nnet_folds", "fit_ksvm_folds", "kfold", "varimp", "mess", "Mess", "terrain", "relief", "geomorphon", "hydro", "hydro_mfd", "covariates", "solar", "sun_tables",
-           "SunTables", "resample", "extract", "align", "proximity", "flowpath", "project", "focal", "patches", "zonal", "vector", "rasterize", "_lib"]
+           "SunTables", "resample", "extract", "align", "proximity", "flowpath", "project", "focal", "patches", "zonal", "classes", "vector", "rasterize", "_lib"]

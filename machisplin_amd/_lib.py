@@ -137,6 +137,24 @@ class ZonalInfo(C.Structure):
                 ("n_nonfinite", C.c_int64), ("n_inexact", C.c_int64), ("quantum", C.c_double), ("scratch_bytes", C.c_int64)]
 
 
+class ClassTable(C.Structure):
+    """struct mhs_class_table"""
+    _fields_ = [("capacity", C.c_int64), ("counts", C.c_void_p), ("n", C.c_void_p), ("other", C.c_void_p), ("cells", C.c_void_p), ("mode", C.c_void_p),
+                ("variety", C.c_void_p), ("mode_frac", C.c_void_p), ("simpson", C.c_void_p), ("frac", C.c_void_p)]
+
+
+class ClassPlanes(C.Structure):
+    """struct mhs_class_planes"""
+    _fields_ = [("mode", C.c_void_p), ("variety", C.c_void_p), ("n", C.c_void_p), ("mode_frac", C.c_void_p), ("simpson", C.c_void_p),
+                ("frac", C.c_void_p), ("ld", C.c_int64), ("frac_stride", C.c_int64), ("dtype", C.c_int)]
+
+
+class ClassInfo(C.Structure):
+    """struct mhs_class_info"""
+    _fields_ = [("K", C.c_int32), ("codes", C.c_int32 * 256), ("n_zones", C.c_int64), ("n_valid", C.c_int64), ("n_na", C.c_int64),
+                ("n_other", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 class Features(C.Structure):
     """struct mhs_features"""
     _fields_ = [("kind", C.c_int), ("n_vertices", C.c_int64), ("n_parts", C.c_int64), ("n_features", C.c_int64), ("coords", C.c_void_p),
@@ -300,6 +318,16 @@ SIGNATURES = {
                                 C.POINTER(ZonalPlanes), _vp, C.POINTER(ZonalInfo)]),
     "mhs_zonal": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, C.c_double, C.c_int, C.POINTER(ZonalTable),
                             C.POINTER(ZonalPlanes), C.POINTER(ZonalInfo)]),
+    "mhs_class_crosstab_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, C.POINTER(ClassTable),
+                                         C.POINTER(ClassPlanes), _vp, C.POINTER(ClassInfo)]),
+    "mhs_class_crosstab": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _vp, C.c_int, _vp, C.c_int, C.POINTER(ClassTable),
+                                     C.POINTER(ClassPlanes), C.POINTER(ClassInfo)]),
+    "mhs_class_aggregate_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(Grid), _vp, C.c_int, _vp, C.c_int,
+                                          C.POINTER(ClassPlanes), _vp, C.POINTER(ClassInfo)]),
+    "mhs_class_aggregate": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.POINTER(Grid), _vp, C.c_int, _vp, C.c_int,
+                                      C.POINTER(ClassPlanes), C.POINTER(ClassInfo)]),
+    "mhs_class_focal_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                      C.POINTER(ClassPlanes), _vp, C.POINTER(ClassInfo)]),
     "mhs_rasterize_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Features), C.c_int, C.c_int, C.POINTER(RasterizeOut), _i64, _vp,
                                     C.POINTER(RasterizeInfo)]),
     "mhs_rasterize": (C.c_int, [C.POINTER(Grid), C.POINTER(Features), C.c_int, C.c_int, C.POINTER(RasterizeOut), _i64, C.POINTER(RasterizeInfo)]),

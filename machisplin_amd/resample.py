@@ -4,7 +4,8 @@ The reference package's README says "All rasters must be the same: resolution, p
 ``terra::crop`` and ``terra::extract`` for the rest.  This module brings stacks in the same coordinate system -- they may differ
 in resolution, origin and extent -- onto one grid: :func:`resample` (nearest, bilinear, cubic; the aggregates mean, min, max,
 sum, count for a coarser target), :func:`extract` at points and :func:`align`, which makes one float32 stack, ready for
-``mltps`` and ``Mess``, from several.  Another coordinate system is ``project``'s part.
+``mltps`` and ``Mess``, from several.  Another coordinate system is ``project``'s part.  A CATEGORICAL raster onto a coarser
+grid -- the mode, or the share of each class in the target cell -- is :func:`classes.aggregate`, over the same footprints.
 include/machisplin_hip.h, section "resample", states the rules.  All arithmetic on the cells runs in libmachisplin_hip.so
 (csrc/resample.hip); this module only marshals arguments.
 """

@@ -33,6 +33,7 @@ PATCH_DIST_SPEC = {"dist_na_edge": ("na", 0), "dist_na_min": ("na", 1), "dist_le
 BASIN_SPEC = {"basin_mean": "mean", "basin_minus_mean": "minus_mean", "basin_dev": "dev"}      # covariates(): spec name -> the plane of zonal
 ZONE_SPEC = {"zone_mean": "mean", "zone_minus_mean": "minus_mean", "zone_dev": "dev"}      # covariates(): spec name -> the plane of zonal, zones from vector features
 DIST_FEATURES = "dist_features"                                         # covariates(): the distance to vector features
+CLASS_SPEC = {"class_frac": 4, "class_cover": 3}                         # covariates(): spec name -> the entry's length (classes.focal / classes.aggregate)
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
 FLOW_OUTLET = "flowdist_outlet"                                         # covariates(): the path length to the root
 FOCAL_SPEC = {"focal_mean": "mean", "focal_sd": "sd", "tpi_scale": "minus_mean", "dev": "dev"}      # covariates(): spec name -> the statistic of focal
@@ -444,6 +445,42 @@ def _vector_layers(dem_stack, spec, layer):
     return out
 
 
+def _class_entry(e):
+    """(categorical stack, layer, code[, radius]) of a "class_frac" / "class_cover" entry, checked"""
+    if len(e) != CLASS_SPEC[e[0]]:
+        raise ValueError(f"{e[0]!r} takes " + ("a categorical RasterStack (or (stack, layer)), a class code and the radius in cells" if e[0] == "class_frac"
+                                               else "a categorical RasterStack (or (stack, layer)) and a class code"))
+    cat, cat_layer = e[1] if isinstance(e[1], tuple) else (e[1], 0)
+    if not isinstance(cat, RasterStack):
+        raise ValueError(f"{e[0]!r}: the categorical raster must be a RasterStack or (RasterStack, layer)")
+    if int(e[2]) != e[2] or not 0 <= int(e[2]) <= 65535:
+        raise ValueError(f"{e[0]!r}: the class code must be an integer in 0 .. 65535, not {e[2]!r}")
+    if e[0] == "class_frac" and int(e[3]) != e[3]:
+        raise ValueError(f"'class_frac': the radius must be a whole number of cells, not {e[3]!r}")
+    return (cat, int(cat_layer), int(e[2])) + ((int(e[3]),) if e[0] == "class_frac" else ())
+
+
+def _class_layers(dem_stack, spec):
+    """the ("class_frac", cat, code, R) and ("class_cover", cat, code) layers of :func:`covariates`: the share of class ``code`` of
+    the categorical raster ``cat`` within R cells (:func:`classes.focal`; ``cat`` on the DEM's own grid) and in the DEM's cell
+    (:func:`classes.aggregate`; ``cat`` on any grid of the same coordinate system).  Entries that share ``cat`` (and R) share one
+    call, whose class list is their codes; keyed (name, id(cat), layer, code[, R])"""
+    import torch
+    from . import classes as _classes
+    entries = [(e[0],) + _class_entry(e) for e in spec if e[0] in CLASS_SPEC]
+    out = {}
+    for name, cat, cat_layer, *rest in dict.fromkeys((n, c, l) + ((r[1],) if n == "class_frac" else ()) for n, c, l, *r in entries):
+        codes = list(dict.fromkeys(en[3] for en in entries if en[:3] == (name, cat, cat_layer) and tuple(en[4:]) == tuple(rest)))
+        if name == "class_frac":
+            if cat.geom != dem_stack.geom:
+                raise ValueError("'class_frac': the categorical raster must be on the DEM's own grid (classes.aggregate, or 'class_cover', brings another grid onto it)")
+            planes, _ = _classes.focal(cat, rest[0], cat_layer, codes, ("frac",), codes, "square", out_dtype=torch.float32)
+        else:
+            planes, _ = _classes.aggregate(cat, dem_stack.geom, cat_layer, codes, ("frac",), codes, out_dtype=torch.float32)
+        out.update({(name, id(cat), cat_layer, code) + tuple(rest): planes["frac"][j] for j, code in enumerate(codes)})
+    return out
+
+
 def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), layer=0, lonlat=False, z_factor=1.0, lat=None, sun=None):
     """A float32 covariate stack made from the DEM, ready for ``mltps``, ``mltps_predict`` and ``Mess``: the DEM first,
     then one layer per entry of ``spec`` --
@@ -493,6 +530,12 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                   an administrative unit, a catchment: the zone's mean elevation, the cell's
                                                   elevation minus it, and that over the zone's sample sd (one rasterize call and
                                                   one :func:`zonal.zonal` call per distinct ``feats`` make all three; NaN outside)
+      ("class_frac", cat, code, R)                the share of class ``code`` among the valid cells of the categorical raster ``cat`` -- a
+                                                  land-cover RasterStack on the DEM's own grid, or (stack, layer) -- within the square
+                                                  window of R cells (:func:`classes.focal`'s ``frac``; NaN where ``cat`` is NA)
+      ("class_cover", cat, code)                  the share of class ``code`` among the cells of ``cat`` -- on any grid of the same
+                                                  coordinate system -- whose centre lies in the DEM's cell (:func:`classes.aggregate`'s
+                                                  ``frac``; entries that share ``cat``, and R, share one call)
     NA cells are NaN (the stack's nodata is NaN).  The returned RasterStack carries the layers' names in ``.names``."""
     import torch
     spec = [(e,) if isinstance(e, str) else tuple(e) for e in spec]
@@ -527,6 +570,8 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             if len(e) != 1 + n_args or (n_args and (int(e[-1]) != e[-1] or int(e[-1]) < 1)):
                 raise ValueError(f"{e[0]!r} takes " + ("no argument", "one argument, the smallest patch in cells (a whole number >= 1)",
                                                        "a threshold and the smallest patch in cells (a whole number >= 1)")[n_args])
+        if e[0] in CLASS_SPEC:
+            _class_entry(e)
     stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
     flow_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in FLOW_SPEC))
     basins = tuple(dict.fromkeys(BASIN_SPEC[e[0]] for e in spec if e[0] in BASIN_SPEC))
@@ -584,8 +629,14 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             by_name[e] = _prox.proximity(keep, products="dist", unit=g.xres, out_dtype=torch.float32)[0]
     if any(e[0] in ZONE_SPEC or e[0] == DIST_FEATURES for e in spec):
         by_name.update(_vector_layers(dem_stack, spec, layer))
+    if any(e[0] in CLASS_SPEC for e in spec):
+        by_name.update(_class_layers(dem_stack, spec))
     for k, e in enumerate(spec):
-        if e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
+        if e[0] in CLASS_SPEC:
+            cat, cat_layer, *rest = _class_entry(e)
+            planes[1 + k] = by_name[(e[0], id(cat), cat_layer) + tuple(rest)]
+            names.append(e[0] + "_".join(str(v) for v in rest))
+        elif e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
             planes[1 + k] = by_name[(e[0], id(e[1]))]
             names.append(e[0])
         elif e[0] in PATCH_DIST_SPEC:

@@ -8,6 +8,8 @@ include/machisplin_hip.h, section "zonal", states the rule: the values are quant
 no result depends on the order of addition and every table and plane equals a numpy and Python-int restatement bit for bit.
 All work on the cells runs in libmachisplin_hip.so (csrc/zonal.hip); this module only marshals arguments.
 
+The classes of a CATEGORICAL layer per zone -- counts, fractions, the mode -- are :func:`classes.crosstab`.
+
 Out of scope: median and mode per zone, zones given as floats, more than 2^31 - 1 cells, weights (a cell's area on a lon/lat
 grid).
 """
