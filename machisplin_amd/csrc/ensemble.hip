@@ -1020,6 +1020,15 @@ __global__ __launch_bounds__(256, 5) void gbm_lutreg_rt_kernel(const double *__r
 // times) fall to the last case for every tree, which is slower than gbm_lutreg_rt_kernel: launch_gbm_lut samples the
 // grid first and takes this kernel only where it pays.
 // Block = 16 waves; the chunk's leaf LUT (16 KB) and class words (1.25 KB) are staged in LDS for all of them, double-buffered.
+// Class word of level q of tree t (lut_cls, private to this kernel): rank threshold << 3 | predictor, 0 for a padding level;
+// thresholds stay below 2^20 (build_lut_meta_t publishes no class words otherwise and the model keeps off this kernel).
+// The lane = tree code keeps per lane the 5-bit mask of the straddling levels, their count, the leaf index of the others
+// (`known`), B, and for one or two straddling levels the scaled leaf differences plus the one or two class words, which it
+// re-reads from LDS at the level the mask's leading bit names and repacks as (threshold as a float's bits | predictor).  The
+// cell loops fetch that word with one v_readlane and split it on the scalar unit; the three-or-more loop reads the tree's mask
+// and walks its set bits with scalar branches, one v_readlane of the level's word each.  There are no per-lane lists of
+// (threshold, predictor, bit position) any more: they cost every lane 27 to ~100 vector instructions per chunk whenever one
+// lane of the wave had a straddling level (profiles/gbm_coherent_classify.txt).
 constexpr int GBC_WAVES = 16;
 __device__ __forceinline__ double gbc_lds_f64(unsigned a) { return *(__attribute__((address_space(3))) const double *)(uintptr_t)a; }
 typedef float float4v __attribute__((ext_vector_type(4)));
@@ -1117,9 +1126,9 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
         for (int q = 0; q < S; ++q) w[q] = cw[q];
 #pragma unroll
         for (int q = 0; q < S; ++q) mm[q] = srange[wave * 8 + (int)(w[q] & 7u)];
-        // (round 5: the straddling levels are first collected as a 5-bit mask and their (c, predictor, bit position) lists are
-        // filled from it only in lanes that have any -- one at a time, most significant bit = first level -- instead of 25
-        // predicated moves per lane and chunk: the classification is the whole price of a tree without a straddling split)
+        // the straddling levels as a 5-bit mask (most significant bit = first level) and the other levels' outcomes as the
+        // leaf index `known`: the whole price of a tree without a straddling split.  No list of the straddling levels is kept
+        // per lane: what a straddling tree's cell loop needs is taken from its class words when the loop reaches the tree
         unsigned known = 0u, smask = 0u;
 #pragma unroll
         for (int q = 0; q < S; ++q) {
@@ -1129,24 +1138,6 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
             if (!(all1 || all0)) smask |= 16u >> q;
         }
         const unsigned nstr = (unsigned)__popc(smask);
-        unsigned cl[S], vl[S];     // the straddling levels in level order: c as a float's bits; 4 * predictor | bit position << 8
-#pragma unroll
-        for (int q = 0; q < S; ++q) { cl[q] = 0u; vl[q] = 0u; }
-        {
-            unsigned sm = smask;
-#pragma unroll
-            for (int l = 0; l < S; ++l) {
-                if (sm) {                                              // (nested: level l + 1 is looked at only behind level l)
-                    const int pos = 31 - __clz((int)sm);               // bit position of the level in the leaf index; level q = 4 - pos
-                    unsigned wq = w[S - 1];
-#pragma unroll
-                    for (int k = 0; k < S - 1; ++k) if (pos == S - 1 - k) wq = w[k];
-                    cl[l] = __float_as_uint((float)(int)(wq >> 3));
-                    vl[l] = ((wq & 7u) << 2) | ((unsigned)pos << 8);
-                    sm &= ~(1u << pos);
-                } else break;
-            }
-        }
         if (PROBE) {
             if (nstr) pcost += 85 + 26 * (int)nstr;
             if (more) {
@@ -1164,21 +1155,36 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
         //     B + b1 (A1 - B) + b2 ((A2 - B) + b1 (A12 - A1 - A2 + B)),     A1, A2, A12 = the leaves with bit 1 / bit 2 / both set.
         // The cell loops below form a predicate as the float clamp(c - rank) written into the HIGH word of a register pair
         // whose low word is 0: read as a double that is 0 or 2^-7, so the differences are scaled by 2^7 (2^14) here -- exact.
+        // f1, f2: the class words of the first and the second straddling level, re-read from LDS at the position that the
+        // mask's leading bit gives (level q = bit 4 - q of the leaf index) and put into the cell loops' form: the threshold
+        // as a float's bits | predictor (thresholds stay below 2^20, or build_lut_meta_t publishes no class words: the
+        // float's low three bits are zero)
         double d1 = 0.0, d2 = 0.0, d12 = 0.0;
+        unsigned f1 = 0u, f2 = 0u;
         if (single || pair) {
-            const unsigned p1 = 1u << (vl[0] >> 8), p2 = 1u << (vl[1] >> 8);
+            const int pos1 = 31 - __clz((int)(smask | 1u));
+            const unsigned p1 = 1u << pos1;
+            f1 = cw[S - 1 - pos1];
             const double A1 = L[known + p1];
             d1 = (A1 - B) * 128.0;
             if (pair) {
+                const int pos2 = 31 - __clz((int)((smask & ~p1) | 1u));
+                const unsigned p2 = 1u << pos2;
+                f2 = cw[S - 1 - pos2];
                 const double A2 = L[known + p2], A12 = L[known + p1 + p2];
                 d2 = (A2 - B) * 128.0;
                 d12 = (((A12 - A1) - A2) + B) * 16384.0;
             }
+            f1 = __float_as_uint((float)(int)(f1 >> 3)) | (f1 & 7u);
+            f2 = __float_as_uint((float)(int)(f2 >> 3)) | (f2 & 7u);      // (a single's f2 is 0 and stays 0: no branch for it)
         }
         // ---- lane = cell.  What a tree needs sits in the registers of the lane that classified it and is fetched from
-        // there with v_readlane (no list in LDS, no wait); the predictor's ranks are picked with the VGPR index mode.
+        // there with v_readlane (no list in LDS, no wait): one class word per straddling level, whose two fields come apart
+        // on the scalar unit; the predictor's ranks are picked with the VGPR index mode.
 #define MHS_GBC_RL(x) __builtin_amdgcn_readlane((int)(x), t)
 #define MHS_GBC_RLD(x) __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), t), __builtin_amdgcn_readlane(__double2loint(x), t))
+#define MHS_GBC_THR(fw) (int)((unsigned)(fw) & ~7u)
+#define MHS_GBC_VO(fw) (int)(((unsigned)(fw) & 7u) << 2)
 #define MHS_GBC_BITS(h0, h1, h2, h3, vo, cc)                                                                 \
         asm volatile("s_set_gpr_idx_on %[v], 0x1\n\t"                                                        \
                      "v_add_f32_e64 %[a], v64, %[c] clamp\n\t"                                               \
@@ -1190,7 +1196,8 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
                      : "{v[64:95]}"(keys), [v] "s"(vo), [c] "s"(cc));
         for (unsigned long long m1 = __builtin_amdgcn_ballot_w64(single); m1; m1 &= m1 - 1ull) {
             const int t = (int)__builtin_ctzll(m1);
-            const int cc = MHS_GBC_RL(cl[0]), vo = MHS_GBC_RL(vl[0]) & 0xFF;
+            const int fw = MHS_GBC_RL(f1);
+            const int cc = MHS_GBC_THR(fw), vo = MHS_GBC_VO(fw);
             const double e1 = MHS_GBC_RLD(d1);
             int h[R];
             MHS_GBC_BITS(h[0], h[1], h[2], h[3], vo, cc)
@@ -1199,7 +1206,8 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
         }
         for (unsigned long long mp = __builtin_amdgcn_ballot_w64(pair); mp; mp &= mp - 1ull) {
             const int t = (int)__builtin_ctzll(mp);
-            const int c1 = MHS_GBC_RL(cl[0]), v1 = MHS_GBC_RL(vl[0]) & 0xFF, c2 = MHS_GBC_RL(cl[1]), v2 = MHS_GBC_RL(vl[1]) & 0xFF;
+            const int fa = MHS_GBC_RL(f1), fb = MHS_GBC_RL(f2);
+            const int c1 = MHS_GBC_THR(fa), v1 = MHS_GBC_VO(fa), c2 = MHS_GBC_THR(fb), v2 = MHS_GBC_VO(fb);
             const double e1 = MHS_GBC_RLD(d1), e2 = MHS_GBC_RLD(d2), e12 = MHS_GBC_RLD(d12);
             int h[R], k[R];
             MHS_GBC_BITS(h[0], h[1], h[2], h[3], v1, c1)
@@ -1213,23 +1221,32 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
         }
 #undef MHS_GBC_BITS
 #undef MHS_GBC_RLD
-#undef MHS_GBC_RL
         // Three or more: their straddling levels only (the others' bits are in `known`), each a packed predicate and a packed
         // multiply-add that drops the bit into the slot, which is kept as a float 2^23 + slot (its bit pattern is the LUT's
         // dword index plus a constant)
         const unsigned abase = (unsigned)buf * (unsigned)((CH << S) * sizeof(double)) - 0x58000000u;
-        for (unsigned long long m2 = __builtin_amdgcn_ballot_w64(multi); m2; m2 &= m2 - 1ull) {
+        unsigned long long m2 = __builtin_amdgcn_ballot_w64(multi);
+        // the five class words in the cell loops' form, repacked only in a chunk where some lane has three or more (the
+        // copy before gives wf a defined value in the others, where the loop below does not run)
+        unsigned wf[S];
+#pragma unroll
+        for (int q = 0; q < S; ++q) wf[q] = w[q];
+        if (m2) {
+#pragma unroll
+            for (int q = 0; q < S; ++q) wf[q] = __float_as_uint((float)(int)(w[q] >> 3)) | (w[q] & 7u);
+        }
+        for (; m2; m2 &= m2 - 1ull) {
             const int t = (int)__builtin_ctzll(m2);
-            const int n = __builtin_amdgcn_readlane((int)nstr, t);
-            const float a0 = __uint_as_float(0x4B000000u + ((unsigned)t << S) + (unsigned)__builtin_amdgcn_readlane((int)known, t));
+            const unsigned sm = (unsigned)MHS_GBC_RL(smask);
+            const float a0 = __uint_as_float(0x4B000000u + ((unsigned)t << S) + (unsigned)MHS_GBC_RL(known));
             float2v s01 = {a0, a0}, s23 = {a0, a0};
 #pragma unroll
-            for (int l = 0; l < S; ++l) {
-                if (l < n) {
-                    const unsigned long long cc = (unsigned)__builtin_amdgcn_readlane((int)cl[l], t);
-                    const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)vl[l], t);
-                    const int vo = (int)(vw & 0xFFu);
-                    const unsigned long long wb = (127u + (vw >> 8)) << 23;
+            for (int q = 0; q < S; ++q) {
+                if (sm & (16u >> q)) {                                  // (the slot is a sum of exact integers: any order)
+                    const int fw = MHS_GBC_RL(wf[q]);
+                    const unsigned long long cc = (unsigned)MHS_GBC_THR(fw);
+                    const int vo = MHS_GBC_VO(fw);
+                    const unsigned long long wb = (127u + (unsigned)(S - 1 - q)) << 23;
                     float2v b01, b23;
                     asm volatile("s_set_gpr_idx_on %[vo], 0x1\n\t"
                                  "v_pk_add_f32 %[b01], v[64:65], %[cc] op_sel_hi:[1,0] clamp\n\t"
@@ -1246,6 +1263,9 @@ __global__ __launch_bounds__(1024) void gbm_coherent_kernel(const double *__rest
             acc[2] = acc[2] + gbc_lds_f64(__float_as_uint(s23.x) * 8u + abase);
             acc[3] = acc[3] + gbc_lds_f64(__float_as_uint(s23.y) * 8u + abase);
         }
+#undef MHS_GBC_VO
+#undef MHS_GBC_THR
+#undef MHS_GBC_RL
         // ---- the next chunk into the other buffer
         if (more) {
             double *ld = slut + (buf ^ 1) * (CH << S);
@@ -1571,7 +1591,10 @@ static int build_lut_meta_t(mhs_model *m, const mhs_grid &grid, int C) {
                 const unsigned c = (unsigned)(std::lower_bound(sv.begin(), sv.end(), tkey[(size_t)t * S + q]) - sv.begin()) + 1u;
                 cw[(size_t)t * 5 + q] = (c << 3) | (unsigned)v;
             }
-        if (int rc = publish(m, cw, &m->lut_cls)) return rc;
+        bool fits = true;                 // the kernel packs a threshold as a float with the predictor in its low three bits
+        for (int v = 0; v < m->p; ++v) fits = fits && sorted[(size_t)v].size() < ((size_t)1 << 20);
+        if (fits) { if (int rc = publish(m, cw, &m->lut_cls)) return rc; }
+        else if (m->lut_cls) { m->retired.push_back((void *)m->lut_cls); m->lut_cls = nullptr; }
     }
     if (int rc = publish(m, flat, (KT **)&m->lut_sorted)) return rc;
     if (int rc = publish(m, off, &m->lut_sorted_off)) return rc;
