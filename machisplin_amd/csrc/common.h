@@ -59,7 +59,7 @@ struct Context {
     unsigned long long *svr_pool = nullptr;
     hipEvent_t svr_pool_ev[SVR_POOL_SLOTS] = {};
     unsigned svr_pool_next = 0;
-    int svr_rt_blocks_per_cu[16] = {};    // by P: resident blocks of svr_rt_resident_kernel<P> per compute unit (0 = not asked yet)
+    int svr_rt_blocks_per_cu[16] = {};    // by P: resident blocks of svr_rt_resident_kernel<P> per compute unit (0 = not asked yet); entry 0 (no such P): the form with the hand-scheduled loop
     double *points_arena = nullptr;       // grow-only device scratch of mhs_residual_points
     size_t points_arena_cap = 0;          // in doubles
     // grow-only device scratch of mhs_mosaic_feather_dev (sums, counts, seam boxes), one per mosaic lane: lane 0 = the calling

@@ -324,13 +324,20 @@ __global__ __launch_bounds__(256) void svr_kernel(const double *__restrict__ svp
 // are hoisted out of that loop into vector registers for the whole kernel (141 VGPRs at P = 5; held to 128 the compiler
 // spills them, 44 bytes of scratch); the callee keeps them to itself.  The same function, the same bits.
 __device__ __attribute__((noinline)) double svr_rt_exp_call(double z) { return exp(z); }
+// HAND (P = 5, R = 3, TAB2; the resident kernel's default): the support-vector loop of a staged chunk is the hand-scheduled
+// block of svr_rt_loop5.inc / svr_rt_loop5q.inc (tools/gen_svr_rt_asm.py) -- the same vector instructions on the same
+// values in the same order as the compiler's loop below, so the same bits.  The compiler's loop drains lgkmcnt(0) directly
+// behind every table read and behind every support vector's scalar load.  The block keeps two table reads in flight on
+// three register sets and waits with counted lgkmcnt(N); the next support vector's record (double-buffered in 2 x 8
+// scalar registers) and ap are requested a support vector ahead and drained once, where the drain is cheapest.
 // One tile: the 64 R cells of row `row` from column `tcol` on, R cells per lane.  aw is the wave's own 1 KB of LDS.
-template <int P, int R, bool TAB2, bool EXPCALL>
+template <int P, int R, bool TAB2, bool EXPCALL, bool HAND = false>
 __device__ __forceinline__ void svr_rt_tile(const double *__restrict__ svp, int nsv, int stride, int npos,
                                             const double *__restrict__ xcs, const double *etab, double *aw, double sigma, double b,
                                             double amax, double y_center, double y_scale, const StackDev &s, const PredGeom &g,
                                             int row, int tcol, int lane, double weight, int accumulate, double *__restrict__ out) {
     constexpr int CH = 128;
+    static_assert(!HAND || (P == 5 && R == 3 && TAB2), "svr_rt_loop5*.inc are written for P = 5, R = 3 and the 64 KB table");
     double x[R][P], q[R], acc[R], accn[R];
     bool na[R], ok[R];
     int col[R];
@@ -367,7 +374,7 @@ __device__ __forceinline__ void svr_rt_tile(const double *__restrict__ svp, int 
     const bool fold = __builtin_amdgcn_readfirstlane((int)(qhi - qlo <= 0.5)) != 0;   // false too when every cell of the wave is NA (qhi = -1, qlo = 2e300)
     const double S = fold ? qhi : 0.0;
     double magic = 0.0, c1 = 0.0;
-    if constexpr (TAB2) rt_exp_consts(magic, c1);
+    if constexpr (TAB2 && !HAND) rt_exp_consts(magic, c1);      // the hand-scheduled loop sets its own two registers
     auto sum_range = [&](int v0, int v1, double (&a)[R], auto folded) {
         constexpr bool FOLD = decltype(folded)::value;
         auto pair = [&](const double *sp, const double ap) {
@@ -388,6 +395,42 @@ __device__ __forceinline__ void svr_rt_tile(const double *__restrict__ svp, int 
                 aw[e] = fma(sp[P - 1], xlat, sp[P]) + S;
             }
             __builtin_amdgcn_wave_barrier();
+            if constexpr (HAND) {
+                // nt pipelined trips of four, then rem = 1 .. 4 support vectors on their own (tools/gen_svr_rt_asm.py)
+                int nt = (n - 1) >> 2;
+                const int rem = n - 4 * nt;
+                unsigned ca = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double *)aw;
+                const double *rec = svp + (int64_t)vb * stride;          // the chunk's first record; stride * 8 bytes to the next
+                const int rec_bytes = stride * (int)sizeof(double);
+                const double NK = -EXP_RANGE * EXP_SCALE, NMAGIC = -RT_EXP_MAGIC, C2 = 0.5 / (EXP_SCALE * EXP_SCALE);
+                constexpr unsigned long long MGB = __builtin_bit_cast(unsigned long long, RT_EXP_MAGIC),
+                                             C1B = __builtin_bit_cast(unsigned long long, RT_EXP_C1);
+#define MHS_SVR_LOOP_CLOBBERS                                                                                                       \
+    "memory", "scc", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98",     \
+        "s99", "s100", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114",       \
+        "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"
+#define MHS_SVR_LOOP_X                                                                                                              \
+    [x00] "v"(x[0][0]), [x01] "v"(x[0][1]), [x02] "v"(x[0][2]), [x03] "v"(x[0][3]), [x10] "v"(x[1][0]), [x11] "v"(x[1][1]),        \
+        [x12] "v"(x[1][2]), [x13] "v"(x[1][3]), [x20] "v"(x[2][0]), [x21] "v"(x[2][1]), [x22] "v"(x[2][2]), [x23] "v"(x[2][3]),    \
+        [mglo] "i"((unsigned)MGB), [mghi] "i"((unsigned)(MGB >> 32)), [c1lo] "i"((unsigned)C1B),                    \
+        [c1hi] "i"((unsigned)(C1B >> 32)), [rem] "s"(rem), [sp] "s"(rec), [st] "s"(rec_bytes), [nk] "s"(NK), [nm] "s"(NMAGIC),     \
+        [c2] "s"(C2)
+                if constexpr (FOLD)
+                    asm volatile(
+#include "svr_rt_loop5.inc"
+                        : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [ca] "+v"(ca), [nt] "+s"(nt)
+                        : MHS_SVR_LOOP_X
+                        : MHS_SVR_LOOP_CLOBBERS);
+                else
+                    asm volatile(
+#include "svr_rt_loop5q.inc"
+                        : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [ca] "+v"(ca), [nt] "+s"(nt)
+                        : MHS_SVR_LOOP_X, [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2])
+                        : MHS_SVR_LOOP_CLOBBERS);
+#undef MHS_SVR_LOOP_X
+#undef MHS_SVR_LOOP_CLOBBERS
+                continue;
+            }
             const double *sp = svp + (int64_t)vb * stride;
             const double *ar = aw;
             int e = 0;
@@ -416,13 +459,13 @@ __device__ __forceinline__ void svr_rt_tile(const double *__restrict__ svp, int 
 }
 
 // A tile by its index, for the resident kernel (exp() as a call).
-template <int P, int R, bool TAB2>
+template <int P, int R, bool TAB2, bool HAND>
 __device__ __forceinline__ void svr_rt_run(int64_t tile, const double *__restrict__ svp, int nsv, int stride, int npos,
                                            const double *__restrict__ xcs, const double *etab, double *aw, double sigma, double b,
                                            double amax, double y_center, double y_scale, const StackDev &s, const PredGeom &g,
                                            int tiles_per_row, int lane, double weight, int accumulate, double *__restrict__ out) {
     const int row = (int)(tile / tiles_per_row), tcol = (int)(tile - (int64_t)row * tiles_per_row) * (64 * R);
-    svr_rt_tile<P, R, TAB2, true>(svp, nsv, stride, npos, xcs, etab, aw, sigma, b, amax, y_center, y_scale, s, g, row, tcol, lane, weight,
+    svr_rt_tile<P, R, TAB2, true, HAND>(svp, nsv, stride, npos, xcs, etab, aw, sigma, b, amax, y_center, y_scale, s, g, row, tcol, lane, weight,
                                   accumulate, out);
 }
 template <int NW, bool TAB2>
@@ -482,12 +525,22 @@ inline void svr_rt_field_counts(const PredGeom &g, const StackDev &s) {      // 
     (void)g0; (void)g1; (void)g2; (void)g3; (void)g4; (void)g5; (void)g6; (void)g7; (void)g8;
     (void)s0; (void)s1; (void)s2; (void)s3; (void)s4; (void)s5; (void)s6; (void)s7;
 }
-template <int P, int R, int NW, bool TAB2, int WPS>
+// The block's LDS as ONE object, the table first: the hand-scheduled loop reads the table at the LDS address its 16-bit
+// shift produces, with no base added, so the table must sit at address 0.
+template <int NW, bool TAB2>
+struct alignas(16) SvrRtLds {
+    double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
+    double aw[NW][128];
+};
+template <int P, int R, int NW, bool TAB2, int WPS, bool HAND>
 __global__ __launch_bounds__(64 * NW, WPS) void svr_rt_resident_kernel(const double *__restrict__ svp, const double *__restrict__ xcs,
                                                                   const double *__restrict__ gtab, double *__restrict__ out,
                                                                   unsigned long long *__restrict__ pool, SvrRtScalars sc) {
-    __shared__ double etab[TAB2 ? EXP_TAB2_N : EXP_TAB_N];
-    __shared__ double aw[NW][128];
+    __shared__ SvrRtLds<NW, TAB2> lds;
+    double *const etab = lds.etab;
+    auto &aw = lds.aw;
+    if constexpr (HAND)      // decided when the kernel is compiled: no instruction is left of it
+        if ((unsigned)(uintptr_t)(__attribute__((address_space(3))) double *)lds.etab != 0u) __builtin_trap();
     svr_rt_stage<NW, TAB2>(etab, gtab);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -503,7 +556,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void svr_rt_resident_kernel(const dou
         const PredGeom g = {k->g.xmin, k->g.ymax, k->g.xres, k->g.yres, k->g.r0, k->g.c0, k->g.nr, k->g.nc, k->g.ld_out};
         if (tile >= (int64_t)g.nr * k->tiles_per_row) return;
         const StackDev s = {k->s.data, k->s.C, k->s.dtype, k->s.plane_stride, k->s.ld, k->s.nodata, k->s.has_nodata, k->s.all_from_planes};
-        svr_rt_run<P, R, TAB2>(tile, svp, k->nsv, k->stride, k->npos, xcs, etab, aw[wave], k->sigma, k->b, k->amax,
+        svr_rt_run<P, R, TAB2, HAND>(tile, svp, k->nsv, k->stride, k->npos, xcs, etab, aw[wave], k->sigma, k->b, k->amax,
                                k->y_center, k->y_scale, s, g, k->tiles_per_row, lane, k->weight, k->accumulate, out);
     }
 }
@@ -1364,12 +1417,16 @@ static void launch_nnet(const mhs_model *m, const StackDev &s, const PredGeom &g
 // slower than two of 8; with resident waves no wave waits for a block-mate, the block's shape is free, and one block per CU
 // stages the table once instead of twice: a cfg3 step takes 230.1 ms with the one-tile form in 2 x 8 and 224.3 resident in 1 x 16
 // (resident in 2 x 8: 4.4 ms more than in 1 x 16).  Short tiles at row ends were measured on top and not kept (-0.7 ms, within noise).
+// P = 5: the support-vector loop of a chunk is the hand-scheduled block of svr_rt_loop5*.inc (two table reads in flight,
+// counted waits, the records double-buffered in scalar registers; profiles/ksvm_pair_schedule.txt); P = 3, 4 keep the
+// compiler's loop, which MHS_SVR_CXX_LOOP selects at P = 5 as well (the same planes, bit for bit).
 // Larger P keep the one-tile kernel with table_exp_neg_acc, the 32 KB table and blocks of 4 waves, as before.  P = 7 resident
 // with the 64 KB table in one block of 12 was TIMED at cfg5 (3 087 -> 2 898 ms per step) but its planes were never checked
 // on a device, so it is not used; P = 6 and P = 8 .. 12 were measured in no form.
 constexpr bool svr_rt_tab2(int P) { return P <= 5; }       // and with it resident waves
 constexpr int svr_rt_waves_per_simd(int P) { return P <= 5 ? 4 : 3; }   // what the resident form is compiled for (its register budget)
 constexpr int svr_rt_waves(int P) { return svr_rt_tab2(P) ? 16 : 4; }
+constexpr bool svr_rt_hand(int P) { return P == 5; }       // the hand-scheduled support-vector loop (svr_rt_loop5*.inc); P = 3, 4 keep the compiler's
 
 // The tile counter of one resident launch.  A slot's ring holds SVR_POOL_SLOTS counters; a launch takes the next one, zeroes
 // it on its OWN stream ahead of the kernel and records the slot's event behind the kernel.  The launch that takes the same
@@ -1402,10 +1459,14 @@ static int launch_svr(const mhs_model *m, const StackDev &s, const PredGeom &g, 
         constexpr int NW = svr_rt_waves(P);
         const int64_t covering = (ntiles + NW - 1) / NW;       // blocks whose waves cover the tiles one each
         if constexpr (svr_rt_tab2(P)) {
-            auto kern = svr_rt_resident_kernel<P, R, NW, true, svr_rt_waves_per_simd(P)>;
+            // MHS_SVR_CXX_LOOP: the compiler's support-vector loop where the hand-scheduled one is the default (the same planes)
+            const bool hand = svr_rt_hand(P) && !getenv("MHS_SVR_CXX_LOOP");
+            auto kern = svr_rt_resident_kernel<P, R, NW, true, svr_rt_waves_per_simd(P), false>;
+            if constexpr (svr_rt_hand(P))
+                if (hand) kern = svr_rt_resident_kernel<P, R, NW, true, svr_rt_waves_per_simd(P), true>;
             Context &c = ctx();
             std::lock_guard<std::mutex> lk(svr_pool_mu[current_slot()]);
-            int &per_cu = c.svr_rt_blocks_per_cu[P];            // blocks of this form a compute unit holds; the slot's own, under its mutex
+            int &per_cu = c.svr_rt_blocks_per_cu[hand ? 0 : P];   // blocks of this form a compute unit holds (index 0: the hand loop, P = 5 only); the slot's own, under its mutex
             if (per_cu == 0) {
                 int n = 0;
                 MHS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kern, 64 * NW, 0));
