@@ -1261,8 +1261,8 @@ MHS_API int mhs_patches(const mhs_grid *g, const mhs_stack *stack, int layer, in
  * nrow * ncol <= INT32_MAX, 0 <= n_zones <= INT32_MAX, quantum 0 or a power of two, the layer in range, ld_zones >= ncol, each
  * requested plane's ld >= ncol, the planes' dtype, capacity >= 0, no unknown bit in flags, some output.
  *
- * OUT OF SCOPE: median and mode per zone; zones given as floats; more than 2^31 - 1 cells; weights (the area of a cell on a
- * lon/lat grid).
+ * OUT OF SCOPE: the median and other quantiles per zone (section "zonal quantiles" below), the mode ("classes"); zones given
+ * as floats; more than 2^31 - 1 cells; weights (the area of a cell on a lon/lat grid).
  *
  * The algorithm (csrc/zonal.hip), every phase its own launch, a kernel boundary the only ordering: (1) range and
  * zone check: max|v|, max(zone), the +-Inf count -- skipped when quantum and n_zones are given and info is NULL; (2) accumulate:
@@ -1309,6 +1309,124 @@ MHS_API int mhs_zonal_dev(const mhs_grid *g, const mhs_stack *stack, int layer, 
  * the planes come down.  Blocks until done. */
 MHS_API int mhs_zonal(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t n_zones, double quantum, int flags,
                       const mhs_zonal_table *table, const mhs_zonal_planes *planes, mhs_zonal_info *info);
+
+/* --------------------------------------------------------------------- sort --
+ * A device sort of 64-bit keys: the primitive that order statistics need ("zonal quantiles" below is built on it).  keys[0 .. n)
+ * on the device become ASCENDING IN PLACE; the result is always in `keys`, whichever buffer the last pass ended in.  Only the
+ * bits bit_lo .. bit_hi - 1 are looked at: THE CALLER GUARANTEES that the keys are equal outside that window (it is not
+ * checked; keys that differ only outside it keep their input order).  0 <= n <= INT32_MAX, 0 <= bit_lo <= bit_hi <= 64.
+ *
+ * THE ALGORITHM (csrc/sort_keys.hip; the constants are csrc/sort_keys.h's): a least-significant-digit radix sort, 8 bits a pass.
+ * The histograms of ALL digits of the window are taken in one upfront pass over the keys and read by the host (the call's one
+ * synchronisation of the stream); a digit whose histogram has a SINGLE OCCUPIED BIN is skipped, since its pass would be the
+ * identity.  A pass is three launches: the tiles' bin counts (a tile is SORT_TILE_KEYS = 2 048 keys), a prefix sum of them per bin
+ * over the tiles on top of the bins before it, and the scatter.  DETERMINISM IS THE CONTRACT: a key's place in a pass is
+ * computed from RANKS -- its digit's peers in the wave by ballots, the waves combined through LDS, the tile's place from the
+ * prefix sum -- and never by an atomic that hands out slots, so every pass is stable, and a repeated call gives the same bytes.
+ * A tile's keys are staged through LDS in digit order, so that a bin's run leaves as contiguous stores.  No library sort is
+ * linked.
+ * SCRATCH, stream-ordered memory given back behind the last kernel: a second key buffer (8 n bytes, 256-byte aligned), one uint32
+ * per bin and tile (1 KiB per 2 048 keys) and 8 KiB of histograms.  info (may be NULL) returns passes_run and scratch_bytes.
+ * MHS_ERR_INVALID names the argument before any device call; MHS_ERR_ALLOC if there is no memory. */
+typedef struct mhs_sort_info {
+    int passes_run;            /* the digits that were not skipped */
+    int64_t scratch_bytes;     /* the call's device scratch */
+} mhs_sort_info;
+MHS_API int mhs_sort_keys_dev(uint64_t *keys, int64_t n, int bit_lo, int bit_hi, void *stream, mhs_sort_info *info);
+
+/* ---------------------------------------------------------- zonal quantiles --
+ * Order statistics of one layer: the median (any quantile) per ZONE of a zone plane, per coarse cell of a TARGET grid
+ * (terra::aggregate(fun = median)) or of the WHOLE LAYER (terra::global), and a cell's rank inside its zone -- the median
+ * elevation of a basin, the 5 % / 95 % elevation of a patch, a DEM's median on the model grid, a layer's thresholds, a cell's
+ * hypsometric position in its basin.  No exact commutative accumulator gives a quantile, so the cells are SORTED ("sort" above).
+ * THE RULE (this text is the specification; csrc/quantile_rule.h holds it as code, on top of csrc/zonal_rule.h).
+ *
+ * UNCHANGED FROM "zonal", through the same functions: the input layer; NA and +-Inf; membership (0 <= z < n_zones, negative =
+ * none, a zone >= n_zones is MHS_ERR_INVALID naming n_zones before anything is written, n_zones = 0 is measured); the
+ * quantisation q = rint(v / quantum) with its default, its refusal and n_inexact.  Phase 1 of "zonal" always runs here.
+ *
+ * THE ZONE OF A CELL: (a) zones != NULL: the zone plane.  (b) zones == NULL, target != NULL: the target cell whose footprint
+ * holds the source cell, by "resample"'s aggregate footprints (rs_foot_col / rs_foot_row of csrc/resample_rule.h, unchanged: two
+ * index tables are made from them on the host); zone = target row * target ncol + target column, n_zones = target nrow * ncol;
+ * a source cell in no footprint has no zone.  (c) both NULL: every cell is in zone 0 (n_zones = 1).  zones and target together
+ * are refused; without a zone plane n_zones must be given as 0.
+ *
+ * THE QUANTILE.  Per zone let s[0 .. n) be the contributing cells' q in ascending order.  For p in [0, 1] (NaN is refused),
+ * R's type 7 = numpy's "linear", every operation rounded once, nothing fused:
+ *      h  = (double)(n - 1) * p;   lo = (int64)floor(h);   g = h - (double)lo;   hi = min(lo + 1, n - 1)
+ *      Q  = ((double)s[lo] + g * (double)((int64)s[hi] - (int64)s[lo])) * quantum;          n = 0: NA
+ * CONSEQUENCES.  p = 0 and p = 1 are "zonal"'s min and max bit for bit.  min <= Q <= max always: with d = s[hi] - s[lo] >= 0 and
+ * 0 <= g < 1, fl(g d) <= d and s[lo] + fl(g d) lies between two representable numbers.  With n_inexact = 0 the median (p = 0.5)
+ * equals numpy.median of the zone's values bit for bit: for n odd h is an integer and Q = s[lo] quantum; for n even g = 0.5 and
+ * g d is exact, so Q is the exact mean of the two middle values rounded once.  Against the exact type 7 value X of the same
+ * q: |Q - X| <= u (n D + D + M) quantum, u = 2^-53, D = s[n-1] - s[0], M = max(|s[0]|, |s[n-1]|) (the derivation is in
+ * quantile_rule.h: h carries one rounding, g is exact, g d and the sum round once); numpy.quantile(method = "linear") lies
+ * within the same bound of X.
+ * PER CELL, only at a contributing cell: below (int32) = the number of contributing cells of the cell's zone with q smaller
+ * than its own, -1 elsewhere; frac_below = (double)below / (double)n, NA elsewhere.  Ties share the smallest rank.
+ *
+ * probs: n_probs = 1 .. 16 probabilities, unsorted and repeated values allowed.
+ * OUTPUTS; each optional, a call must ask for at least one of table, planes, info.
+ *   TABLE: q holds capacity x n_probs doubles, row-major, row = zone; count int64.  DENSE (zone = NULL): row z is zone z,
+ *     n_zones rows, NA where n = 0; n_zones > capacity is MHS_ERR_INVALID naming capacity.  PRESENT (zone != NULL; needs info):
+ *     only the zones with n > 0 -- not "zonal"'s cells > 0: a zone of NA cells has no quantile --, ascending, K = info->n_present
+ *     rows; K > capacity is MHS_ERR_INVALID naming capacity.
+ *   PLANES: q[j] gives each cell its zone's quantile j, NA without a zone; below, frac_below as above.  Float planes are dtype
+ *     MHS_F32 or MHS_F64, an F32 value the F64 value rounded once; below is int32.  A plane q[j] with j >= n_probs is refused.
+ *   INFO: "zonal"'s fields (n_present counts the zones with n > 0) and passes_run, the sort's passes.
+ *
+ * THE ALGORITHM (csrc/quantile.hip), each phase its own launch: (1) "zonal"'s range and zone check, the same
+ * function; without a zone plane the cells' zones are first written as an int32 plane into the second key buffer, which is free
+ * until the sort; (2) keys (zone << 32) | (uint32)(q + 2^30); a cell that does not contribute gets the SENTINEL n_zones << 32,
+ * which sorts last (so the sort's window is 32 + bits(n_zones) bits, not bits(n_zones - 1)); (3) the sort; (4) segment heads from
+ * neighbouring keys, a blocked prefix sum and a compaction give the present zones, their starts and counts with no table of
+ * n_zones slots; (5) quantiles by direct look-up of s[lo], s[hi]; (6) planes: below by a lower-bound bisection in the cell's
+ * segment.  A dense table or planes take the zones' starts from one bisection per zone slot.
+ * SCRATCH, stream-ordered: two key buffers, 16 bytes per cell; per tile of 2 048 cells 1 KiB of digit counts, and 4 bytes for a
+ * present table; 4 bytes per source row and column with a target; a FIXED part of at most MHS_QUANTILE_SCRATCH_FIXED bytes
+ * (histograms, the counter block, alignments); and 4 bytes per zone slot ONLY for a dense table or planes.  A present table
+ * without planes allocates nothing proportional to n_zones: the form for cell-number labels.
+ *
+ * LIMITS, checked before the first device call, the message names the argument: those of "zonal"; flags must be 0.
+ * OUT OF SCOPE: focal (window) medians; weighted quantiles (cell area on lon/lat grids); quantile types other than 7; mid-rank
+ * percentiles for ties; 32-bit packed keys for narrow layers (the first speed-up to look at: an int16 layer with fewer than
+ * 2^16 zones fits); more than 16 probabilities per call; more than 2^31 - 1 cells; a bench.py line. */
+#define MHS_QUANTILE_MAX_PROBS 16
+#define MHS_QUANTILE_SCRATCH_FIXED 16384
+typedef struct mhs_quantile_table {
+    int64_t capacity;          /* rows that every array below holds */
+    int32_t *zone;             /* NULL: dense.  Else the present form: the zone number of each row */
+    int64_t *count;            /* n per row */
+    double *q;                 /* capacity x n_probs, row-major */
+} mhs_quantile_table;
+typedef struct mhs_quantile_planes {
+    void *q[MHS_QUANTILE_MAX_PROBS];         /* by probability; NULL: not wanted */
+    int64_t ld_q[MHS_QUANTILE_MAX_PROBS];    /* the row stride of each, in elements */
+    int32_t *below;
+    int64_t ld_below;
+    void *frac_below;
+    int64_t ld_frac_below;
+    int dtype;                               /* MHS_F64 or MHS_F32 */
+} mhs_quantile_planes;
+typedef struct mhs_quantile_info {
+    int64_t n_zones;           /* as given, measured, or implied by the target */
+    int64_t n_present;         /* zones with n > 0 */
+    int64_t n_cells_in_zones;
+    int64_t n_contributing;
+    int64_t n_nonfinite;
+    int64_t n_inexact;
+    double quantum;
+    int64_t scratch_bytes;
+    int64_t passes_run;        /* the sort's passes */
+} mhs_quantile_info;
+/* DEVICE planes.  The stream is synchronised behind phase 1, inside the sort, and behind the last kernel when info is given. */
+MHS_API int mhs_zonal_quantile_dev(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t ld_zones, int64_t n_zones,
+                                   double quantum, int flags, const double *probs, int n_probs, const mhs_grid *target,
+                                   const mhs_quantile_table *table, const mhs_quantile_planes *planes, void *stream, mhs_quantile_info *info);
+/* same, HOST planes (nrow x ncol dense; ld is not looked at): what the R shim hands over.  Blocks until done. */
+MHS_API int mhs_zonal_quantile(const mhs_grid *g, const mhs_stack *stack, int layer, const int32_t *zones, int64_t n_zones, double quantum, int flags,
+                               const double *probs, int n_probs, const mhs_grid *target, const mhs_quantile_table *table,
+                               const mhs_quantile_planes *planes, mhs_quantile_info *info);
 
 /* ---------------------------------------------------------------- rasterize --
  * Points, lines and polygons burned onto the grid: what terra::rasterize is used for -- the administrative units or catchments
@@ -1478,7 +1596,7 @@ MHS_API int mhs_rasterize(const mhs_grid *g, const mhs_features *features, int r
  *
  * OUT OF SCOPE: a "mode" method inside mhs_resample; the present table form; several radii per focal call; codes outside
  * 0 .. 65 535 or more than 256 classes; Shannon entropy; fractions weighted by cell area on lon/lat grids; warping categorical
- * rasters ("warp" with the nearest cell, then this); a median per zone; more than 2^31 - 1 cells.
+ * rasters ("warp" with the nearest cell, then this); a median per zone (section "zonal quantiles"); more than 2^31 - 1 cells.
  *
  * The algorithm (csrc/classes.hip), every phase its own launch, a kernel boundary the only ordering.  Code to k:
  * a direct table in LDS where max code - min code < 1 024, else a bisection in the sorted list in LDS; both give the same k.

@@ -469,6 +469,62 @@ mhs_zonal <- function(x, z, stats = "mean", planes = NULL, present = TRUE, n.zon
        info = stats::setNames(out[[3]], c("n_zones", "n_present", "n_cells_in_zones", "n_contributing", "n_nonfinite", "n_inexact", "quantum")))
 }
 
+# ---- zonal quantiles: the median (any quantile) per zone, per coarser cell, of the whole layer -------------------------------------
+# Section "zonal quantiles" of machisplin_hip.h: R's type 7 quantile (stats::quantile's default) of the quantised values, from a
+# deterministic device sort.  z = NULL: the whole layer (terra::global).  planes: some of "q", "below", "frac_below".
+# Returns list(table = data.frame(zone, count, q<p> ...), planes = SpatRaster or NULL, info).
+mhs_zonal_quantile <- function(x, z = NULL, probs = 0.5, planes = NULL, present = TRUE, n.zones = NULL, quantum = NULL, layer = 1L) {
+  .mhs_quantile_planes <- c("q", "below", "frac_below")
+  if (!length(probs) || length(probs) > 16 || any(is.na(probs)) || any(probs < 0 | probs > 1)) stop("mhs_zonal_quantile: probs must be 1 .. 16 probabilities in [0, 1]")
+  if (length(setdiff(planes, .mhs_quantile_planes))) stop("mhs_zonal_quantile: planes must name some of q, below, frac_below")
+  if (!is.null(z) && (terra::ncell(z) != terra::ncell(x) || terra::ncol(z) != terra::ncol(x))) stop("mhs_zonal_quantile: shape mismatch: z is not on the grid of x")
+  if (!is.null(n.zones) && (is.null(z) || is.na(n.zones) || n.zones < 1 || n.zones > 2147483647)) stop("mhs_zonal_quantile: n.zones goes with z and must be in 1 .. 2^31 - 1")
+  if (!is.null(quantum) && (is.na(quantum) || quantum <= 0 || log2(quantum) != floor(log2(quantum)))) stop("mhs_zonal_quantile: quantum must be a power of two")
+  zv <- NULL
+  if (!is.null(z)) {
+    zv <- terra::values(z[[1]])[, 1]
+    if (any(zv != floor(zv), na.rm = TRUE)) stop("mhs_zonal_quantile: zones given as fractions are out of scope")
+    zv <- as.integer(zv)
+  }
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  planes <- unique(planes)
+  out <- .Call("mhsr_zonal_quantile", .mhs_geom(x), vals, NA_real_, zv, NULL,
+               c(layer - 1, if (is.null(n.zones)) 0 else n.zones, if (is.null(quantum)) 0 else quantum, as.numeric(isTRUE(present)), 1,
+                 sum(2^(match(planes, .mhs_quantile_planes) - 1))),
+               as.numeric(probs))
+  q <- matrix(out[[1]][[3]], ncol = length(probs), byrow = TRUE)
+  colnames(q) <- paste0("q", probs)
+  zone <- if (isTRUE(present)) out[[1]][[1]] else seq_len(nrow(q)) - 1L
+  table <- data.frame(zone = zone, count = out[[1]][[2]], q, check.names = FALSE)
+  r <- NULL
+  if (length(planes)) {
+    layers <- list()
+    if ("q" %in% planes) for (j in seq_along(probs)) {
+      l <- terra::setValues(terra::rast(x[[1]]), out[[2]][[1]][[j]]); names(l) <- paste0("q", probs[j]); layers <- c(layers, l)
+    }
+    if ("below" %in% planes) { l <- terra::setValues(terra::rast(x[[1]]), out[[2]][[2]]); names(l) <- "below"; layers <- c(layers, l) }
+    if ("frac_below" %in% planes) { l <- terra::setValues(terra::rast(x[[1]]), out[[2]][[3]]); names(l) <- "frac_below"; layers <- c(layers, l) }
+    r <- do.call(c, layers)
+  }
+  list(table = table, planes = r,
+       info = stats::setNames(out[[3]], c("n_zones", "n_present", "n_cells_in_zones", "n_contributing", "n_nonfinite", "n_inexact", "quantum", "passes_run")))
+}
+
+# terra::aggregate(x, fun = median) and its quantiles onto the grid of y (same coordinate system, any resolution, origin and
+# extent): a cell of y takes the cells of x whose centre lies in it, resample's footprints.  Returns a SpatRaster on y's grid with
+# one layer per probability and the layer "count".
+mhs_aggregate_quantile <- function(x, y, probs = 0.5, quantum = NULL, layer = 1L) {
+  if (!length(probs) || length(probs) > 16 || any(is.na(probs)) || any(probs < 0 | probs > 1)) stop("mhs_aggregate_quantile: probs must be 1 .. 16 probabilities in [0, 1]")
+  if (!is.null(quantum) && (is.na(quantum) || quantum <= 0 || log2(quantum) != floor(log2(quantum)))) stop("mhs_aggregate_quantile: quantum must be a power of two")
+  vals <- terra::values(x); storage.mode(vals) <- "double"
+  out <- .Call("mhsr_zonal_quantile", .mhs_geom(x), vals, NA_real_, NULL, .mhs_geom(y),
+               c(layer - 1, 0, if (is.null(quantum)) 0 else quantum, 0, 1, 0), as.numeric(probs))
+  q <- matrix(out[[1]][[3]], ncol = length(probs), byrow = TRUE)
+  layers <- lapply(seq_along(probs), function(j) { l <- terra::setValues(terra::rast(y[[1]]), q[, j]); names(l) <- paste0("q", probs[j]); l })
+  cnt <- terra::setValues(terra::rast(y[[1]]), out[[1]][[2]]); names(cnt) <- "count"
+  do.call(c, c(layers, cnt))
+}
+
 # ---- categorical layers: class counts, fractions and mode per zone and per coarser cell -------------------------------------------
 # What terra::crosstab and terra::aggregate(fun = "modal") are used for, and how a land-cover raster enters a covariate stack: as
 # class fractions.  Section "classes" of machisplin_hip.h states the rule: a value is the class whose code it equals exactly, every

@@ -678,6 +678,98 @@ SEXP mhsr_zonal(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP opts, SEXP
     return out;
 }
 
+/* Zonal quantiles (section "zonal quantiles" of machisplin_hip.h) through the host entry mhs_zonal_quantile.  planes, nodata: as
+ * for mhsr_zonal; zones: an integer vector of one zone per cell, or NULL; target: NULL or the geometry c(xmin, ymax, xres, yres,
+ * nrow, ncol) of the grid whose cells are the zones (zones must then be NULL); both NULL: the whole layer.  opts: c(layer,
+ * n_zones, quantum, present, table, planes) with layer 0-based, n_zones and quantum 0 = the library's choice, table != 0 a table,
+ * planes a bit mask of 1 q, 2 below, 4 frac_below.  probs: 1 .. 16 probabilities.  Returns list(table = list(zone, count, q)
+ * with q a vector of rows x n_probs values, row-major; planes = list(q = a list of one plane per probability, below, frac_below);
+ * info = c(n_zones, n_present, n_cells_in_zones, n_contributing, n_nonfinite, n_inexact, quantum, passes_run)). */
+SEXP mhsr_zonal_quantile(SEXP geom, SEXP planes, SEXP nodata, SEXP zones, SEXP target, SEXP opts, SEXP probs) {
+    mhs_grid g = grid_from(geom);
+    mhs_stack st = planes_from(planes, nodata, &g, "mhsr_zonal_quantile");
+    if (!Rf_isReal(opts) || Rf_length(opts) != 6) Rf_error("mhsr_zonal_quantile: opts must be c(layer, n_zones, quantum, present, table, planes)");
+    const double *o = REAL(opts);
+    if (!(o[0] >= 0.0 && o[0] <= 2147483647.0)) Rf_error("mhsr_zonal_quantile: layer must be a 0-based layer number");
+    if (!(o[1] >= 0.0 && o[1] <= 2147483647.0)) Rf_error("mhsr_zonal_quantile: n_zones must be 0 (measure it) or in 1 .. 2^31 - 1");
+    if (!(o[2] >= 0.0)) Rf_error("mhsr_zonal_quantile: quantum must be 0 (the library's choice) or a power of two");
+    if (!(o[5] >= 0.0 && o[5] <= 7.0)) Rf_error("mhsr_zonal_quantile: planes must be a bit mask of 1 q, 2 below, 4 frac_below");
+    if (!Rf_isReal(probs) || Rf_length(probs) < 1 || Rf_length(probs) > MHS_QUANTILE_MAX_PROBS) Rf_error("mhsr_zonal_quantile: probs must hold 1 .. 16 probabilities");
+    if (!(g.nrow > 0 && g.ncol > 0 && (double)g.nrow * (double)g.ncol <= 2147483647.0)) Rf_error("mhsr_zonal_quantile: bad grid dimension");
+    const R_xlen_t n = (R_xlen_t)g.nrow * g.ncol;
+    const int have_zones = !Rf_isNull(zones), have_target = !Rf_isNull(target);
+    if (have_zones && have_target) Rf_error("mhsr_zonal_quantile: zones and target are both given");
+    if (have_zones && (TYPEOF(zones) != INTSXP || Rf_xlength(zones) != n)) Rf_error("mhsr_zonal_quantile: zones must be NULL or an integer vector of one zone per cell");
+    if (!have_zones && o[1] != 0.0) Rf_error("mhsr_zonal_quantile: n_zones goes with a zone plane");
+    mhs_grid tg = g;
+    if (have_target) {
+        tg = grid_from(target);
+        if (!(tg.nrow > 0 && tg.ncol > 0 && (double)tg.nrow * (double)tg.ncol <= 2147483647.0)) Rf_error("mhsr_zonal_quantile: bad target dimension");
+    }
+    const int n_probs = Rf_length(probs), present = o[3] != 0.0, want_table = o[4] != 0.0, ps = (int)o[5];
+    if (!want_table && !ps) Rf_error("mhsr_zonal_quantile: no output: neither a table nor a plane is asked for");
+    const int32_t *zp = have_zones ? (const int32_t *)INTEGER(zones) : NULL;
+    const mhs_grid *tp = have_target ? &tg : NULL;
+    int64_t n_zones = (int64_t)o[1];
+    double quantum = o[2];
+    mhs_quantile_info info = { 0 };
+    if (!have_zones) n_zones = have_target ? tg.nrow * tg.ncol : 1;
+    else if (want_table && !present && n_zones == 0) {             /* the library measures n_zones before the dense table is sized */
+        chk(mhs_zonal_quantile(&g, &st, (int)o[0], zp, 0, quantum, 0, REAL(probs), n_probs, tp, NULL, NULL, &info));
+        n_zones = info.n_zones;
+        quantum = info.quantum;
+    }
+    const R_xlen_t rows = !want_table ? 0 : !present ? (R_xlen_t)n_zones : (n_zones && n_zones < n) ? (R_xlen_t)n_zones : n;
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SEXP tab = PROTECT(Rf_allocVector(VECSXP, 3)), pl = PROTECT(Rf_allocVector(VECSXP, 3));
+    int n_protect = 3;
+    for (int k = 0; k < 3; ++k) { SET_VECTOR_ELT(tab, k, R_NilValue); SET_VECTOR_ELT(pl, k, R_NilValue); }
+    mhs_quantile_table qt = { (int64_t)rows, NULL, NULL, NULL };
+    const int with_table = want_table && rows > 0;
+    if (with_table) {
+        if (present) qt.zone = (int32_t *)R_alloc((size_t)rows, sizeof(int32_t));
+        qt.count = (int64_t *)R_alloc((size_t)rows, sizeof(int64_t));
+        qt.q = (double *)R_alloc((size_t)rows * (size_t)n_probs, sizeof(double));
+    }
+    mhs_quantile_planes qp = { { NULL }, { 0 }, NULL, 0, NULL, 0, MHS_F64 };
+    if (ps & 1) {
+        SET_VECTOR_ELT(pl, 0, Rf_allocVector(VECSXP, n_probs));
+        for (int j = 0; j < n_probs; ++j) {
+            SET_VECTOR_ELT(VECTOR_ELT(pl, 0), j, Rf_allocVector(REALSXP, n));
+            qp.q[j] = REAL(VECTOR_ELT(VECTOR_ELT(pl, 0), j));
+            qp.ld_q[j] = g.ncol;
+        }
+    }
+    if (ps & 2) { SET_VECTOR_ELT(pl, 1, Rf_allocVector(INTSXP, n)); qp.below = (int32_t *)INTEGER(VECTOR_ELT(pl, 1)); qp.ld_below = g.ncol; }
+    if (ps & 4) { SET_VECTOR_ELT(pl, 2, Rf_allocVector(REALSXP, n)); qp.frac_below = REAL(VECTOR_ELT(pl, 2)); qp.ld_frac_below = g.ncol; }
+    int rc = MHS_OK;
+    if (with_table || ps)
+        rc = mhs_zonal_quantile(&g, &st, (int)o[0], zp, have_zones ? n_zones : 0, quantum, 0, REAL(probs), n_probs, tp, with_table ? &qt : NULL, ps ? &qp : NULL, &info);
+    if (rc == MHS_OK) {
+        const R_xlen_t k_rows = !with_table ? 0 : present ? (R_xlen_t)info.n_present : rows;
+        if (want_table) {
+            if (present) {
+                SET_VECTOR_ELT(tab, 0, Rf_allocVector(INTSXP, k_rows));
+                for (R_xlen_t k = 0; k < k_rows; ++k) INTEGER(VECTOR_ELT(tab, 0))[k] = qt.zone[k];
+            }
+            SET_VECTOR_ELT(tab, 1, Rf_allocVector(REALSXP, k_rows));
+            SET_VECTOR_ELT(tab, 2, Rf_allocVector(REALSXP, k_rows * n_probs));
+            for (R_xlen_t k = 0; k < k_rows; ++k) REAL(VECTOR_ELT(tab, 1))[k] = (double)qt.count[k];
+            for (R_xlen_t k = 0; k < k_rows * n_probs; ++k) REAL(VECTOR_ELT(tab, 2))[k] = qt.q[k];
+        }
+        SEXP inf = PROTECT(Rf_allocVector(REALSXP, 8)); ++n_protect;
+        REAL(inf)[0] = (double)info.n_zones; REAL(inf)[1] = (double)info.n_present; REAL(inf)[2] = (double)info.n_cells_in_zones;
+        REAL(inf)[3] = (double)info.n_contributing; REAL(inf)[4] = (double)info.n_nonfinite; REAL(inf)[5] = (double)info.n_inexact;
+        REAL(inf)[6] = info.quantum; REAL(inf)[7] = (double)info.passes_run;
+        SET_VECTOR_ELT(out, 0, tab);
+        SET_VECTOR_ELT(out, 1, pl);
+        SET_VECTOR_ELT(out, 2, inf);
+    }
+    UNPROTECT(n_protect);
+    chk(rc);
+    return out;
+}
+
 /* the class list and frac_of of the two class entries: integer vectors, or NULL (classes: measure them; frac_of: all classes) */
 static int class_codes(SEXP v, const char *who, const char *what, const int32_t **out) {
     *out = NULL;

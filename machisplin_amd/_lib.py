@@ -137,6 +137,29 @@ class ZonalInfo(C.Structure):
                 ("n_nonfinite", C.c_int64), ("n_inexact", C.c_int64), ("quantum", C.c_double), ("scratch_bytes", C.c_int64)]
 
 
+class SortInfo(C.Structure):
+    """struct mhs_sort_info"""
+    _fields_ = [("passes_run", C.c_int), ("scratch_bytes", C.c_int64)]
+
+
+class QuantileTable(C.Structure):
+    """struct mhs_quantile_table"""
+    _fields_ = [("capacity", C.c_int64), ("zone", C.c_void_p), ("count", C.c_void_p), ("q", C.c_void_p)]
+
+
+class QuantilePlanes(C.Structure):
+    """struct mhs_quantile_planes"""
+    _fields_ = [("q", C.c_void_p * 16), ("ld_q", C.c_int64 * 16), ("below", C.c_void_p), ("ld_below", C.c_int64), ("frac_below", C.c_void_p),
+                ("ld_frac_below", C.c_int64), ("dtype", C.c_int)]
+
+
+class QuantileInfo(C.Structure):
+    """struct mhs_quantile_info"""
+    _fields_ = [("n_zones", C.c_int64), ("n_present", C.c_int64), ("n_cells_in_zones", C.c_int64), ("n_contributing", C.c_int64),
+                ("n_nonfinite", C.c_int64), ("n_inexact", C.c_int64), ("quantum", C.c_double), ("scratch_bytes", C.c_int64),
+                ("passes_run", C.c_int64)]
+
+
 class ClassTable(C.Structure):
     """struct mhs_class_table"""
     _fields_ = [("capacity", C.c_int64), ("counts", C.c_void_p), ("n", C.c_void_p), ("other", C.c_void_p), ("cells", C.c_void_p), ("mode", C.c_void_p),
@@ -318,6 +341,11 @@ SIGNATURES = {
                                 C.POINTER(ZonalPlanes), _vp, C.POINTER(ZonalInfo)]),
     "mhs_zonal": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, C.c_double, C.c_int, C.POINTER(ZonalTable),
                             C.POINTER(ZonalPlanes), C.POINTER(ZonalInfo)]),
+    "mhs_sort_keys_dev": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, C.POINTER(SortInfo)]),
+    "mhs_zonal_quantile_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _i64, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                         C.POINTER(Grid), C.POINTER(QuantileTable), C.POINTER(QuantilePlanes), _vp, C.POINTER(QuantileInfo)]),
+    "mhs_zonal_quantile": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                     C.POINTER(Grid), C.POINTER(QuantileTable), C.POINTER(QuantilePlanes), C.POINTER(QuantileInfo)]),
     "mhs_class_crosstab_dev": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _i64, _vp, C.c_int, _vp, C.c_int, C.POINTER(ClassTable),
                                          C.POINTER(ClassPlanes), _vp, C.POINTER(ClassInfo)]),
     "mhs_class_crosstab": (C.c_int, [C.POINTER(Grid), C.POINTER(Stack), C.c_int, _vp, _i64, _vp, C.c_int, _vp, C.c_int, C.POINTER(ClassTable),

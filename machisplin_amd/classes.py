@@ -14,7 +14,7 @@ addition and every table and plane equals a numpy restatement bit for bit.  A ti
 work on the cells runs in libmachisplin_hip.so (csrc/classes.hip); this module only marshals arguments.
 
 Out of scope: the "present" table form, several radii per call, codes outside 0 .. 65 535 or more than 256 classes, Shannon
-entropy, area weights on lon/lat grids, a median per zone, more than 2^31 - 1 cells.
+entropy, area weights on lon/lat grids, a median per zone (:func:`zonal.quantile` has it), more than 2^31 - 1 cells.
 """
 from __future__ import annotations
 

@@ -38,6 +38,7 @@
 #include <mutex>
 #include "ensemble_int.h"
 #include "proximity_rule.h"
+#include "zonal_int.h"
 #include "zonal_rule.h"
 
 namespace mhs {
@@ -49,22 +50,6 @@ static_assert(ZONAL_TILE_COLS == 64, "a wave holds one tile row in its lanes");
 static_assert(ZONAL_TILE_ROWS % ZN_WAVES == 0 && ZONAL_SCAN_BLOCK % ZN_NT == 0, "whole rows per wave, whole chunks per block");
 static_assert((ZONAL_LDS_SLOTS & (ZONAL_LDS_SLOTS - 1)) == 0 && ZONAL_LDS_SLOTS % ZN_NT == 0, "a power of two, whole slots per thread");
 static_assert(MHS_ZONAL_N_STATS == ZONAL_N_STATS, "the header and the rule agree");
-
-struct ZonalGeom {
-    int nrow, ncol;
-    double nodata;
-    int has_nodata;
-    int tiles_c;             // tiles side by side
-};
-
-struct ZonalCounters {
-    unsigned long long max_abs_bits;         // the bits of max|v|: non-negative doubles order like their bits
-    unsigned long long n_nonfinite, n_in_zone, n_contrib, n_inexact, n_present;
-    unsigned zones_end;                      // max(zone) + 1
-    unsigned bad;                            // 1: a zone >= n_zones; 2: a value that does not fit the quantum
-};
-static_assert(sizeof(ZonalCounters) <= 256, "the counter block");
-enum { ZN_BAD_ZONE = 1, ZN_BAD_QUANTUM = 2 };
 
 // the global table, one array per accumulator; NULL where no requested statistic needs it
 struct ZonalTables {
@@ -86,8 +71,6 @@ struct ZonalPlaneOut {
     void *p[ZONAL_N_STATS];
     int64_t ld[ZONAL_N_STATS];
 };
-
-MHS_ZONAL_HD inline bool zn_finite(double v) { return std::fabs(v) <= 1.7976931348623157e308; }
 
 __device__ inline unsigned zn_wave_sum(unsigned v) {
 #pragma unroll
@@ -424,11 +407,6 @@ __global__ __launch_bounds__(ZN_NT) void zonal_planes_kernel(const ZonalGeom g, 
     if (o.p[10]) ((O *)o.p[10])[r * o.ld[10] + c] = (O)(contributes ? zonal_dev(mm, f.s[3][zn]) : na);
 }
 
-#define ZN_REQUIRE(cond, ...)                                              \
-    do {                                                                   \
-        if (!(cond)) { set_error(__VA_ARGS__); return MHS_ERR_INVALID; }    \
-    } while (0)
-
 static unsigned zn_table_stats(const mhs_zonal_table *t) {
     if (!t) return 0u;
     return (t->count ? ZONAL_COUNT : 0u) | (t->sum ? ZONAL_SUM : 0u) | (t->mean ? ZONAL_MEAN : 0u) | (t->sd ? ZONAL_SD : 0u) |
@@ -479,24 +457,27 @@ static int zonal_check(const char *fn, const mhs_grid *grid, const mhs_stack *st
     return MHS_OK;
 }
 
-// a block of stream-ordered memory, given back behind whatever was enqueued last
-struct ZonalScratch {
-    char *p = nullptr;
-    hipStream_t st = nullptr;
-    ~ZonalScratch() { if (p) (void)hipFreeAsync(p, st); }
-    int get(const char *fn, size_t bytes, hipStream_t s, const char *what) {
-        st = s;
-        if (hipMallocAsync((void **)&p, bytes, s) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            set_error("%s: no device memory for %s (%zu bytes)", fn, what, bytes);
-            return MHS_ERR_ALLOC;
-        }
-        return MHS_OK;
-    }
-};
-
-static size_t zn_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// Phase 1 and what the host decides from it (zonal_int.h)
+int zonal_measure(const char *fn, const ZonalGeom &g, int dtype, const void *plane, int64_t ldz, const int32_t *zones, int64_t ldq, hipStream_t st,
+                  ZonalCounters *counters, ZonalCounters *c, int64_t *n_zones, double *quantum) {
+    const size_t n = (size_t)g.nrow * (size_t)g.ncol;
+    const int n_cu = ctx().n_cu > 0 ? ctx().n_cu : 256;
+    const unsigned nb = std::min<unsigned>((unsigned)((n + ZN_NT - 1) / ZN_NT), (unsigned)n_cu * 8u);
+    if (dtype == MHS_F64) hipLaunchKernelGGL(zonal_range_kernel<double>, dim3(nb), dim3(ZN_NT), 0, st, g, (const double *)plane, ldz, zones, ldq, counters);
+    else if (dtype == MHS_F32) hipLaunchKernelGGL(zonal_range_kernel<float>, dim3(nb), dim3(ZN_NT), 0, st, g, (const float *)plane, ldz, zones, ldq, counters);
+    else hipLaunchKernelGGL(zonal_range_kernel<short>, dim3(nb), dim3(ZN_NT), 0, st, g, (const short *)plane, ldz, zones, ldq, counters);
+    MHS_HIP(hipGetLastError());
+    MHS_HIP(hipMemcpyAsync(c, counters, sizeof(*c), hipMemcpyDeviceToHost, st));
+    MHS_HIP(hipStreamSynchronize(st));
+    double max_abs;
+    std::memcpy(&max_abs, &c->max_abs_bits, 8);
+    if (*n_zones == 0) *n_zones = (int64_t)c->zones_end;
+    ZN_REQUIRE((int64_t)c->zones_end <= *n_zones, "%s: the zone plane holds zone %lld, which is not below n_zones %lld", fn, (long long)c->zones_end - 1,
+               (long long)*n_zones);
+    if (*quantum == 0.0) *quantum = zonal_default_quantum(max_abs);
+    ZN_REQUIRE(zonal_fits(max_abs, *quantum), "%s: quantum %g is too small: the layer's largest magnitude %g passes 2^30 * quantum", fn, *quantum, max_abs);
+    return MHS_OK;
+}
 
 template <typename T>
 static void launch_zonal_planes(int out_dtype, unsigned nb, hipStream_t st, const ZonalGeom &g, const void *z, int64_t ldz, const int32_t *zones,
@@ -527,20 +508,7 @@ static int zonal_run(const char *fn, const ZonalGeom &g, int dtype, const void *
     const bool measure = n_zones == 0 || (quantum == 0.0 && dtype != MHS_I16) || info;
     if (quantum == 0.0 && dtype == MHS_I16) quantum = 1.0;
     if (measure) {
-        const unsigned nb = std::min<unsigned>(nb_cells, (unsigned)n_cu * 8u);
-        if (dtype == MHS_F64) hipLaunchKernelGGL(zonal_range_kernel<double>, dim3(nb), dim3(ZN_NT), 0, st, g, (const double *)plane, ldz, zones, ldq, counters);
-        else if (dtype == MHS_F32) hipLaunchKernelGGL(zonal_range_kernel<float>, dim3(nb), dim3(ZN_NT), 0, st, g, (const float *)plane, ldz, zones, ldq, counters);
-        else hipLaunchKernelGGL(zonal_range_kernel<short>, dim3(nb), dim3(ZN_NT), 0, st, g, (const short *)plane, ldz, zones, ldq, counters);
-        MHS_HIP(hipGetLastError());
-        MHS_HIP(hipMemcpyAsync(&c, counters, sizeof(c), hipMemcpyDeviceToHost, st));
-        MHS_HIP(hipStreamSynchronize(st));
-        double max_abs;
-        std::memcpy(&max_abs, &c.max_abs_bits, 8);
-        if (n_zones == 0) n_zones = (int64_t)c.zones_end;
-        ZN_REQUIRE((int64_t)c.zones_end <= n_zones, "%s: the zone plane holds zone %lld, which is not below n_zones %lld", fn, (long long)c.zones_end - 1,
-                   (long long)n_zones);
-        if (quantum == 0.0) quantum = zonal_default_quantum(max_abs);
-        ZN_REQUIRE(zonal_fits(max_abs, quantum), "%s: quantum %g is too small: the layer's largest magnitude %g passes 2^30 * quantum", fn, quantum, max_abs);
+        if (int rc = zonal_measure(fn, g, dtype, plane, ldz, zones, ldq, st, counters, &c, &n_zones, &quantum)) return rc;
         ZN_REQUIRE(!ts || present || n_zones <= table->capacity, "%s: n_zones %lld passes the dense table's capacity %lld", fn, (long long)n_zones,
                    (long long)table->capacity);
     }

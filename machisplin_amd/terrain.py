@@ -32,6 +32,8 @@ STREAM_SPEC = {"dist_stream": "dist", "above_stream": "value"}          # covari
 PATCH_DIST_SPEC = {"dist_na_edge": ("na", 0), "dist_na_min": ("na", 1), "dist_le_min": ("le", 2)}      # covariates(): spec name -> the predicate of patches, its arguments
 BASIN_SPEC = {"basin_mean": "mean", "basin_minus_mean": "minus_mean", "basin_dev": "dev"}      # covariates(): spec name -> the plane of zonal
 ZONE_SPEC = {"zone_mean": "mean", "zone_minus_mean": "minus_mean", "zone_dev": "dev"}      # covariates(): spec name -> the plane of zonal, zones from vector features
+BASIN_QUANTILE_SPEC = {"basin_median": "q", "basin_frac_below": "frac_below"}      # covariates(): spec name -> the plane of zonal.quantile at p = 0.5
+ZONE_QUANTILE_SPEC = {"zone_median": "q", "zone_frac_below": "frac_below"}         # ... zones from vector features
 DIST_FEATURES = "dist_features"                                         # covariates(): the distance to vector features
 CLASS_SPEC = {"class_frac": 4, "class_cover": 3}                         # covariates(): spec name -> the entry's length (classes.focal / classes.aggregate)
 FLOW_SPEC = {"hand": "drop", "flowdist_stream": "dist"}                 # covariates(): spec name -> the product of flowpath
@@ -406,16 +408,31 @@ def _flow_layers(dem_stack, demf, flowdir, flowacc, thresholds, spec, layer):
     return out
 
 
-def _basin_layers(dem_stack, flowdir, wanted, layer):
+def _quantile_planes(dem_stack, zones, n_zones, wanted, layer):
+    """the planes ``wanted`` ("q": the zone's median, "frac_below") of one :func:`zonal.quantile` call at p = 0.5, float32"""
+    import torch
+    from . import zonal as _zonal
+    _, planes, _ = _zonal.quantile(dem_stack, zones, (0.5,), layer, wanted, n_zones=n_zones, table=None, out_dtype=torch.float32)
+    return {k: (v[0] if k == "q" else v) for k, v in planes.items()}
+
+
+def _basin_layers(dem_stack, flowdir, wanted, layer, wanted_q=()):
     """the "basin_mean", "basin_minus_mean" and "basin_dev" layers of :func:`covariates`: the outlet labels of the D8 forest are
-    the zones (a cell number per basin, -1 at NA cells), and one zonal call makes the planes; keyed by the spec's name"""
+    the zones (a cell number per basin, -1 at NA cells), and one zonal call makes the planes; "basin_median" and
+    "basin_frac_below" come from one :func:`zonal.quantile` call on the same labels; keyed by the spec's name"""
     import torch
     from . import flowpath as _flow
     from . import zonal as _zonal
     g = dem_stack.geom
     basin = _flow.flowpath(flowdir, dem_stack, layer, "outlet", None, "index")[0]
-    _, planes, _ = _zonal.zonal(dem_stack, basin, layer, stats=(), planes=wanted, n_zones=g.nrow * g.ncol, table=None, out_dtype=torch.float32)
-    return {name: planes[plane] for name, plane in BASIN_SPEC.items() if plane in planes}
+    out = {}
+    if wanted:
+        _, planes, _ = _zonal.zonal(dem_stack, basin, layer, stats=(), planes=wanted, n_zones=g.nrow * g.ncol, table=None, out_dtype=torch.float32)
+        out.update({name: planes[plane] for name, plane in BASIN_SPEC.items() if plane in planes})
+    if wanted_q:
+        planes = _quantile_planes(dem_stack, basin, g.nrow * g.ncol, wanted_q, layer)
+        out.update({name: planes[plane] for name, plane in BASIN_QUANTILE_SPEC.items() if plane in planes})
+    return out
 
 
 def _vector_layers(dem_stack, spec, layer):
@@ -436,12 +453,17 @@ def _vector_layers(dem_stack, spec, layer):
         burned, _ = _rast.rasterize(marked, g, ("value",), touches=True, device=dev)
         out[(DIST_FEATURES, id(feats))] = _prox.proximity(RasterStack(g, burned["value"][None], float("nan")), 0, "valid", None, "dist",
                                                           out_dtype=torch.float32)[0]
-    for feats in {id(e[1]): e[1] for e in spec if e[0] in ZONE_SPEC}.values():
+    for feats in {id(e[1]): e[1] for e in spec if e[0] in ZONE_SPEC or e[0] in ZONE_QUANTILE_SPEC}.values():
         wanted = tuple(dict.fromkeys(ZONE_SPEC[e[0]] for e in spec if e[0] in ZONE_SPEC and e[1] is feats))
+        wanted_q = tuple(dict.fromkeys(ZONE_QUANTILE_SPEC[e[0]] for e in spec if e[0] in ZONE_QUANTILE_SPEC and e[1] is feats))
         zones, _ = _rast.rasterize(feats, g, ("index",), device=dev)
-        _, planes, _ = _zonal.zonal(dem_stack, zones["index"], layer, stats=(), planes=wanted, n_zones=max(feats.n_features, 1), table=None,
-                                    out_dtype=torch.float32)
-        out.update({(name, id(feats)): planes[plane] for name, plane in ZONE_SPEC.items() if plane in planes})
+        if wanted:
+            _, planes, _ = _zonal.zonal(dem_stack, zones["index"], layer, stats=(), planes=wanted, n_zones=max(feats.n_features, 1), table=None,
+                                        out_dtype=torch.float32)
+            out.update({(name, id(feats)): planes[plane] for name, plane in ZONE_SPEC.items() if plane in planes})
+        if wanted_q:                                  # the one rasterize call is shared; one quantile call per zone plane
+            planes = _quantile_planes(dem_stack, zones["index"], max(feats.n_features, 1), wanted_q, layer)
+            out.update({(name, id(feats)): planes[plane] for name, plane in ZONE_QUANTILE_SPEC.items() if plane in planes})
     return out
 
 
@@ -530,6 +552,12 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                   an administrative unit, a catchment: the zone's mean elevation, the cell's
                                                   elevation minus it, and that over the zone's sample sd (one rasterize call and
                                                   one :func:`zonal.zonal` call per distinct ``feats`` make all three; NaN outside)
+      "basin_median", "basin_frac_below"          the MEDIAN elevation of the cell's drainage basin, and the share of the basin's cells
+                                                  that lie below the cell -- its hypsometric position, a cold-air-pooling
+                                                  covariate (the same ``hydro`` and ``flowpath`` calls as the basin layers above,
+                                                  and one :func:`zonal.quantile` call)
+      ("zone_median" | "zone_frac_below", feats)  the same two against the polygon of ``feats`` that holds the cell's centre (the
+                                                  one rasterize call is shared with the zone layers above; one quantile call)
       ("class_frac", cat, code, R)                the share of class ``code`` among the valid cells of the categorical raster ``cat`` -- a
                                                   land-cover RasterStack on the DEM's own grid, or (stack, layer) -- within the square
                                                   window of R cells (:func:`classes.focal`'s ``frac``; NaN where ``cat`` is NA)
@@ -555,9 +583,9 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                                                        else "no argument"))
             if lonlat:
                 raise ValueError(f"{e[0]!r} follows flow paths in metric cells: lonlat=True is out of scope (resample.resample onto a metric grid)")
-        if e[0] in BASIN_SPEC and len(e) != 1:
+        if (e[0] in BASIN_SPEC or e[0] in BASIN_QUANTILE_SPEC) and len(e) != 1:
             raise ValueError(f"{e[0]!r} takes no argument")
-        if e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
+        if e[0] in ZONE_SPEC or e[0] in ZONE_QUANTILE_SPEC or e[0] == DIST_FEATURES:
             from .vector import Features
             if len(e) != 2 or not isinstance(e[1], Features):
                 raise ValueError(f"{e[0]!r} takes one argument, a vector.Features in the DEM's coordinate system")
@@ -575,9 +603,10 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
     stream_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in STREAM_SPEC))
     flow_a = list(dict.fromkeys(float(e[1]) for e in spec if e[0] in FLOW_SPEC))
     basins = tuple(dict.fromkeys(BASIN_SPEC[e[0]] for e in spec if e[0] in BASIN_SPEC))
-    flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec) or bool(basins)
+    basins_q = tuple(dict.fromkeys(BASIN_QUANTILE_SPEC[e[0]] for e in spec if e[0] in BASIN_QUANTILE_SPEC))
+    flows = bool(flow_a) or any(e[0] == FLOW_OUTLET for e in spec) or bool(basins) or bool(basins_q)
     tv = [e[0] for e in spec if len(e) == 1 and e[0] not in HYDRO_SPEC and e[0] not in HYDRO_MFD_SPEC and e[0] not in DIST_SPEC and e[0] != FLOW_OUTLET
-          and e[0] not in PATCH_DIST_SPEC and e[0] not in BASIN_SPEC]
+          and e[0] not in PATCH_DIST_SPEC and e[0] not in BASIN_SPEC and e[0] not in BASIN_QUANTILE_SPEC]
     if tv:
         got = terrain(dem_stack, layer, tuple(dict.fromkeys(tv)), lonlat, z_factor, out_dtype=torch.float32)
         by_name.update(zip(dict.fromkeys(tv), got))
@@ -592,8 +621,8 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
                 by_name.update(_stream_layers(dem_stack, demf, hp["flowacc"], stream_a, spec))
             if flows and call is hydro:
                 by_name.update(_flow_layers(dem_stack, demf, hp["flowdir"], hp.get("flowacc"), flow_a, spec, layer))
-            if basins and call is hydro:
-                by_name.update(_basin_layers(dem_stack, hp["flowdir"], basins, layer))
+            if (basins or basins_q) and call is hydro:
+                by_name.update(_basin_layers(dem_stack, hp["flowdir"], basins, layer, basins_q))
             for n in hv:
                 product, log = table[n]
                 by_name[n] = (torch.log(hp[product]) if log else hp[product]).to(torch.float32)
@@ -627,7 +656,7 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             keep = _patches.sieve(dem_stack, layer, where, float(e[1]) if n_args == 2 else None, 8, min_size=int(e[-1]) if n_args else 1,
                                   edge="any" if n_args else "touching")
             by_name[e] = _prox.proximity(keep, products="dist", unit=g.xres, out_dtype=torch.float32)[0]
-    if any(e[0] in ZONE_SPEC or e[0] == DIST_FEATURES for e in spec):
+    if any(e[0] in ZONE_SPEC or e[0] in ZONE_QUANTILE_SPEC or e[0] == DIST_FEATURES for e in spec):
         by_name.update(_vector_layers(dem_stack, spec, layer))
     if any(e[0] in CLASS_SPEC for e in spec):
         by_name.update(_class_layers(dem_stack, spec))
@@ -636,7 +665,7 @@ def covariates(dem_stack: RasterStack, spec=("slope_deg", ("above_min", 17)), la
             cat, cat_layer, *rest = _class_entry(e)
             planes[1 + k] = by_name[(e[0], id(cat), cat_layer) + tuple(rest)]
             names.append(e[0] + "_".join(str(v) for v in rest))
-        elif e[0] in ZONE_SPEC or e[0] == DIST_FEATURES:
+        elif e[0] in ZONE_SPEC or e[0] in ZONE_QUANTILE_SPEC or e[0] == DIST_FEATURES:
             planes[1 + k] = by_name[(e[0], id(e[1]))]
             names.append(e[0])
         elif e[0] in PATCH_DIST_SPEC:

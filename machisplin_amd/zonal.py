@@ -10,8 +10,13 @@ All work on the cells runs in libmachisplin_hip.so (csrc/zonal.hip); this module
 
 The classes of a CATEGORICAL layer per zone -- counts, fractions, the mode -- are :func:`classes.crosstab`.
 
-Out of scope: median and mode per zone, zones given as floats, more than 2^31 - 1 cells, weights (a cell's area on a lon/lat
-grid).
+ORDER STATISTICS -- the median or any quantile per zone, per coarse cell (:func:`aggregate_quantile`) or of the whole layer, and a
+cell's rank inside its zone -- are :func:`quantile` (section "zonal quantiles", csrc/quantile.hip): the cells' (zone, q) keys go
+through the library's deterministic radix sort (:func:`sort_keys`, csrc/sort_keys.hip), and every quantile is a look-up.
+
+Out of scope: the mode per zone here (:func:`classes.crosstab` has it), zones given as floats, more than 2^31 - 1 cells, weights (a
+cell's area on a lon/lat grid); for quantiles also window medians, types other than 7, mid-rank percentiles, more than 16
+probabilities per call.
 """
 from __future__ import annotations
 
@@ -137,3 +142,171 @@ def zonal(stack, zones, layer=0, stats=("mean",), planes=(), n_zones=None, table
         k = info["n_present"]
         tab_out = {"zone": zone[:k], **{n: v[:k] for n, v in tab_out.items()}}
     return tab_out, pl_out, info
+
+
+QUANTILE_PLANES = ("q", "below", "frac_below")
+MAX_PROBS = 16
+
+
+def _check_quantile(stack, zones, probs, layer, planes, n_zones, table, quantum, out_dtype, target=None):
+    """every argument check of :func:`quantile` and :func:`aggregate_quantile`, before any device call: (probs, planes, n_zones, quantum)"""
+    import torch
+    if table not in TABLES:
+        raise ValueError(f"unknown table {table!r}: one of 'dense', 'present' or None")
+    try:
+        probs = tuple(float(p) for p in ((probs,) if isinstance(probs, (int, float)) else probs))
+    except (TypeError, ValueError):
+        raise ValueError("probs must be a sequence of numbers in [0, 1]") from None
+    if not 1 <= len(probs) <= MAX_PROBS:
+        raise ValueError(f"probs must hold 1 .. {MAX_PROBS} probabilities, not {len(probs)}")
+    for p in probs:
+        if not 0.0 <= p <= 1.0:                                            # NaN fails both comparisons
+            raise ValueError(f"probs: {p!r} is not in [0, 1]")
+    planes = _names("planes", planes, QUANTILE_PLANES)
+    if table is None and not planes:
+        raise ValueError("no output: table is None and planes is empty")
+    if zones is not None and target is not None:
+        raise ValueError("zones and a target grid are both given: a cell's zone is one or the other")
+    g = stack.geom
+    if zones is not None and (not isinstance(zones, torch.Tensor) or zones.dim() != 2 or zones.dtype.is_floating_point or zones.dtype.is_complex
+                              or zones.dtype == torch.bool):
+        raise ValueError("zones must be a 2-D integer tensor or None (zones given as floats are out of scope)")
+    if not 0 <= int(layer) < stack.n_layers:
+        raise ValueError(f"layer {layer} is not one of the stack's {stack.n_layers} layers")
+    if g.nrow < 1 or g.ncol < 1:
+        raise ValueError("the grid has no cell (nrow, ncol)")
+    if g.nrow * g.ncol > INT32_MAX:
+        raise ValueError(f"grid too large: nrow * ncol = {g.nrow * g.ncol} passes 2^31 - 1")
+    if zones is not None and tuple(zones.shape) != (g.nrow, g.ncol):
+        raise ValueError(f"shape mismatch: zones is {tuple(zones.shape)}, the stack's grid ({g.nrow}, {g.ncol})")
+    if target is not None and (target.nrow < 1 or target.ncol < 1 or target.nrow * target.ncol > INT32_MAX or not target.xres > 0 or not target.yres > 0):
+        raise ValueError("geom: the target grid needs 1 .. 2^31 - 1 cells and positive resolutions")
+    if n_zones is not None:
+        if zones is None:
+            raise ValueError("n_zones goes with a zone plane: without one it follows from the target grid, or is 1")
+        n_zones = int(n_zones)
+        if not 1 <= n_zones <= INT32_MAX:
+            raise ValueError(f"n_zones must be in 1 .. 2^31 - 1 (a zone is an int32), not {n_zones}")
+    if quantum is not None:
+        quantum = float(quantum)
+        if not (2.0 ** -1022 <= quantum <= 2.0 ** 1023) or math.frexp(quantum)[0] != 0.5:
+            raise ValueError(f"quantum must be a power of two in 2^-1022 .. 2^1023, not {quantum!r}")
+    if out_dtype not in (None, torch.float64, torch.float32):
+        raise ValueError("out_dtype must be torch.float64 or torch.float32")
+    return probs, planes, n_zones, quantum
+
+
+def _quantile(stack, zones, probs, layer, planes, n_zones, table, quantum, out_dtype, stream, target):
+    import torch
+    out_dtype = out_dtype or torch.float64
+    g = stack.geom
+    src = stack.planes
+    dev = src.device
+    if zones is not None and (zones.device != dev or zones.dtype != torch.int32 or zones.stride(1) != 1):
+        zones = zones.to(device=dev, dtype=torch.int32).contiguous()
+    cg = g.c_struct()
+    ct = target.c_struct() if target is not None else None
+    dt = {torch.float64: _lib.F64, torch.float32: _lib.F32, torch.int16: _lib.I16}[src.dtype]
+    cs = _lib.Stack(src.data_ptr(), src.shape[0], dt, src.stride(0), src.stride(1), stack.nodata)
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    cp = (C.c_double * len(probs))(*probs)
+    info = _lib.QuantileInfo()
+
+    def call(tab, pl, nz, q):
+        _lib.check(_lib.lib().mhs_zonal_quantile_dev(C.byref(cg), C.byref(cs), int(layer), zones.data_ptr() if zones is not None else None,
+                                                     zones.stride(0) if zones is not None else 0, nz or 0, q or 0.0, 0, cp, len(probs),
+                                                     C.byref(ct) if ct is not None else None, C.byref(tab) if tab is not None else None,
+                                                     C.byref(pl) if pl is not None else None, st, C.byref(info)))
+
+    if zones is None:
+        rows_dense = target.nrow * target.ncol if target is not None else 1
+    elif table == "dense" and n_zones is None:                   # the library measures n_zones (and the quantum) before the table is sized
+        call(None, None, None, quantum)
+        n_zones, quantum = info.n_zones, info.quantum
+        rows_dense = n_zones
+    else:
+        rows_dense = n_zones
+    tab = tab_out = zone = None
+    if table is not None:
+        rows = rows_dense if table == "dense" else min(rows_dense or g.nrow * g.ncol, g.nrow * g.ncol)
+        tab_out = {"q": torch.empty((rows, len(probs)), dtype=torch.float64, device=dev), "count": torch.empty(rows, dtype=torch.int64, device=dev)}
+        zone = torch.empty(rows, dtype=torch.int32, device=dev) if table == "present" else None
+        tab = _lib.QuantileTable(rows, zone.data_ptr() if zone is not None else None, tab_out["count"].data_ptr(), tab_out["q"].data_ptr())
+    pl = None
+    pl_out = {}
+    if planes:
+        pl = _lib.QuantilePlanes()
+        pl.dtype = _lib.F64 if out_dtype == torch.float64 else _lib.F32
+        if "q" in planes:
+            pl_out["q"] = torch.empty((len(probs), g.nrow, g.ncol), dtype=out_dtype, device=dev)
+            for j in range(len(probs)):
+                pl.q[j], pl.ld_q[j] = pl_out["q"][j].data_ptr(), g.ncol
+        if "below" in planes:
+            pl_out["below"] = torch.empty((g.nrow, g.ncol), dtype=torch.int32, device=dev)
+            pl.below, pl.ld_below = pl_out["below"].data_ptr(), g.ncol
+        if "frac_below" in planes:
+            pl_out["frac_below"] = torch.empty((g.nrow, g.ncol), dtype=out_dtype, device=dev)
+            pl.frac_below, pl.ld_frac_below = pl_out["frac_below"].data_ptr(), g.ncol
+        pl_out = {n: pl_out[n] for n in planes}
+    call(tab, pl, n_zones if zones is not None else None, quantum)
+    info = {k: getattr(info, k) for k, _ in _lib.QuantileInfo._fields_}
+    if table == "present":
+        k = info["n_present"]
+        tab_out = {"zone": zone[:k], "q": tab_out["q"][:k], "count": tab_out["count"][:k]}
+    return tab_out, pl_out, info
+
+
+def quantile(stack, zones=None, probs=(0.5,), layer=0, planes=(), n_zones=None, table="dense", quantum=None, out_dtype=None, stream=None):
+    """The quantiles ``probs`` (1 .. 16 probabilities in [0, 1]; R's type 7, numpy's ``linear``) of layer ``layer`` inside each zone
+    of ``zones`` (include/machisplin_hip.h, section "zonal quantiles"); ``zones=None``: the whole layer is zone 0.  Membership,
+    NA, ``n_zones``, ``quantum`` and ``info["n_inexact"]`` are :func:`zonal`'s: the quantiles are those of ``q = rint(v /
+    quantum)``, ``p = 0`` and ``p = 1`` equal ``zonal``'s ``min`` and ``max`` bit for bit, and with ``n_inexact == 0`` the median
+    equals ``numpy.median`` of the zone's values bit for bit.
+
+    ``table="dense"`` gives ``{"q": [n_zones, n_probs] float64, "count": [n_zones] int64}``; ``"present"`` only the zones with a
+    contributing cell, ascending, with ``"zone"`` -- it allocates nothing proportional to ``n_zones``, the form for cell-number
+    labels --; None no table.  ``planes`` names some of :data:`QUANTILE_PLANES`: ``q`` (``[n_probs, nrow, ncol]``: each cell
+    receives its zone's quantiles, NaN without a zone), ``below`` (int32: the contributing cells of the cell's zone with a smaller
+    value, -1 where the cell does not contribute) and ``frac_below`` (``below / n``, NaN likewise); float planes are ``out_dtype``.
+
+    Returns ``(table, planes, info)``; ``info`` has the fields of mhs_quantile_info (zonal's, ``n_present`` counting the zones with
+    a contributing cell, and ``passes_run``, ``scratch_bytes``)."""
+    probs, planes, n_zones, quantum = _check_quantile(stack, zones, probs, layer, planes, n_zones, table, quantum, out_dtype)
+    return _quantile(stack, zones, probs, layer, planes, n_zones, table, quantum, out_dtype, stream, None)
+
+
+def aggregate_quantile(stack, geom, probs=(0.5,), layer=0, quantum=None, out_dtype=None, stream=None):
+    """``terra::aggregate(fun = median)`` and its quantiles: layer ``layer`` on the grid ``geom`` (same coordinate system, any
+    resolution, origin and extent), a target cell taking the source cells whose centre lies in it -- the footprints of
+    ``resample.resample``'s aggregates, so ``p = 0``, ``p = 1`` and the count equal its ``min``, ``max`` and ``count``.
+
+    Returns ``(planes [n_probs, geom.nrow, geom.ncol], count plane [geom.nrow, geom.ncol] int64, info)``; a target cell without a
+    contributing source cell holds NaN and count 0."""
+    import torch
+    probs, _, _, quantum = _check_quantile(stack, None, probs, layer, (), None, "dense", quantum, out_dtype, target=geom)
+    table, _, info = _quantile(stack, None, probs, layer, (), None, "dense", quantum, None, stream, geom)
+    q = table["q"].t().contiguous().reshape(len(probs), geom.nrow, geom.ncol)
+    if out_dtype == torch.float32:
+        q = q.to(torch.float32)
+    return q, table["count"].reshape(geom.nrow, geom.ncol), info
+
+
+def sort_keys(keys, bit_lo=0, bit_hi=64, stream=None):
+    """Sort a 1-D uint64 (or int64, read as uint64) device tensor ascending IN PLACE by its bits ``bit_lo .. bit_hi - 1`` with the
+    library's deterministic radix sort (include/machisplin_hip.h, section "sort"); the caller guarantees that the keys agree
+    outside that window.  Returns ``{"passes_run", "scratch_bytes"}``."""
+    import torch
+    if not isinstance(keys, torch.Tensor) or keys.dim() != 1 or keys.dtype not in (torch.uint64, torch.int64):
+        raise ValueError("keys must be a 1-D uint64 or int64 tensor")
+    if keys.numel() > 1 and keys.stride(0) != 1:
+        raise ValueError("keys must be contiguous")
+    if keys.numel() > INT32_MAX:
+        raise ValueError("keys: more than 2^31 - 1 keys")
+    if not 0 <= int(bit_lo) <= int(bit_hi) <= 64:
+        raise ValueError("bit_lo, bit_hi: the window needs 0 <= bit_lo <= bit_hi <= 64")
+    if not keys.is_cuda:
+        raise ValueError("keys must be a device tensor")
+    st = stream if stream is not None else torch.cuda.current_stream(keys.device).cuda_stream
+    info = _lib.SortInfo()
+    _lib.check(_lib.lib().mhs_sort_keys_dev(keys.data_ptr() if keys.numel() else None, keys.numel(), int(bit_lo), int(bit_hi), st, C.byref(info)))
+    return {"passes_run": info.passes_run, "scratch_bytes": info.scratch_bytes}
